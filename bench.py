@@ -19,13 +19,19 @@ real dataset); every step runs the full on-device augmentation (random crop 32/p
 horizontal flip, normalise) — nothing is skipped inside the timed region.
 Weights: random init of the real architecture (21.8 M parameters).
 
-After the timed steps a real epoch is MEASURED (not derived): every rank trains
-ceil(50000 / N / B) full batches of its shard, BN statistics are averaged over the
+A plain run does only what the headline figure needs: set up, W warm-up steps, K timed
+steps, one JSON line.  ``--dump-outputs DIR`` also writes what the last timed step computed
+(see :func:`dump_outputs`), so two builds can be compared output for output: with the same
+arguments the data, the initial weights and the augmentation draws are the same in every run.
+
+With ``--full`` a real epoch is MEASURED (not derived) after the timed steps: every rank
+trains ceil(50000 / N / B) full batches of its shard, BN statistics are averaged over the
 ranks, then the 10,000-image validation set is evaluated (sharded over the ranks),
-the reference's epoch time definition (ml/pkg/train/job.go:222-231, 327).
+the reference's epoch time definition (ml/pkg/train/job.go:222-231, 327); at N = 1 the
+same epoch is also run through the whole framework (``--e2e``).
 
 Usage:
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     N > 1 without WORLD_SIZE in the environment: the script launches N ranks itself
     (torch.distributed.run, one process per GPU, RCCL over xGMI) before touching the GPU.
   python bench.py --gpus N --cpu-smoke   (gloo on CPU: proves the N-rank launch path)
@@ -67,7 +73,12 @@ def parse():
                     help="run the RCCL all-reduce path even with one rank (single-GPU rehearsal of dp>1)")
     ap.add_argument("--graph-comm", choices=["on", "off"], default="on",
                     help="capture the RCCL all-reduces inside the step's hipGraph (off: eager between segment graphs)")
-    ap.add_argument("--no-epoch", action="store_true", help="skip the measured epoch after the timed steps")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure a whole epoch with validation and (see --e2e) the "
+                         "same epoch through the framework; off: only the headline figure")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32; rank 0)")
+    ap.add_argument("--no-epoch", action="store_true", help="with --full: skip the measured epoch")
     ap.add_argument("--comm-dtype", choices=["fp32", "bf16"], default="fp32",
                     help="gradient all-reduce precision (bf16 = compressed, half the xGMI bytes)")
     ap.add_argument("--comm-plan", default="auto",
@@ -76,12 +87,19 @@ def parse():
     ap.add_argument("--comm-timing", type=int, default=20,
                     help="sample the in-graph gradient all-reduce time every N steps (0 = off)")
     ap.add_argument("--e2e", choices=["auto", "on", "off"], default="auto",
-                    help="also run the epoch through the whole framework (server, worker, storage, kubeml "
-                         "train; kubeml_amd/experiments/e2e.py) and report e2e_epoch_time_s (auto: N = 1)")
+                    help="with --full: also run the epoch through the whole framework (server, worker, storage, "
+                         "kubeml train; kubeml_amd/experiments/e2e.py) and report e2e_epoch_time_s (auto: N = 1)")
     ap.add_argument("--cpu-smoke", action="store_true", help="gloo/CPU rehearsal of the N-rank launch (tiny model)")
     ap.add_argument("--trace", default=None, help="write a Chrome trace (device compute/comm timeline) to this dir; "
                                                   "collectives then run outside the step graph")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.e2e == "on" and not args.full:
+        ap.error("--e2e on needs --full")
+    if not args.full:       # the plain run: the timed steps only
+        args.no_epoch, args.e2e = True, "off"
+    return args
 
 
 def _free_port():
@@ -309,6 +327,8 @@ def main():
         in_sync = bool((hi - lo).abs().item() <= 1e-9 * max(1.0, abs(hi.item())))
     ms = dt / args.steps * 1e3
     img_s = B * world * args.steps / dt
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, space)
 
     epoch = None
     if not args.no_epoch:
@@ -370,6 +390,42 @@ def main():
         out.update(measure_e2e(img_s))
     if rank == 0:
         print(json.dumps(out), file=json_out, flush=True)
+
+
+DUMP_SAMPLE = 7 * 1024 * 1024   # elements kept of each flat buffer (29.4 MB as float32)
+
+
+def dump_outputs(directory, loss, space):
+    """What a caller of the timed step holds after its last call, as float32 ``.npy`` files:
+
+    * ``loss``     the loss the step returned
+    * ``weights``  the fp32 master weights the step's SGD left (flat parameter space)
+    * ``grads``    the gradients of that step (same layout)
+    * ``bn_stats`` every floating-point module buffer (BN running mean / variance), whole
+
+    When the space is larger than DUMP_SAMPLE, ``weights`` and ``grads`` hold the same fixed
+    sample of DUMP_SAMPLE flat positions (sorted; drawn with a constant seed, so it depends
+    only on the space's size): a third of ResNet-34's space, under 59 MB in all."""
+    import numpy as np
+    import torch
+    os.makedirs(directory, exist_ok=True)
+    torch.cuda.synchronize()
+    n = space.numel
+    idx = None
+    if n > DUMP_SAMPLE:
+        pick = np.sort(np.random.default_rng(20240607).choice(n, size=DUMP_SAMPLE, replace=False))
+        idx = torch.from_numpy(pick).to(space.master.device)
+
+    def host(t):
+        t = t.detach().reshape(-1)
+        if idx is not None and t.numel() == n:
+            t = t.index_select(0, idx)
+        return t.to(torch.float32).cpu().numpy()
+    bufs = [getattr(m, name).detach().reshape(-1).to(torch.float32) for m, name in space.float_buffers]
+    arrays = {"loss": host(loss), "weights": host(space.master), "grads": host(space.grad),
+              "bn_stats": (torch.cat(bufs) if bufs else torch.zeros(0)).cpu().numpy()}
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def measure_e2e(bench_img_s):

@@ -6,7 +6,7 @@
   momentum 0.9 / dampening 0.1 across a ``reset_state()`` (device first-step flag).
 * K-AVG pack/finish kernels on the flat state buffer: divisor from the device count
   slot, bf16 shadow refresh, int64 counters floored back (reference integer division).
-* ``bench.py`` end to end: the default path (timed steps + a measured epoch with
+* ``bench.py`` end to end: the ``--full`` path (timed steps + a measured epoch with
   validation) and the 1-rank RCCL rehearsal of the captured, overlapped all-reduce.
 """
 import json
@@ -158,17 +158,42 @@ def _bench(*extra, timeout=600):
 
 
 def test_bench_measures_epoch_with_validation():
-    d = _bench("--steps", "10", "--warmup", "2", "--batch", "128", "--e2e", "off")
+    d = _bench("--full", "--steps", "10", "--warmup", "2", "--batch", "128", "--e2e", "off")
     assert d["n_gpus"] == 1 and d["value"] > 0 and d["epoch_measured"] is True
     assert d["val_images"] >= 10000 and d["epoch_time_s"] > d["epoch_train_s"] > 0
     assert d["loss_first_last"][1] == d["loss_first_last"][1]
     assert "e2e_epoch_time_s" not in d
 
 
+def test_bench_plain_run_is_lean_and_dumps_reproducible_outputs(tmp_path):
+    """Without --full only the timed steps run (no epoch, no e2e keys); --dump-outputs writes
+    the last step's loss / weights / gradients / BN statistics as float32 arrays, at most 64 MB,
+    bitwise equal between two runs with the same arguments."""
+    import numpy as np
+
+    def run(name, steps):
+        d = _bench("--gpus", "1", "--steps", str(steps), "--warmup", "1", "--batch", "64", "--dump-outputs",
+                   str(tmp_path / name))
+        assert d["steps"] == steps and d["ms_per_step"] > 0 and d["value"] > 0 and d["dtype"] == "bf16"
+        assert not any(k.startswith(("epoch_", "e2e_", "val_")) for k in d), sorted(d)
+        files = sorted(p.name for p in (tmp_path / name).iterdir())
+        assert files == ["bn_stats.npy", "grads.npy", "loss.npy", "weights.npy"], files
+        out = {f[:-4]: np.load(tmp_path / name / f) for f in files}
+        assert all(a.dtype == np.float32 and a.size > 0 and np.isfinite(a).all() for a in out.values())
+        assert sum(a.nbytes for a in out.values()) <= 64e6
+        return d, out
+    da, a = run("a", 3)
+    _, b = run("b", 3)
+    assert a["loss"].shape == (1,) and abs(float(a["loss"][0]) - da["loss_first_last"][1]) < 1e-3
+    assert np.abs(a["grads"]).max() > 0 and np.abs(a["weights"]).max() > 0
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+
+
 def test_bench_reports_the_framework_epoch():
-    """bench.py's default (N = 1) also runs the epoch through the whole stack: server, worker,
+    """bench.py --full (N = 1) also runs the epoch through the whole stack: server, worker,
     storage upload, `kubeml train` with validation every epoch (experiments/e2e.py)."""
-    d = _bench("--steps", "10", "--warmup", "2", "--e2e", "on", timeout=900)
+    d = _bench("--full", "--steps", "10", "--warmup", "2", "--e2e", "on", timeout=900)
     assert d.get("e2e_error") is None, d.get("e2e_error")
     assert d["e2e_epoch_time_s"] > 0 and len(d["e2e_epoch_wall_s"]) == 4 and d["e2e_warmup_epochs"] == 2
     assert d["e2e_total_s"] >= sum(d["e2e_epoch_wall_s"]) - 1e-3
