@@ -39,6 +39,17 @@
 //   (deterministic) and runs the epilogue; tickets are reset by the last arriver
 //   (graph-replay safe, no memset per call).  WGRAD uses the same slabs: one writer per
 //   weight-gradient element, stored (or added) without atomics.
+// * Kernel variants (the plan's variant code): 0 register-staged pipeline (IgemmBody), 1 / 2
+//   LDS-DMA pipeline with 3 / 4 stages (GldsBody), 3 direct LDS-free (DirectBody), 4 halo patch
+//   (HaloBody), 5 one-shot panels (OneShotBody forward, OneShotBwdBody dgrad / wgrad), 6 stem
+//   patch (StemBody / StemRowsBody), 8 folded one-shot wgrad of an unrolled 2x2-map conv
+//   (OneShotFold22Body, only inside k_conv_pair).
+// * The dgrad and the wgrad of one conv run as ONE launch (k_conv_pair, KML_PAIR_LIST): halo /
+//   register-staged / direct dgrad bodies next to the register-staged wgrad, and for the
+//   latency-bound single-tap convs (ResNet-34 layer3 unrolled on 2x2 maps, layer4 centre tap on
+//   1x1 maps) the one-shot dgrad next to a one-shot wgrad — for the unrolled convs the folded
+//   body, which chains the (p, q) sub-GEMMs of a 3x3 tap and writes dw[K][3][3][C] directly (no
+//   1x1-form scratch, no fold pass).
 // * Epilogues: FWD bias / ReLU / per-channel BatchNorm sum+sumsq from the fp32 values
 //   (BN needs no statistics pass); DGRAD adds an optional bf16 addend (the other
 //   branch of a residual block) so gradient merges need no add kernel.
@@ -1928,21 +1939,25 @@ struct OneShotBody {
 // DMA source address) and read with ds_read_b64_tr_b16 (frag_kstrided).
 //   DGRAD: dX[m][c] = sum_k dY[m][k] W'[k][c]   (A = dY rows, K = Cout)
 //   WGRAD: dW'[k][c] = sum_m dY[m][k] X[m][c]   (K = pixels; both panels K-strided)
-template <int MODE, int BM, int BN, int KD>
+template <int MODE, int BM, int BN, int KD, int NH = 1>
 struct OneShotBwdBody {
   static_assert(MODE == DGRAD || MODE == WGRAD, "one-shot backward: dgrad / wgrad");
+  static_assert(NH == 1 || MODE == DGRAD, "K in passes: dgrad only");
   static constexpr bool A_KC = MODE == DGRAD;             // A K-contiguous (dY rows) or K-strided
-  static constexpr int A_BYTES = BM * KD * 2, B_BYTES = BN * KD * 2;
+  // NH > 1: the K axis is taken in NH passes of KP (panels of KD / NH rows, so two blocks of a
+  // K = 1024 dgrad fit one CU's LDS and overlap each other's round trip)
+  static constexpr int KP = KD / NH;
+  static constexpr int A_BYTES = BM * KP * 2, B_BYTES = BN * KP * 2;
   static constexpr int WM = BM / 2, WN = BN / 2, MR = WM / 16, NR = WN / 16;
   static constexpr int NIA = A_BYTES / 1024, NIB = B_BYTES / 1024;
   static constexpr int SMEM_EPI = 16 + BM * (BN + 8) * 2 + 2 * BN * 4;
   static constexpr int SMEM = A_BYTES + B_BYTES > SMEM_EPI ? A_BYTES + B_BYTES : SMEM_EPI;
   static constexpr int THREADS = 256;
-  static_assert(NIA % 4 == 0 && NIB % 4 == 0 && (KD / 8) % 16 == 0, "one-shot panel shape");
+  static_assert(KD % NH == 0 && NIA % 4 == 0 && NIB % 4 == 0 && (KP / 8) % 16 == 0, "one-shot panel shape");
   static_assert((BM == 32 || BM == 64) && (BN == 32 || BN == 64), "K-strided tiles of 32 / 64 columns");
   static_assert(SMEM <= 160 * 1024, "one-shot panels exceed LDS");
 
-  // one 16-byte chunk of a K-strided [KD][R] tile: DMA slot L -> (k row, logical chunk)
+  // one 16-byte chunk of a K-strided [KP][R] tile: DMA slot L -> (k row, logical chunk)
   template <int R>
   __device__ __forceinline__ static void ks_slot(int L, int& k, int& lc) {
     k = L / (R / 8);
@@ -1955,50 +1970,10 @@ struct OneShotBwdBody {
     const int tapoff = (a.r0 * a.KW + a.s0) * a.C;
     char* const sA = smem;
     char* const sB = smem + A_BYTES;
-#pragma unroll
-    for (int j = 0; j < NIA / 4; ++j) {
-      const int u = j * 4 + wave, L = u * 64 + lane;
-      const bf16_t* src;
-      if constexpr (MODE == DGRAD) {  // dY rows [BM][KD], chunk ^ (row & 15)
-        const int row = L / (KD / 8), lc = (L % (KD / 8)) ^ (row & 15), m = m0 + row;
-        src = m < a.M ? a.dy + (long long)m * a.K + lc * 8 : a.zp;
-      } else {                        // dY as [KD pixels][BM out-channels]
-        int k, lc;
-        ks_slot<BM>(L, k, lc);
-        const int col = m0 + lc * 8;
-        src = (k < a.Kd && col < a.M) ? a.dy + (long long)k * a.K + col : a.zp;
-      }
-      __builtin_amdgcn_global_load_lds((const void*)src, (__attribute__((address_space(3))) void*)(sA + u * 1024),
-                                       16, 0, 0);
-    }
-#pragma unroll
-    for (int j = 0; j < NIB / 4; ++j) {
-      const int u = j * 4 + wave, L = u * 64 + lane;
-      int k, lc;
-      ks_slot<BN>(L, k, lc);
-      const int col = n0 + lc * 8;
-      const bf16_t* src = a.zp;
-      if constexpr (MODE == DGRAD) {  // W'[k][col]: k = output channel, col = input channel
-        if (k < a.K && col < a.N) {
-          if (a.g22) {
-            const int p = fdiv(k, a.fd_gK), q = fdiv(col, a.fd_gC);
-            src = a.w + ((long long)(k - p * a.fd_gK.d) * 9 + tap22(p, q)) * a.fd_gC.d + (col - q * a.fd_gC.d);
-          } else {
-            src = a.w + (long long)k * a.KH * a.KW * a.C + tapoff + col;
-          }
-        }
-      } else {                        // X as [KD pixels][BN in-channels]
-        if (k < a.Kd && col < a.N) src = a.x + (long long)k * a.C + col;
-      }
-      __builtin_amdgcn_global_load_lds((const void*)src, (__attribute__((address_space(3))) void*)(sB + u * 1024),
-                                       16, 0, 0);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
     auto rdA = [&](int i, int ks) -> bf16x8_t {
       if constexpr (A_KC) {
         const int row = wm * WM + i * 16 + (lane & 15), c = 4 * ks + (lane >> 4);
-        return *reinterpret_cast<const bf16x8_t*>(sA + (row * (KD / 8) + (c ^ (row & 15))) * 16);
+        return *reinterpret_cast<const bf16x8_t*>(sA + (row * (KP / 8) + (c ^ (row & 15))) * 16);
       } else {
         return frag_kstrided<BM>(reinterpret_cast<const bf16_t*>(sA), wm * WM + i * 16, ks, lane);
       }
@@ -2011,29 +1986,177 @@ struct OneShotBwdBody {
     for (int i = 0; i < MR; ++i)
 #pragma unroll
       for (int j = 0; j < NR; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-    constexpr int KS = KD / 32;
-    bf16x8_t af[2][MR], bf[2][NR];
 #pragma unroll
-    for (int i = 0; i < MR; ++i) af[0][i] = rdA(i, 0);
+    for (int h = 0; h < NH; ++h) {
+      const int kh = h * KP;  // first K row of this pass
+      if (h) __syncthreads();  // every wave has read the previous pass's panels
 #pragma unroll
-    for (int j = 0; j < NR; ++j) bf[0][j] = rdB(j, 0);
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-      if (ks + 1 < KS) {
-#pragma unroll
-        for (int i = 0; i < MR; ++i) af[(ks + 1) & 1][i] = rdA(i, ks + 1);
-#pragma unroll
-        for (int j = 0; j < NR; ++j) bf[(ks + 1) & 1][j] = rdB(j, ks + 1);
+      for (int j = 0; j < NIA / 4; ++j) {
+        const int u = j * 4 + wave, L = u * 64 + lane;
+        const bf16_t* src;
+        if constexpr (MODE == DGRAD) {  // dY rows [BM][KP], chunk ^ (row & 15)
+          const int row = L / (KP / 8), lc = (L % (KP / 8)) ^ (row & 15), m = m0 + row;
+          src = m < a.M ? a.dy + (long long)m * a.K + kh + lc * 8 : a.zp;
+        } else {                        // dY as [KD pixels][BM out-channels]
+          int k, lc;
+          ks_slot<BM>(L, k, lc);
+          const int col = m0 + lc * 8;
+          src = (k < a.Kd && col < a.M) ? a.dy + (long long)k * a.K + col : a.zp;
+        }
+        __builtin_amdgcn_global_load_lds((const void*)src, (__attribute__((address_space(3))) void*)(sA + u * 1024),
+                                         16, 0, 0);
       }
 #pragma unroll
-      for (int i = 0; i < MR; ++i)
+      for (int j = 0; j < NIB / 4; ++j) {
+        const int u = j * 4 + wave, L = u * 64 + lane;
+        int k, lc;
+        ks_slot<BN>(L, k, lc);
+        const int col = n0 + lc * 8;
+        const bf16_t* src = a.zp;
+        if constexpr (MODE == DGRAD) {  // W'[k][col]: k = output channel, col = input channel
+          k += kh;
+          if (k < a.K && col < a.N) {
+            if (a.g22) {
+              const int p = fdiv(k, a.fd_gK), q = fdiv(col, a.fd_gC);
+              src = a.w + ((long long)(k - p * a.fd_gK.d) * 9 + tap22(p, q)) * a.fd_gC.d + (col - q * a.fd_gC.d);
+            } else {
+              src = a.w + (long long)k * a.KH * a.KW * a.C + tapoff + col;
+            }
+          }
+        } else {                        // X as [KD pixels][BN in-channels]
+          if (k < a.Kd && col < a.N) src = a.x + (long long)k * a.C + col;
+        }
+        __builtin_amdgcn_global_load_lds((const void*)src, (__attribute__((address_space(3))) void*)(sB + u * 1024),
+                                         16, 0, 0);
+      }
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
+      constexpr int KS = KP / 32;
+      bf16x8_t af[2][MR], bf[2][NR];
 #pragma unroll
-        for (int j = 0; j < NR; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[ks & 1][i], bf[ks & 1][j], acc[i][j], 0, 0, 0);
+      for (int i = 0; i < MR; ++i) af[0][i] = rdA(i, 0);
+#pragma unroll
+      for (int j = 0; j < NR; ++j) bf[0][j] = rdB(j, 0);
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks) {
+        if (ks + 1 < KS) {
+#pragma unroll
+          for (int i = 0; i < MR; ++i) af[(ks + 1) & 1][i] = rdA(i, ks + 1);
+#pragma unroll
+          for (int j = 0; j < NR; ++j) bf[(ks + 1) & 1][j] = rdB(j, ks + 1);
+        }
+#pragma unroll
+        for (int i = 0; i < MR; ++i)
+#pragma unroll
+          for (int j = 0; j < NR; ++j)
+            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[ks & 1][i], bf[ks & 1][j], acc[i][j], 0, 0, 0);
+      }
     }
     __syncthreads();  // LDS is reused by the epilogue
     conv_epilogue<MODE, MR, NR, WM, WN, false, true>(a, acc, m0, n0, wm, wn, lane, tid, 0, 0,
                                                      reinterpret_cast<unsigned*>(smem));
+  }
+};
+
+// Folded one-shot WGRAD of an unrolled 2x2-map conv (1x1 form: dY rows [(p, k)], X rows
+// [(q, c)], p / q = output / input position): dW[k][tap][c] = sum over the (p, q) with
+// tap22(p, q) = tap of sum_m dY[m][(p, k)] X[m][(q, c)], written straight onto the 3x3 taps (no
+// 1x1-form scratch, no fold pass).  A block owns a 16 k x 16 c tile of all 9 taps (one writer
+// per element: no split-K, no atomics).  Its panels are the K-strided [KD pixels][64] images of
+// the 4 position segments of the k range (dY) and of the c range (X), requested at once by
+// LDS-DMA like OneShotBwdBody<WGRAD>.  The 16 (p, q) sub-GEMMs are 4 per wave, each in its own
+// accumulator: wave 0 the centre tap (4 pairs), waves 1 / 2 two edge taps each (2 pairs per
+// tap), wave 3 the four corners; a tap's accumulators are added in pair order (deterministic).
+template <int KD>
+struct OneShotFold22Body {
+  static constexpr int TK = 16, TC = 16, R = 64;
+  static constexpr int P_BYTES = KD * R * 2;   // one panel
+  static constexpr int NI = P_BYTES / 1024;
+  static constexpr int SMEM = 2 * P_BYTES;
+  static constexpr int THREADS = 256;
+  static_assert(NI % 4 == 0 && KD % 32 == 0, "folded one-shot panel shape");
+
+  __device__ __forceinline__ static void run(const ConvArgs& a, const Blk& bk, char* smem) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int k0 = bk.y * TK, c0 = bk.x * TC;
+    const int Kq = a.fd_gK.d, Cq = a.fd_gC.d;
+    char* const sA = smem;
+    char* const sB = smem + P_BYTES;
+    // this wave's four (p, q) pairs, one byte each (p * 4 + q), grouped by tap
+    const unsigned pairs = wave == 0 ? 0x0F0A0500u : wave == 1 ? 0x07020D08u : wave == 2 ? 0x0B010E04u : 0x0306090Cu;
+    int pp[4], qq[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      pp[t] = (pairs >> (8 * t + 2)) & 3;
+      qq[t] = (pairs >> (8 * t)) & 3;
+    }
+    f32x4_t acc[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) acc[t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < NI / 4; ++j) {
+      const int u = j * 4 + wave, L = u * 64 + lane;
+      const int k = L / (R / 8), lc = (L % (R / 8)) ^ swz_ks<R>(k);  // pixel row, logical chunk
+      const int pos = lc >> 1, off = (lc & 1) * 8;                   // column lc * 8 = (position, channel)
+      const bf16_t* sa = (k < a.Kd && k0 + off < Kq) ? a.dy + (long long)k * a.K + pos * Kq + k0 + off : a.zp;
+      const bf16_t* sb = (k < a.Kd && c0 + off < Cq) ? a.x + (long long)k * a.C + pos * Cq + c0 + off : a.zp;
+      __builtin_amdgcn_global_load_lds((const void*)sa, (__attribute__((address_space(3))) void*)(sA + u * 1024),
+                                       16, 0, 0);
+      __builtin_amdgcn_global_load_lds((const void*)sb, (__attribute__((address_space(3))) void*)(sB + u * 1024),
+                                       16, 0, 0);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    constexpr int KS = KD / 32;
+    bf16x8_t af[2][4], bf[2][4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      af[0][t] = frag_kstrided<R>(reinterpret_cast<const bf16_t*>(sA), pp[t] * 16, 0, lane);
+      bf[0][t] = frag_kstrided<R>(reinterpret_cast<const bf16_t*>(sB), qq[t] * 16, 0, lane);
+    }
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+      if (ks + 1 < KS) {
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+          af[(ks + 1) & 1][t] = frag_kstrided<R>(reinterpret_cast<const bf16_t*>(sA), pp[t] * 16, ks + 1, lane);
+          bf[(ks + 1) & 1][t] = frag_kstrided<R>(reinterpret_cast<const bf16_t*>(sB), qq[t] * 16, ks + 1, lane);
+        }
+      }
+#pragma unroll
+      for (int t = 0; t < 4; ++t)
+        acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[ks & 1][t], bf[ks & 1][t], acc[t], 0, 0, 0);
+    }
+    // pairs per tap: 4 (centre), 2 (edges), 1 (corners); the first pair of a tap takes the sum
+    unsigned heads = 0xFu;
+    if (wave == 0) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) acc[0][e] = ((acc[0][e] + acc[1][e]) + acc[2][e]) + acc[3][e];
+      heads = 0x1u;
+    } else if (wave != 3) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        acc[0][e] += acc[1][e];
+        acc[2][e] += acc[3][e];
+      }
+      heads = 0x5u;
+    }
+    const int fr = lane & 15, fq = lane >> 4;
+    const int col = c0 + fr;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      if (!((heads >> t) & 1u) || col >= Cq) continue;
+      const int tap = tap22(pp[t], qq[t]);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int row = k0 + fq * 4 + e;
+        if (row < Kq) {
+          float* p = a.dw + ((long long)row * 9 + tap) * Cq + col;
+          if (a.accumulate) *p += acc[t][e];
+          else *p = acc[t][e];
+        }
+      }
+    }
   }
 };
 
@@ -2444,9 +2567,10 @@ __global__ __launch_bounds__(256) void k_conv_pair(ConvArgs ad, ConvArgs aw, int
 }
 
 // Instantiated pairs: X(dgrad variant, dgrad cfg bm, bn, bk, dgrad body, dgrad tile M, N,
-// wgrad body, wgrad tile M, N).  Variant codes as in plan_conv (0 = register-staged,
-// 3 = direct with bk = waves); the wgrad side is always the register-staged BK=64 kernel.
-// Any other combination runs as two launches (kml_conv_pair_supported).
+// wgrad body, wgrad tile M, N, wgrad variant, wgrad cfg bk).  Variant codes as in plan_conv
+// (0 = register-staged, 3 = direct with bk = waves, 4 = halo, 5 = one-shot panels, 8 = folded
+// one-shot wgrad of an unrolled conv).  Any other combination runs as two launches
+// (kml_conv_pair_supported).
 using DgIg3264 = IgemmBody<DGRAD, 32, 64, 64, true>;
 using DgIg3232 = IgemmBody<DGRAD, 32, 32, 64, true>;
 using DgDi3232 = DirectBody<DGRAD, 2, 2, 4, 4>;
@@ -2457,21 +2581,32 @@ using WgIg6432 = IgemmBody<WGRAD, 64, 32, 64, true>;
 // halo dgrad bodies (variant 4): the plan's bk slot carries Cout * 16 + H (the body's geometry)
 using DgHa64x8 = HaloBody<DGRAD, 64, 8, 1, 32, 1>;
 using DgHa128x4 = HaloBody<DGRAD, 128, 4, 4, 32, 1>;
-#define KML_PAIR_LIST(X)                                   \
-  X(4, 64, 32, 1032, DgHa64x8, 64, 32, WgIg3232, 32, 32)   \
-  X(4, 64, 32, 1032, DgHa64x8, 64, 32, WgIg6432, 64, 32)   \
-  X(4, 64, 32, 2052, DgHa128x4, 64, 32, WgIg3232, 32, 32)  \
-  X(4, 64, 32, 2052, DgHa128x4, 64, 32, WgIg6432, 64, 32)  \
-  X(0, 32, 64, 64, DgIg3264, 32, 64, WgIg3232, 32, 32)     \
-  X(0, 32, 64, 64, DgIg3264, 32, 64, WgIg6432, 64, 32)     \
-  X(0, 32, 32, 64, DgIg3232, 32, 32, WgIg3232, 32, 32)     \
-  X(0, 32, 32, 64, DgIg3232, 32, 32, WgIg6432, 64, 32)     \
-  X(3, 32, 32, 4, DgDi3232, 32, 32, WgIg3232, 32, 32)      \
-  X(3, 32, 32, 4, DgDi3232, 32, 32, WgIg6432, 64, 32)      \
-  X(3, 32, 16, 4, DgDi3216, 32, 16, WgIg3232, 32, 32)      \
-  X(3, 32, 16, 4, DgDi3216, 32, 16, WgIg6432, 64, 32)      \
-  X(3, 64, 32, 4, DgDi6432, 64, 32, WgIg3232, 32, 32)      \
-  X(3, 64, 32, 4, DgDi6432, 64, 32, WgIg6432, 64, 32)
+// one-shot bodies (variant 5): the dgrad plan's bk slot carries Cout (+ 1: K taken in two
+// halves), the wgrad plan's the panel depth in pixels (fewer pixels are zero-filled)
+using DgOs1024 = OneShotBwdBody<DGRAD, 32, 32, 1024>;
+using DgOs1024h = OneShotBwdBody<DGRAD, 32, 32, 1024, 2>;
+using DgOs512 = OneShotBwdBody<DGRAD, 32, 32, 512>;
+using WgOs256 = OneShotBwdBody<WGRAD, 32, 32, 256>;
+using WgFo256 = OneShotFold22Body<256>;
+constexpr int WV_FOLD22 = 8;
+#define KML_PAIR_LIST(X)                                          \
+  X(4, 64, 32, 1032, DgHa64x8, 64, 32, WgIg3232, 32, 32, 0, 64)   \
+  X(4, 64, 32, 1032, DgHa64x8, 64, 32, WgIg6432, 64, 32, 0, 64)   \
+  X(4, 64, 32, 2052, DgHa128x4, 64, 32, WgIg3232, 32, 32, 0, 64)  \
+  X(4, 64, 32, 2052, DgHa128x4, 64, 32, WgIg6432, 64, 32, 0, 64)  \
+  X(0, 32, 64, 64, DgIg3264, 32, 64, WgIg3232, 32, 32, 0, 64)     \
+  X(0, 32, 64, 64, DgIg3264, 32, 64, WgIg6432, 64, 32, 0, 64)     \
+  X(0, 32, 32, 64, DgIg3232, 32, 32, WgIg3232, 32, 32, 0, 64)     \
+  X(0, 32, 32, 64, DgIg3232, 32, 32, WgIg6432, 64, 32, 0, 64)     \
+  X(3, 32, 32, 4, DgDi3232, 32, 32, WgIg3232, 32, 32, 0, 64)      \
+  X(3, 32, 32, 4, DgDi3232, 32, 32, WgIg6432, 64, 32, 0, 64)      \
+  X(3, 32, 16, 4, DgDi3216, 32, 16, WgIg3232, 32, 32, 0, 64)      \
+  X(3, 32, 16, 4, DgDi3216, 32, 16, WgIg6432, 64, 32, 0, 64)      \
+  X(3, 64, 32, 4, DgDi6432, 64, 32, WgIg3232, 32, 32, 0, 64)      \
+  X(3, 64, 32, 4, DgDi6432, 64, 32, WgIg6432, 64, 32, 0, 64)      \
+  X(5, 32, 32, 1024, DgOs1024, 32, 32, WgFo256, 16, 16, 8, 256)   \
+  X(5, 32, 32, 1025, DgOs1024h, 32, 32, WgFo256, 16, 16, 8, 256)  \
+  X(5, 32, 32, 512, DgOs512, 32, 32, WgOs256, 32, 32, 5, 256)
 
 template <class DB, class WB>
 int launch_pair(const ConvArgs& ad, int dbm, int dbn, const ConvArgs& aw, int wbm, int wbn, hipStream_t s) {
@@ -2488,9 +2623,9 @@ int launch_pair(const ConvArgs& ad, int dbm, int dbn, const ConvArgs& aw, int wb
 // 1 + index of the instantiated pair, 0 if none
 int pair_index(int dv, int dbm, int dbn, int dbk, int wv, int wbm, int wbn, int wbk) {
   int idx = 0;
-#define KML_PAIR_FIND(DV, DBM, DBN, DBK, DB, DTM, DTN, WB, WBM, WBN)                                   \
-  ++idx;                                                                                             \
-  if (dv == DV && dbm == DBM && dbn == DBN && dbk == DBK && wv == 0 && wbm == WBM && wbn == WBN && wbk == 64) \
+#define KML_PAIR_FIND(DV, DBM, DBN, DBK, DB, DTM, DTN, WB, WBM, WBN, WV, WBK)                            \
+  ++idx;                                                                                              \
+  if (dv == DV && dbm == DBM && dbn == DBN && dbk == DBK && wv == WV && wbm == WBM && wbn == WBN && wbk == WBK) \
     return idx;
   KML_PAIR_LIST(KML_PAIR_FIND)
 #undef KML_PAIR_FIND
@@ -2499,7 +2634,7 @@ int pair_index(int dv, int dbm, int dbn, int dbk, int wv, int wbm, int wbn, int 
 
 int dispatch_pair(int which, const ConvArgs& ad, const ConvArgs& aw, hipStream_t s) {
   int idx = 0;
-#define KML_PAIR_RUN(DV, DBM, DBN, DBK, DB, DTM, DTN, WB, WBM, WBN) \
+#define KML_PAIR_RUN(DV, DBM, DBN, DBK, DB, DTM, DTN, WB, WBM, WBN, WV, WBK) \
   if (++idx == which) return launch_pair<DB, WB>(ad, DTM, DTN, aw, WBM, WBN, s);
   KML_PAIR_LIST(KML_PAIR_RUN)
 #undef KML_PAIR_RUN
@@ -2893,7 +3028,8 @@ int prep_dgrad(ConvArgs& a, const bf16_t* dy, const bf16_t* w, const bf16_t* wt,
 // writer — split-K partial tiles go through the slab and are summed in split order by the
 // last block of the tile — so weight gradients are bitwise reproducible and need no zeroed
 // buffer.  (An unrolled conv's dense 1x1-form gradient goes to a scratch that
-// kml_conv_fold22_multi folds onto the 3x3 taps in a fixed order.)
+// kml_conv_fold22_multi folds onto the 3x3 taps in a fixed order — except in the folded
+// one-shot pair, kml_conv_bwd_pair with wgrad variant 8, which writes the taps itself.)
 int prep_wgrad(ConvArgs& a, const bf16_t* x, const bf16_t* dy, float* dw, int B, int H, int W, int C, int K, int KH,
                int KW, int sh, int sw, int ph, int pw, int bk, int splits, int variant, int accumulate, float* slab,
                unsigned* counters, float* dbias, int bias_acc) {
@@ -2941,6 +3077,22 @@ KML_API int kml_conv_bwd_pair(const bf16_t* dy, const bf16_t* w, const bf16_t* w
   e = prep_wgrad(aw, x, dy, dw, B, H, W, C, K, KH, KW, sh, sw, ph, pw, wbk, wsplits, wvariant, waccumulate, wslab,
                  wcounters, wbias, wbias_acc);
   if (e) return e;
+  const bool one_tap = (ad.r1 - ad.r0) == 1 && (ad.s1 - ad.s0) == 1;
+  const bool rows = (H * W == 1 && ad.OH * ad.OW == 1) || (KH == 1 && KW == 1 && sh == 1 && sw == 1 && !ph && !pw);
+  if (dvariant == 5) {  // one-shot dgrad panels: single tap, contiguous dY rows, K = Cout (as kml_conv_dgrad)
+    if (!one_tap || !rows || ad.splits != 1 || (dbk & ~1) != K) return (int)hipErrorInvalidValue;
+    ad.Kd = K;
+  }
+  if (wvariant == 5 || wvariant == WV_FOLD22) {  // one-shot wgrad panels: K = pixels <= the panel depth
+    if (!one_tap || !rows || wbias || aw.splits != 1 || aw.Kd > wbk) return (int)hipErrorInvalidValue;
+  }
+  if (wvariant == WV_FOLD22) {
+    // the conv is the 1x1 form (C = 4 Cq, K = 4 Kq) of an unrolled 2x2-map conv and dw its 3x3
+    // gradient [Kq][3][3][Cq]: the block grid covers Kq x Cq
+    if (H * W != 1 || KH != 1 || KW != 1 || K % 32 || C % 32) return (int)hipErrorInvalidValue;
+    aw.fd_gK = make_fd(K / 4); aw.fd_gC = make_fd(C / 4);
+    aw.M = K / 4; aw.N = C / 4;
+  }
   return dispatch_pair(which, ad, aw, s);
 }
 

@@ -330,14 +330,18 @@ class ConvBNUnit:
             # dgrad + wgrad as one grouped launch (falls back to two for unpaired plans)
             w = shadow_of(conv.weight)
             wt = getattr(conv, "_kml_wt", None)
-            if wt is None and K.bwd_plans(x.shape, w.shape[0], kh, kw, conv.stride, conv.padding,
-                                          unroll=wu is not None)[0][4] == K.DIRECT:
+            dplan, wplan, _ = K.bwd_plans(x.shape, w.shape[0], kh, kw, conv.stride, conv.padding,
+                                          unroll=wu is not None)
+            if wt is None and dplan[4] == K.DIRECT:
                 object.__setattr__(conv, "_kml_wants_wt", True)   # batched by refresh_transposed()
-            dw, acc = _wgrad_target(conv, x, wu is not None)
+            # folded route: the unrolled conv's pair writes the 3x3 gradient itself (no 1x1-form
+            # scratch, no deferred fold: the gradient is final when conv_bwd returns)
+            folded = wu is not None and wplan[4] == K.FOLD22
+            dw, acc = _wgrad_target(conv, x, wu is not None and not folded)
             r = K.conv_bwd(dc, w, x, dw, kh, kw, conv.stride, conv.padding,
                            addend=addend, bnf=bnf, wt=wt, wu=wu, bnf_mask=True, accumulate=acc,
                            rider=_take_rider(conv))
-            if wu is not None:
+            if wu is not None and not folded:
                 conv.weight._kml_flat.defer_fold22(conv.weight, dw)
             object.__setattr__(conv, "_kml_wt", None)             # valid for one backward pass
             dx, part_out = r if bnf is not None else (r, None)

@@ -582,11 +582,52 @@ def oneshot_plan(C, K, Kd, H, W, KH, KW, stride, pad, B=0):
     return None
 
 
-# tests / micro-benchmarks only: as two launches the one-shot dgrad + wgrad lose to the grouped
-# implicit-GEMM pair (1.376 vs 1.353 ms/step, profiles/r3/oneshot.md)
+# tests / micro-benchmarks only: as TWO launches the one-shot dgrad + wgrad lose to the grouped
+# implicit-GEMM pair (1.376 vs 1.353 ms/step, profiles/r3/oneshot.md).  The default route for
+# these shapes is the same bodies inside ONE grouped launch (_ONESHOT_PAIR_ON below).
 _ONESHOT_BWD_ON = False
 _ONESHOT_DG_TILES = {1024: (32, 32), 512: (32, 32)}   # keyed by the dgrad K (= Cout)
 _ONESHOT_WG_TILES = {256: (32, 32)}                    # keyed by the wgrad K (= pixels)
+
+# One-shot dgrad + one-shot wgrad of a single-tap conv in one grouped launch (k_conv_pair), for
+# at most _ONESHOT_PAIR_PIXELS pixel rows (the wgrad panel depth; fewer are zero-filled):
+#   * single-tap convs with contiguous rows and a dgrad K of 512 (ResNet-34 layer4 on 1x1 maps):
+#     OneShotBwdBody<DGRAD, 32, 32, 512> + OneShotBwdBody<WGRAD, 32, 32, 256>;
+#   * unrolled 2x2-map convs with a dgrad K of 1024 (layer3) whose weight gradient goes straight
+#     onto the 3x3 taps (conv_bwd with a (K,3,3,C) dw): OneShotBwdBody<DGRAD, 32, 32, 1024> +
+#     the folded wgrad body (variant FOLD22: no 1x1-form scratch, no fold22_multi pass).
+# False: the tuned implicit-GEMM pairs (A/B runs, tests of the fallback route).
+_ONESHOT_PAIR_ON = True
+_ONESHOT_PAIR_PIXELS = 256
+FOLD22 = 8  # wgrad cfg variant id of the folded one-shot wgrad (pairs only)
+# (dgrad, wgrad) plans of the unrolled pair.  dgrad bk slot = K of the 1x1 form (1024), + 1: K
+# taken in two 512 halves; wgrad bk slot = panel depth in pixels.  The halves shrink the launch's
+# LDS from 128 to 64 KB per block (every block of the launch — dgrad, wgrad, SGD rider — holds
+# that much), so two blocks share a CU: 8.2 vs 11.3 us per launch, 1.24 vs 1.31 ms per step
+# (profiles/r7/oneshot_bwd_pair.md; a 32 KB quarter-panel form measured no better than the halves).
+_ONESHOT_PAIR_U22_FULL = ((32, 32, 1024, 1, ONESHOT), (16, 16, 256, 1, FOLD22))
+_ONESHOT_PAIR_U22_HALF = ((32, 32, 1025, 1, ONESHOT), (16, 16, 256, 1, FOLD22))
+_ONESHOT_PAIR_U22 = _ONESHOT_PAIR_U22_HALF
+
+
+def oneshot_pair_plans(C, K, B, H, W, KH, KW, stride, pad, fold22=False):
+    """(dgrad plan, wgrad plan) of the grouped one-shot backward of a single-tap conv with
+    contiguous rows, or (None, None).  fold22: the conv is the 1x1 form of an unrolled 2x2-map
+    conv whose weight gradient is written onto the 3x3 taps."""
+    if not _ONESHOT_PAIR_ON or _ONESHOT_BWD_ON or C % 32 or K % 32:   # _ONESHOT_BWD_ON: the two-launch route
+        return None, None
+    r0, r1, s0, s1 = tap_window(H, W, KH, KW, stride[0], stride[1], pad[0], pad[1])
+    OH, OW = out_hw(H, W, KH, KW, stride[0], stride[1], pad[0], pad[1])
+    rows = (H * W == 1 and OH * OW == 1) or ((KH, KW) == (1, 1) and tuple(stride) == (1, 1) and tuple(pad) == (0, 0))
+    if not ((r1 - r0) == 1 and (s1 - s0) == 1 and rows) or B * OH * OW > _ONESHOT_PAIR_PIXELS:
+        return None, None
+    if fold22:
+        d, w = _ONESHOT_PAIR_U22
+        if (d[2] & ~1) != K or H * W != 1:
+            return None, None
+    else:
+        d, w = (32, 32, K, 1, ONESHOT), (32, 32, _ONESHOT_PAIR_PIXELS, 1, ONESHOT)
+    return (d, w) if conv_pair_supported(d, w) else (None, None)
 
 
 def oneshot_bwd_plans(C, K, B, H, W, KH, KW, stride, pad):
@@ -922,18 +963,30 @@ def dgrad_plan(in_shape, K, KH, KW, stride, pad, cfg=None):
     return _norm_cfg(cfg or plan_conv("dgrad", B * H * W, C, (r1 - r0) * (s1 - s0) * K))
 
 
-def bwd_plans(in_shape, K, KH, KW, stride, pad, dcfg=None, wcfg=None, unroll=False):
-    """(dgrad plan, wgrad plan, grouped?) conv_bwd runs for this conv: a tuned pair entry
-    when one exists, else the separately tuned plans (grouped if instantiated).
-    unroll: plans of the unrolled 1x1 form (:func:`unrolled22`)."""
+def bwd_plans(in_shape, K, KH, KW, stride, pad, dcfg=None, wcfg=None, unroll=False, scratch=False,
+              oneshot_pair=True):
+    """(dgrad plan, wgrad plan, grouped?) conv_bwd runs for this conv: the grouped one-shot
+    pair for the shapes of :func:`oneshot_pair_plans`, else a tuned pair entry when one
+    exists, else the separately tuned plans (grouped if instantiated).
+    unroll: plans of the unrolled 1x1 form (:func:`unrolled22`); scratch: with the weight
+    gradient left in the ``[4K,1,1,4C]`` 1x1-form scratch instead of folded onto the 3x3 taps.
+    oneshot_pair=False: never the one-shot pair (a conv with a fused bias gradient)."""
     B, H, W, C = in_shape
     if unroll:
-        return bwd_plans((B, 1, 1, 4 * C), 4 * K, 1, 1, (1, 1), (0, 0), dcfg, wcfg)
+        if dcfg is None and wcfg is None and not scratch and oneshot_pair:
+            od, ow = oneshot_pair_plans(4 * C, 4 * K, B, 1, 1, 1, 1, (1, 1), (0, 0), fold22=True)
+            if od is not None:
+                return od, ow, True
+        return bwd_plans((B, 1, 1, 4 * C), 4 * K, 1, 1, (1, 1), (0, 0), dcfg, wcfg, oneshot_pair=False)
     sh, sw = stride
     ph, pw = pad
     OH, OW = out_hw(H, W, KH, KW, sh, sw, ph, pw)
     r0, r1, s0, s1 = tap_window(H, W, KH, KW, sh, sw, ph, pw)
     ntap = (r1 - r0) * (s1 - s0)
+    if dcfg is None and wcfg is None and oneshot_pair:
+        od, ow = oneshot_pair_plans(C, K, B, H, W, KH, KW, stride, pad)
+        if od is not None:
+            return od, ow, True
     if dcfg is None and wcfg is None:
         dcfg, wcfg = _TUNED_PAIR.get((B * H * W, C, ntap * K, K, ntap * C, B * OH * OW), (None, None))
         hp = halo_dgrad_plan(C, K, H, W, KH, KW, stride, pad)
@@ -969,9 +1022,11 @@ def conv_bwd(dy, w, x, dw, KH, KW, stride, pad, addend=None, bnf=None, wt=None, 
     instantiated pair, else as two launches.  ``wt``: precomputed transposed weights for
     a direct-variant dgrad (:func:`weight_transpose_multi`); made here when missing.
     Returns dx, or (dx, (part, G)) when ``bnf`` is given.  wu: unrolled weight
-    (:func:`unrolled22`): both GEMMs run in the dense 1x1 form; ``dw`` is then the
-    ``[4K,1,1,4C]`` fp32 scratch of the 1x1-form weight gradient (stored), which
-    :func:`fold22_multi` folds onto the 3x3 taps.  bnf_mask: as in :func:`conv_dgrad`.
+    (:func:`unrolled22`): both GEMMs run in the dense 1x1 form; ``dw`` is then either the
+    conv's ``(K,3,3,C)`` gradient (the folded route: the grouped one-shot pair writes or
+    adds the taps directly, per ``accumulate``) or the ``[4K,1,1,4C]`` fp32 scratch of the
+    1x1-form weight gradient (stored), which :func:`fold22_multi` folds onto the 3x3 taps.
+    bnf_mask: as in :func:`conv_dgrad`.
     dbias: as in :func:`conv_wgrad` (1x1/s1/p0 convs).
     rider: an :class:`SgdRider` applied by extra blocks of the grouped launch (or by its own
     launch after the two GEMMs when this conv does not run grouped)."""
@@ -984,7 +1039,9 @@ def conv_bwd(dy, w, x, dw, KH, KW, stride, pad, addend=None, bnf=None, wt=None, 
     sh, sw = stride
     ph, pw = pad
     OH, OW = out_hw(H, W, KH, KW, sh, sw, ph, pw)
-    want_dw = (4 * K, 1, 1, 4 * C) if wu is not None else (K, KH, KW, C)
+    # an unrolled conv takes dw as its 3x3 gradient (the folded route) or as the 1x1-form scratch
+    folded = wu is not None and tuple(dw.shape) == (K, KH, KW, C)
+    want_dw = (4 * K, 1, 1, 4 * C) if (wu is not None and not folded) else (K, KH, KW, C)
     if tuple(dy.shape) != (B, OH, OW, K) or tuple(w.shape) != (K, KH, KW, C) or tuple(dw.shape) != want_dw:
         raise ValueError("conv_bwd shape mismatch")
     if K % 8 or C % 8:
@@ -992,9 +1049,18 @@ def conv_bwd(dy, w, x, dw, KH, KW, stride, pad, addend=None, bnf=None, wt=None, 
     fold, g22 = 0, False
     if wu is not None:
         _check_wu(x.shape, w, wu, KH, KW, stride, pad)
+        if folded:
+            if dcfg is not None or wcfg is not None:
+                raise ValueError("conv_bwd: the folded route (a (K,3,3,C) dw with wu) runs its own plans")
+            dcfg, wcfg, ok = bwd_plans(x.shape, K, KH, KW, stride, pad, unroll=True)
+            if not ok or wcfg[4] != FOLD22:
+                raise ValueError("conv_bwd: no folded one-shot pair for this unrolled conv "
+                                 "(pass the [4K,1,1,4C] scratch as dw and fold with fold22_multi)")
         dy, x, addend, bnf = _u22_views(B, C, K, dy=dy, x=x, addend=addend, bnf=bnf)
         g22 = wu is GATHER22
-        w, fold, accumulate = (w if g22 else wu), C, False
+        w, fold = (w if g22 else wu), C
+        if not folded:
+            accumulate = False
         H = W = OH = OW = 1
         KH = KW = sh = sw = 1
         ph = pw = 0
@@ -1003,8 +1069,13 @@ def conv_bwd(dy, w, x, dw, KH, KW, stride, pad, addend=None, bnf=None, wt=None, 
     r0, r1, s0, s1 = tap_window(H, W, KH, KW, sh, sw, ph, pw)
     ntap = (r1 - r0) * (s1 - s0)
     M = B * H * W
-    dplan, wplan, grouped = bwd_plans(x.shape, K, KH, KW, stride, pad, dcfg, wcfg)
-    wroute = None if (wcfg is not None or wu is not None) else wgrad_gemm_route(x.shape, K, KH, KW, stride, pad, dbias)
+    if folded:
+        dplan, wplan, grouped = dcfg, wcfg, True
+    else:
+        dplan, wplan, grouped = bwd_plans(x.shape, K, KH, KW, stride, pad, dcfg, wcfg,
+                                          oneshot_pair=dbias is None and wu is None)
+    wroute = None if (wcfg is not None or wu is not None or wplan[4] == ONESHOT) else \
+        wgrad_gemm_route(x.shape, K, KH, KW, stride, pad, dbias)
     if wroute is not None:
         grouped = False
     if grouped and s2_parity_ok(B, H, W, stride, dplan, g22, fold, operands=addend is not None or bnf is not None):
@@ -1043,7 +1114,10 @@ def conv_bwd(dy, w, x, dw, KH, KW, stride, pad, addend=None, bnf=None, wt=None, 
         slab, cnt = _splitk_ws(dy.device, M, C, bm, bn, dsplits)
     wbm, wbn, wbk, wsplits, wvariant = wplan
     _chk_dbias(dbias, K, KH, KW, stride, pad)
-    wslab, wcnt = _wgrad_ws(dw.device, B, H, W, C, K, KH, KW, stride, pad, wplan, dbias is not None)
+    if wplan[4] in (ONESHOT, FOLD22):
+        wslab = wcnt = None   # one block owns a weight-gradient tile: no split-K
+    else:
+        wslab, wcnt = _wgrad_ws(dw.device, B, H, W, C, K, KH, KW, stride, pad, wplan, dbias is not None)
     with _Riding(rider):
         HIP.call("kml_conv_bwd_pair",
                  "p p p p p p p p p p p p i p p i i i i i i i i i i i i i i i i p p i i i i i i i p p i p i i s",
