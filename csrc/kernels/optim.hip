@@ -24,7 +24,7 @@ __global__ void k_sgd(float* __restrict__ w, const float* __restrict__ g, float*
                       bf16_t* __restrict__ shadow, const float* __restrict__ lr_ptr, float lr_host, float wd,
                       float momentum, float dampening, int nesterov, const float* __restrict__ first_ptr,
                       int first_host, float grad_scale, long long n, float* __restrict__ adv_ctr,
-                      float adv_batch, float adv_n) {
+                      float adv_batch, float adv_n, const float* __restrict__ clip_ptr) {
   // data-sampler counter advance (k_advance's job) folded into this launch: one thread, no
   // other block reads the counter, the next step's augment reads it after the launch boundary
   if (adv_ctr && blockIdx.x == 0 && threadIdx.x == 0) {
@@ -37,6 +37,8 @@ __global__ void k_sgd(float* __restrict__ w, const float* __restrict__ g, float*
   // first step after a reset (torch: momentum buffer := d, no dampening).  The flag lives
   // in device memory so a graph-captured step follows reset_state() between replays.
   const int first = first_ptr ? (*first_ptr != 0.f) : first_host;
+  // global-norm clipping: the coefficient k_grad_norm left on the device scales the gradient
+  if (clip_ptr) grad_scale *= *clip_ptr;
   kml_sgd_range(w, g, mom, shadow, lr, wd, momentum, dampening, nesterov, first, grad_scale, n,
                 blockIdx.x * (long long)blockDim.x + threadIdx.x, (long long)gridDim.x * blockDim.x);
 }
@@ -44,8 +46,10 @@ __global__ void k_sgd(float* __restrict__ w, const float* __restrict__ g, float*
 __global__ void k_adam(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m,
                        float* __restrict__ v, bf16_t* __restrict__ shadow, const float* __restrict__ lr_ptr,
                        const float* __restrict__ step_ptr, float lr_host, float step_host, float b1, float b2,
-                       float eps, float wd, int decoupled, float grad_scale, long long n) {
+                       float eps, float wd, int decoupled, float grad_scale, long long n,
+                       const float* __restrict__ clip_ptr) {
   const float lr = lr_ptr ? *lr_ptr : lr_host;
+  if (clip_ptr) grad_scale *= *clip_ptr;  // global-norm clipping coefficient (k_grad_norm)
   const float t = step_ptr ? *step_ptr : step_host;
   const float bc1 = 1.f - __powf(b1, t), bc2 = 1.f - __powf(b2, t);
   const float step_size = lr / bc1;
@@ -110,25 +114,109 @@ __global__ void k_adam(float* __restrict__ w, const float* __restrict__ g, float
 
 __global__ void k_inc(float* p, float by) { if (threadIdx.x == 0 && blockIdx.x == 0) *p += by; }
 
-// sum of squares of an fp32 vector into out[0] (atomic; out zeroed by caller)
-__global__ __launch_bounds__(256) void k_sumsq(const float* __restrict__ x, float* __restrict__ out, long long n) {
-  float s = 0.f;
-  for (long long i = blockIdx.x * 256LL + threadIdx.x; i < n; i += (long long)gridDim.x * 256)
-    s += x[i] * x[i];
-  s = wave_sum(s);
-  __shared__ float sh[4];
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
+// ---- global-norm gradient clipping ----------------------------------------------------------
+// One launch: every block sums the squares of its grid-stride share of g (fp32, fixed order) into
+// part[blockIdx.x]; the last block to arrive (ticket on `counter`, which it resets to 0) folds the
+// partials in index order and writes
+//   out[0] = sum g^2
+//   out[1] = grad_scale * sqrt(out[0])                 the norm of the averaged gradient
+//   out[2] = min(1, *max_norm_ptr / (out[1] + 1e-6))   torch.nn.utils.clip_grad_norm_'s coefficient
+// No atomics on the sums: the result is a function of (g, n, grid) only, bit for bit.  The
+// threshold is read from device memory, so a graph-captured step follows a changed threshold.
+constexpr int KML_NORM_MAX_BLOCKS = 1024;  // the final fold is one pass of 256 threads x 4
+
+// every thread gets the block's sum (4 waves of 64); sh is reusable after the call's barrier pair
+__device__ __forceinline__ float block_sum256(float v, float* sh) {
+  v = wave_sum(v);
   __syncthreads();
-  if (threadIdx.x == 0) atomicAdd(out, sh[0] + sh[1] + sh[2] + sh[3]);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return (sh[0] + sh[1]) + (sh[2] + sh[3]);
 }
 
-// x *= min(1, max_norm / (sqrt(sumsq) + 1e-6))  — global-norm clipping, scale on device
-__global__ void k_clip_scale(float* __restrict__ x, const float* __restrict__ sumsq, float max_norm, long long n) {
-  const float nrm = sqrtf(*sumsq);
-  const float c = fminf(1.f, max_norm / (nrm + 1e-6f));
-  if (c >= 1.f) return;
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
-    x[i] *= c;
+__global__ __launch_bounds__(256) void k_grad_norm(const float* __restrict__ g, long long n, float grad_scale,
+                                                   const float* __restrict__ max_norm_ptr, float* __restrict__ part,
+                                                   unsigned* __restrict__ counter, float* __restrict__ out) {
+  __shared__ float sh[4];
+  __shared__ unsigned last;
+  const int tid = threadIdx.x;
+  const long long n4 = n >> 2;
+  const long long stride = (long long)gridDim.x * 256;
+  // four float4 groups per thread and iteration, all loads issued before the math (a read-only
+  // stream: as k_adam's U = 2 with a quarter of its bytes per group), one accumulator per slot
+  constexpr int U = 4;
+  float acc[U] = {0.f, 0.f, 0.f, 0.f};
+  long long i0 = blockIdx.x * 256LL + tid;
+  // full iterations load unconditionally (a per-load bounds select makes the compiler branch
+  // around every load and wait for each); the up to U - 1 groups left go one at a time
+  for (; i0 + (U - 1) * stride < n4; i0 += U * stride) {
+    float4 G[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) G[u] = reinterpret_cast<const float4*>(g)[i0 + u * stride];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      acc[u] = fmaf(G[u].x, G[u].x, acc[u]);
+      acc[u] = fmaf(G[u].y, G[u].y, acc[u]);
+      acc[u] = fmaf(G[u].z, G[u].z, acc[u]);
+      acc[u] = fmaf(G[u].w, G[u].w, acc[u]);
+    }
+  }
+  for (; i0 < n4; i0 += stride) {
+    const float4 v = reinterpret_cast<const float4*>(g)[i0];
+    acc[0] = fmaf(v.x, v.x, acc[0]);
+    acc[0] = fmaf(v.y, v.y, acc[0]);
+    acc[0] = fmaf(v.z, v.z, acc[0]);
+    acc[0] = fmaf(v.w, v.w, acc[0]);
+  }
+  float s = (acc[0] + acc[1]) + (acc[2] + acc[3]);
+  for (long long i = (n4 << 2) + blockIdx.x * 256LL + tid; i < n; i += stride) s = fmaf(g[i], g[i], s);
+  s = block_sum256(s, sh);
+  // hand-off to the last arriver (the ticket of k_bn_bwd_reduce2): plain store, agent-scope release
+  // before the ticket, acquire after it; the counter word is back at 0 when the launch ends
+  if (tid == 0) {
+    part[blockIdx.x] = s;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const unsigned t = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const unsigned l = (t == gridDim.x - 1) ? 1u : 0u;
+    if (l) {
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    last = l;
+  }
+  __syncthreads();
+  if (!last) return;
+  // partial b goes to thread b % 256, each thread adds its (at most 4) partials in index order;
+  // agent-scope loads are served by the L2 / memory, never by this CU's L1
+  float t = 0.f;
+  for (int b = tid; b < (int)gridDim.x; b += 256)
+    t += __hip_atomic_load(part + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  t = block_sum256(t, sh);
+  if (tid == 0) {
+    const float nrm = grad_scale * sqrtf(t);
+    // c > 1 is false for a NaN norm, so NaN reaches the update (fminf would return 1); inf gives 0
+    const float c = *max_norm_ptr / (nrm + 1e-6f);
+    out[0] = t;
+    out[1] = nrm;
+    out[2] = c > 1.f ? 1.f : c;
+  }
+}
+
+// x *= coef[0] (the eager in-place clip; coef = out + 2 of k_grad_norm).  A coefficient of exactly
+// 1 leaves the buffer untouched; NaN is not 1 and poisons it.
+__global__ void k_clip_scale(float* __restrict__ x, const float* __restrict__ coef, long long n) {
+  const float c = *coef;
+  if (c == 1.f) return;
+  const long long n4 = n >> 2, stride = (long long)gridDim.x * blockDim.x;
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n4; i += stride) {
+    float4 v = reinterpret_cast<float4*>(x)[i];
+    v.x *= c; v.y *= c; v.z *= c; v.w *= c;
+    reinterpret_cast<float4*>(x)[i] = v;
+  }
+  for (long long i = (n4 << 2) + blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += stride) x[i] *= c;
 }
 
 }  // namespace
@@ -144,22 +232,23 @@ KML_API int kml_memset(void* p, int value, long long bytes, hipStream_t s) {
 KML_API int kml_sgd(float* w, const float* g, float* mom, bf16_t* shadow, const float* lr_ptr, float lr, float wd,
                     float momentum, float dampening, int nesterov, const float* first_ptr, int first,
                     float grad_scale, long long n, int max_blocks, float* adv_ctr, float adv_batch, float adv_n,
-                    hipStream_t s) {
+                    const float* clip_ptr, hipStream_t s) {
   unsigned grid = kml_stream_grid((n + 3) / 4, 256);
   if (max_blocks > 0 && grid > (unsigned)max_blocks) grid = (unsigned)max_blocks;
   hipLaunchKernelGGL(k_sgd, dim3(grid), dim3(256), 0, s, w, g, mom, shadow, lr_ptr, lr, wd, momentum, dampening,
-                     nesterov, first_ptr, first, grad_scale, n, adv_ctr, adv_batch, adv_n);
+                     nesterov, first_ptr, first, grad_scale, n, adv_ctr, adv_batch, adv_n, clip_ptr);
   KML_LAUNCH_CHECK();
 }
 
 // max_blocks > 0 caps the grid (a range update on a side stream beside the backward, as kml_sgd)
 KML_API int kml_adam(float* w, const float* g, float* m, float* v, bf16_t* shadow, const float* lr_ptr,
                      const float* step_ptr, float lr, float step, float b1, float b2, float eps, float wd,
-                     int decoupled, float grad_scale, long long n, int max_blocks, hipStream_t s) {
+                     int decoupled, float grad_scale, long long n, int max_blocks, const float* clip_ptr,
+                     hipStream_t s) {
   unsigned grid = kml_stream_grid((n + 3) / 4, 256);
   if (max_blocks > 0 && grid > (unsigned)max_blocks) grid = (unsigned)max_blocks;
   hipLaunchKernelGGL(k_adam, dim3(grid), dim3(256), 0, s, w, g, m, v, shadow, lr_ptr,
-                     step_ptr, lr, step, b1, b2, eps, wd, decoupled, grad_scale, n);
+                     step_ptr, lr, step, b1, b2, eps, wd, decoupled, grad_scale, n, clip_ptr);
   KML_LAUNCH_CHECK();
 }
 
@@ -168,12 +257,29 @@ KML_API int kml_increment(float* p, float by, hipStream_t s) {
   KML_LAUNCH_CHECK();
 }
 
-__global__ void k_zero1(float* p) { if (threadIdx.x == 0) *p = 0.f; }
+// blocks of kml_grad_norm for n elements: a function of (n, max_blocks) only, so every rank of a
+// data-parallel group (same n) sums in the same order; at most KML_NORM_MAX_BLOCKS
+static inline unsigned kml_norm_grid(long long n, int max_blocks) {
+  long long g = ((n >> 2) + 255) / 256;
+  if (g > KML_NORM_MAX_BLOCKS) g = KML_NORM_MAX_BLOCKS;
+  if (max_blocks > 0 && g > max_blocks) g = max_blocks;
+  if (g < 1) g = 1;
+  return (unsigned)g;
+}
 
-KML_API int kml_clip_grad_norm(float* g, float* ws1, float max_norm, long long n, hipStream_t s) {
-  hipLaunchKernelGGL(k_zero1, dim3(1), dim3(64), 0, s, ws1);
-  hipLaunchKernelGGL(k_sumsq, dim3(kml_stream_grid(n, 256 * 4)), dim3(256), 0, s, g, ws1, n);
-  hipLaunchKernelGGL(k_clip_scale, dim3(kml_stream_grid(n, 256)), dim3(256), 0, s, g, ws1, max_norm, n);
+// part: >= kml_norm_grid(n, max_blocks) floats of scratch; counter: one word, 0 on entry and on
+// exit; out: 3 floats (sum of squares, norm of grad_scale * g, clip coefficient)
+KML_API int kml_grad_norm(const float* g, long long n, float grad_scale, const float* max_norm_ptr, float* part,
+                          unsigned* counter, float* out, int max_blocks, hipStream_t s) {
+  if (n < 0 || !g || !max_norm_ptr || !part || !counter || !out || ((uintptr_t)g & 15)) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_grad_norm, dim3(kml_norm_grid(n, max_blocks)), dim3(256), 0, s, g, n, grad_scale,
+                     max_norm_ptr, part, counter, out);
+  KML_LAUNCH_CHECK();
+}
+
+KML_API int kml_scale_by_coef(float* g, const float* coef, long long n, hipStream_t s) {
+  if (((uintptr_t)g & 15)) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_clip_scale, dim3(kml_stream_grid((n + 3) / 4, 256)), dim3(256), 0, s, g, coef, n);
   KML_LAUNCH_CHECK();
 }
 

@@ -32,6 +32,21 @@ SHARD_RIDE_BLOCKS = 256
 PACKED_RIDE_BLOCKS = 128
 
 
+def optimizer_clips(optimizer) -> bool:
+    """True when the optimizer's step clips the global gradient norm (``max_grad_norm``)."""
+    return bool(getattr(optimizer, "clips", False))
+
+
+def optimizer_can_shard(optimizer) -> bool:
+    """Can the ZeRO-1 shard plan update this rank's chunk with ``optimizer``?  Needs an update of
+    one flat range, and no global-norm clipping: the clip coefficient is a function of the whole
+    summed gradient, which a rank of the shard plan never holds."""
+    if optimizer_clips(optimizer):
+        return False
+    return bool((getattr(optimizer, "kind", None) == "sgd" and optimizer.supports_ranges())
+                or getattr(optimizer, "supports_shard_range", lambda: False)())
+
+
 def make_train_step(model: torch.nn.Module, space, optimizer, loss_fn: Callable, x: torch.Tensor,
                     y: torch.Tensor, *, pre: Optional[Callable[[], None]] = None,
                     post: Optional[Callable[[], None]] = None, group=None, world: int = 1,
@@ -73,11 +88,21 @@ def make_train_step(model: torch.nn.Module, space, optimizer, loss_fn: Callable,
             second queue); the end-of-step launch then covers the rest.  One GPU, no collective,
             fused SGD.  None = ``KUBEML_RIDE`` (default on: ResNet-34 1.330 -> 1.320 ms/step over six
             alternating runs on two boxes, bit-identical weights; profiles/r5/sgd_rider.md).
+    An optimizer built with ``max_grad_norm`` (global-norm clipping) needs the whole reduced
+    gradient before any element is updated: the step then has no riders and no per-stage
+    updates, and a ZeRO-1 plan (``shard`` / ``shardov`` / ``shardride``) runs as the exact
+    all-reduce plan (warning logged; every rank computes the same norm and stays bit-identical).
     forward: ``forward(model, x, y) -> loss`` in place of ``loss_fn(model(x), y)`` (models whose
             call takes more than the batch, e.g. BERT MLM with its positions and labels, or a
             step that prepares its batch on the device first); the step is then not stage-split
     """
     comm = world > 1 or force_comm
+    # global-norm clipping (optimizer built with max_grad_norm) needs the whole reduced gradient
+    # before any element is updated: no riders, no per-stage updates, no sharded update
+    clipping = optimizer_clips(optimizer)
+    if clipping:
+        opt_overlap = False
+        ride = False
     shard = None
     staged_shard = False
     ride_shard = False
@@ -102,9 +127,11 @@ def make_train_step(model: torch.nn.Module, space, optimizer, loss_fn: Callable,
         # the optimizer's capability is checked BEFORE the collective setup (the same answer on
         # every rank), so an optimizer that cannot update one flat range falls back like a node
         # without IPC buffers instead of failing after the self-test
-        can_shard = ((getattr(optimizer, "kind", None) == "sgd" and optimizer.supports_ranges())
-                     or getattr(optimizer, "supports_shard_range", lambda: False)())
-        if on_gpu and not can_shard:
+        can_shard = optimizer_can_shard(optimizer)
+        if on_gpu and clipping:
+            _log.warning("shard plan: global-norm clipping needs the whole reduced gradient on every rank; "
+                         "using the all-reduce plan")
+        elif on_gpu and not can_shard:
             _log.warning("shard plan: the optimizer cannot update one flat range; using the all-reduce plan")
         if on_gpu and can_shard:
             from ..parallel.peer import PeerShard, verified_shard
@@ -115,7 +142,7 @@ def make_train_step(model: torch.nn.Module, space, optimizer, loss_fn: Callable,
             # no IPC buffers / self-test failed (every rank alike) / CPU group: exact all-reduce
             from ..parallel.plan import CommPlan
             plan = CommPlan("peer" if on_gpu else "rccl", "end" if on_gpu else "overlap", "fp32", plan.max_blocks,
-                            source=f"{plan.source} (shard unavailable)")
+                            source=f"{plan.source} (shard unavailable" + (": gradient clipping)" if clipping else ")"))
         peer = shard
         if shard is not None:
             overlap = staged_shard            # one collective after the backward, or one per stage

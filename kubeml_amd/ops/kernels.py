@@ -1624,11 +1624,13 @@ def ce_bwd(logits, labels, ws, out3, grad_out=None, ignore_index=-100, classes=N
 # --------------------------------------------------------------------------------------
 
 def sgd_(w, g, mom, shadow, lr, wd=0.0, momentum=0.0, dampening=0.0, nesterov=False, first=False,
-         grad_scale=1.0, lr_dev=None, first_dev=None, max_blocks=0, advance=None):
+         grad_scale=1.0, lr_dev=None, first_dev=None, max_blocks=0, advance=None, clip_dev=None):
     """first_dev: fp32 device flag (non-zero = first step after a state reset); when given
     it overrides ``first`` so graph replays follow reset_state().  max_blocks: grid cap.
-    advance: (ctr, batch, n) -- also do :func:`advance_counter_` (ctr, batch, n) in this launch."""
+    advance: (ctr, batch, n) -- also do :func:`advance_counter_` (ctr, batch, n) in this launch.
+    clip_dev: fp32 device scalar multiplied into grad_scale (:func:`grad_norm_`'s ``out[2:3]``)."""
     n = w.numel()
+    _chk_clip(clip_dev, w)
     ctr, ab, an = None, 0.0, 0.0
     if advance is not None:
         ctr, ab, an = advance
@@ -1636,9 +1638,16 @@ def sgd_(w, g, mom, shadow, lr, wd=0.0, momentum=0.0, dampening=0.0, nesterov=Fa
         if ctr.numel() < 3 or ctr.device != w.device:
             raise ValueError("advance counter must be a [3] fp32 tensor on the parameters' device")
         ab, an = float(ab), float(an)
-    HIP.call("kml_sgd", "p p p p p f f f f i p i f l i p f f s", _p(w), _p(g), _p(mom), _p(shadow), _p(lr_dev),
+    HIP.call("kml_sgd", "p p p p p f f f f i p i f l i p f f p s", _p(w), _p(g), _p(mom), _p(shadow), _p(lr_dev),
              float(lr), float(wd), float(momentum), float(dampening), int(nesterov), _p(first_dev), int(first),
-             float(grad_scale), n, int(max_blocks), _p(ctr), ab, an, _s())
+             float(grad_scale), n, int(max_blocks), _p(ctr), ab, an, _p(clip_dev), _s())
+
+
+def _chk_clip(clip_dev, w):
+    if clip_dev is not None:
+        _chk(clip_dev, F32, "clip_dev")
+        if clip_dev.numel() < 1 or clip_dev.device != w.device:
+            raise ValueError("clip_dev must be an fp32 scalar on the parameters' device")
 
 
 class SgdRider:
@@ -1702,19 +1711,60 @@ class _Riding:
 
 
 def adam_(w, g, m, v, shadow, lr, step, b1=0.9, b2=0.999, eps=1e-8, wd=0.0, decoupled=False,
-          grad_scale=1.0, lr_dev=None, step_dev=None, max_blocks=0):
+          grad_scale=1.0, lr_dev=None, step_dev=None, max_blocks=0, clip_dev=None):
+    """clip_dev: fp32 device scalar multiplied into grad_scale (:func:`grad_norm_`'s ``out[2:3]``)."""
     n = w.numel()
-    HIP.call("kml_adam", "p p p p p p p f f f f f f i f l i s", _p(w), _p(g), _p(m), _p(v), _p(shadow),
+    _chk_clip(clip_dev, w)
+    HIP.call("kml_adam", "p p p p p p p f f f f f f i f l i p s", _p(w), _p(g), _p(m), _p(v), _p(shadow),
              _p(lr_dev), _p(step_dev), float(lr), float(step), float(b1), float(b2), float(eps), float(wd),
-             int(decoupled), float(grad_scale), n, int(max_blocks), _s())
+             int(decoupled), float(grad_scale), n, int(max_blocks), _p(clip_dev), _s())
 
 
 def increment_(t, by=1.0):
     HIP.call("kml_increment", "p f s", _p(t), float(by), _s())
 
 
-def clip_grad_norm_(g, ws1, max_norm):
-    HIP.call("kml_clip_grad_norm", "p p f l s", _p(g), _p(ws1), float(max_norm), g.numel(), _s())
+GRAD_NORM_MAX_BLOCKS = 1024
+
+
+def grad_norm_blocks(n, max_blocks=0):
+    """Blocks of the :func:`grad_norm_` launch (mirrors the C++): a function of n and max_blocks only."""
+    g = min(_cdiv(n >> 2, 256), GRAD_NORM_MAX_BLOCKS)
+    if max_blocks > 0:
+        g = min(g, int(max_blocks))
+    return max(g, 1)
+
+
+def grad_norm_(g, out, max_norm_dev, grad_scale=1.0, max_blocks=0):
+    """Global norm of the flat fp32 gradient ``g`` in one deterministic launch (no float atomics:
+    ordered per-block partials, folded by the last block to arrive).  ``out`` (fp32 [3]) receives
+    sum(g^2), ``grad_scale * sqrt(sum)`` and torch's clip coefficient ``min(1, max_norm / (norm +
+    1e-6))`` with ``max_norm`` read from the device scalar ``max_norm_dev`` at run time (NaN norm ->
+    NaN coefficient, inf -> 0).  ``sgd_`` / ``adam_`` consume ``out[2:3]`` as ``clip_dev``."""
+    _chk(g, F32, "g")
+    _chk(out, F32, "out")
+    _chk(max_norm_dev, F32, "max_norm_dev")
+    if out.numel() < 3 or max_norm_dev.numel() < 1 or out.device != g.device or max_norm_dev.device != g.device:
+        raise ValueError("grad_norm_: out must be fp32 [3] and max_norm_dev fp32 [1] on the gradient's device")
+    if g.data_ptr() % 16:
+        raise ValueError("grad_norm_: the gradient buffer must be 16-byte aligned")
+    n = g.numel()
+    part = torch.empty(grad_norm_blocks(n, max_blocks), dtype=F32, device=g.device)
+    cnt = _COUNTERS.take(g.device, 1)
+    HIP.call("kml_grad_norm", "p l f p p p p i s", _p(g), n, float(grad_scale), _p(max_norm_dev), _p(part), _p(cnt),
+             _p(out), int(max_blocks), _s())
+    return out
+
+
+def scale_by_coef_(g, out):
+    """``g *= out[2]`` in place (the eager clip; ``out`` as written by :func:`grad_norm_`)."""
+    _chk(g, F32, "g")
+    _chk(out, F32, "out")
+    if out.numel() < 3 or out.device != g.device:
+        raise ValueError("scale_by_coef_: out must be the fp32 [3] result of grad_norm_ on g's device")
+    if g.data_ptr() % 16:
+        raise ValueError("scale_by_coef_: the gradient buffer must be 16-byte aligned")
+    HIP.call("kml_scale_by_coef", "p p l s", _p(g), _p(out) + 8, g.numel(), _s())
 
 
 def kavg_pack_(state, i64, i64_off, n_i64, count_idx, participate):

@@ -19,6 +19,14 @@ read by the kernels at replay time, so a captured step honours a reset between r
 counters, flags); graph capture snapshots and restores them around its warm-up so
 capturing a step never applies an update (engine/step.py).
 
+``max_grad_norm=`` turns on global-norm gradient clipping (torch's ``clip_grad_norm_`` with
+the L2 norm) as part of the step: one deterministic ``kml_grad_norm`` launch over the flat
+gradient leaves the clip coefficient on the device and the fused update multiplies it into
+its gradient scale — no extra pass over the gradient.  The threshold is a device scalar
+(``set_max_grad_norm``), so a captured step follows a changed threshold; clipping on or off
+is fixed at construction (it decides the step's launches).  ``grad_norm_tensor`` is the
+norm of the last step's averaged gradient.
+
 ``from_torch(opt)`` converts a user's ``torch.optim.SGD/Adam/AdamW`` (what
 ``KubeModel.configure_optimizers`` returns in reference code) into the fused one
 with identical hyper-parameters.
@@ -29,7 +37,7 @@ from typing import Dict, List
 
 import torch
 
-__all__ = ["SGD", "Adam", "AdamW", "from_torch", "FusedOptimizer"]
+__all__ = ["SGD", "Adam", "AdamW", "from_torch", "with_max_grad_norm", "FusedOptimizer"]
 
 
 def _spaces(params):
@@ -57,6 +65,88 @@ class FusedOptimizer(torch.optim.Optimizer):
         self._step_dev: Dict[torch.device, torch.Tensor] = {}
         self._first_dev: Dict[torch.device, torch.Tensor] = {}
         self._step_host = 0
+        self._max_norm_dev: Dict[torch.device, torch.Tensor] = {}
+        self._norm_out: Dict[torch.device, torch.Tensor] = {}
+        self._norm_host = None     # CPU / loose-parameter path: the last step's norm
+        mgn = self.defaults.get("max_grad_norm")
+        if mgn is not None and not float(mgn) > 0.0:
+            raise ValueError("max_grad_norm must be a positive number or None")
+
+    # --- global-norm clipping ---------------------------------------------------------
+    @property
+    def clips(self) -> bool:
+        """True when the step clips the global gradient norm (``max_grad_norm`` given)."""
+        return self.param_groups[0].get("max_grad_norm") is not None
+
+    def max_norm_tensor(self, device):
+        """fp32 device scalar the norm launch reads its threshold from."""
+        t = self._max_norm_dev.get(device)
+        if t is None:
+            t = torch.full((1,), float(self.param_groups[0]["max_grad_norm"]), dtype=torch.float32, device=device)
+            self._max_norm_dev[device] = t
+        return t
+
+    def set_max_grad_norm(self, v: float):
+        """Change the clip threshold (a captured step follows it without re-capture).  Only on
+        an optimizer built with ``max_grad_norm``: clipping on / off is a different step."""
+        if not self.clips:
+            raise ValueError("this optimizer was built without max_grad_norm; create it with one to clip")
+        if v is None or not float(v) > 0.0:
+            raise ValueError("max_grad_norm must be a positive number")
+        for g in self.param_groups:
+            g["max_grad_norm"] = float(v)
+        for t in self._max_norm_dev.values():
+            t.fill_(float(v))
+
+    def _norm_out_tensor(self, device):
+        """fp32 [3] scratch of the norm launch: sum of squares, norm, clip coefficient."""
+        t = self._norm_out.get(device)
+        if t is None:
+            t = torch.zeros(3, dtype=torch.float32, device=device)
+            self._norm_out[device] = t
+        return t
+
+    def grad_norm_tensor(self, device=None):
+        """The last step's global norm of the averaged gradient (before clipping) as a one-element
+        tensor: a view of the norm launch's output on a GPU (no synchronisation), a CPU tensor
+        otherwise."""
+        if not self.clips:
+            raise ValueError("this optimizer does not clip: no gradient norm is computed")
+        if device is None:
+            spaces, _ = self._flat_groups()
+            device = spaces[0][0].device if spaces else "cpu"
+        device = torch.device(device)
+        if device.type == "cuda":
+            return self._norm_out_tensor(device)[1:2]
+        return torch.tensor([float("nan") if self._norm_host is None else self._norm_host])
+
+    def _clip_dev(self, sp, loose):
+        """Launch the norm over GPU space ``sp`` and return the device coefficient for the fused
+        update.  Clipping on a GPU needs every parameter in that one flat space."""
+        spaces, _ = self._flat_groups()
+        if len(spaces) != 1 or loose:
+            raise ValueError("max_grad_norm on a GPU needs every parameter in one flat space")
+        from ..ops import kernels as K
+        out = self._norm_out_tensor(sp.device)
+        K.grad_norm_(sp.grad, out, self.max_norm_tensor(sp.device), grad_scale=self._grad_scale)
+        return out[2:3]
+
+    def _no_ranges_when_clipping(self):
+        # the global norm needs the whole gradient before any element is updated
+        if self.clips:
+            raise ValueError("a clipping optimizer cannot step by ranges (the norm needs the whole gradient)")
+
+    def _clip_loose(self, params):
+        """torch form of the norm launch for CPU spaces / loose parameters: the coefficient
+        (a python float, 1.0 when nothing clips) for gradients scaled by grad_scale."""
+        grads = [p.grad for p in params if p.grad is not None]
+        if not grads:
+            return 1.0
+        ss = torch.stack([(g.float() * g.float()).sum() for g in grads]).sum()
+        nrm = self._grad_scale * torch.sqrt(ss)
+        self._norm_host = float(nrm)
+        c = self.param_groups[0]["max_grad_norm"] / (nrm + 1e-6)
+        return float(torch.clamp(c, max=1.0))
 
     # --- device scalars -------------------------------------------------------------
     def lr_tensor(self, device):
@@ -133,6 +223,9 @@ class FusedOptimizer(torch.optim.Optimizer):
             self.lr_tensor(sp.device)
             self.first_tensor(sp.device)
             self._step_dev.setdefault(sp.device, torch.zeros(1, dtype=torch.float32, device=sp.device))
+            if self.clips:            # scratch of the norm launch, not optimizer state
+                self.max_norm_tensor(sp.device)
+                self._norm_out_tensor(sp.device)
         return self
 
     def state_tensors(self) -> List[torch.Tensor]:
@@ -157,9 +250,10 @@ class SGD(FusedOptimizer):
     def _STATE_NAMES(self):
         return ("momentum",) if self.param_groups[0]["momentum"] != 0 else ()
 
-    def __init__(self, params, lr=1e-3, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False):
+    def __init__(self, params, lr=1e-3, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False,
+                 max_grad_norm=None):
         super().__init__(params, dict(lr=lr, momentum=momentum, dampening=dampening,
-                                      weight_decay=weight_decay, nesterov=nesterov))
+                                      weight_decay=weight_decay, nesterov=nesterov, max_grad_norm=max_grad_norm))
         if len(self.param_groups) > 1:
             raise ValueError("fused SGD supports a single param group")
 
@@ -185,14 +279,16 @@ class SGD(FusedOptimizer):
             from ..ops import kernels as K
             mom = self._bufs(sp, ["momentum"])["momentum"] if g["momentum"] != 0 else None
             first = self.first_tensor(sp.device) if mom is not None else None
+            clip = self._clip_dev(sp, loose) if self.clips else None
             K.sgd_(sp.master, sp.grad, mom, sp.shadow, g["lr"], wd=g["weight_decay"], momentum=g["momentum"],
                    dampening=g["dampening"], nesterov=g["nesterov"], first=self._first,
                    grad_scale=self._grad_scale, lr_dev=self.lr_tensor(sp.device), first_dev=first,
-                   advance=advance if k == 0 else None)
+                   advance=advance if k == 0 else None, clip_dev=clip)
             if first is not None:
                 K.fill_(first, 0.0)
         if loose:
-            _torch_sgd(loose, g, self.state, self._grad_scale)
+            coef = self._clip_loose(loose) if self.clips else 1.0
+            _torch_sgd(loose, g, self.state, self._grad_scale * coef)
         self._first = False
         return loss
 
@@ -201,7 +297,7 @@ class SGD(FusedOptimizer):
     def supports_ranges(self) -> bool:
         """True when every parameter lives in one flat space (no loose parameters)."""
         spaces, loose = self._flat_groups()
-        return len(spaces) == 1 and not loose
+        return len(spaces) == 1 and not loose and not self.clips
 
     def supports_shard_range(self) -> bool:
         """One :meth:`step_range` per step over this rank's chunk (engine/dp.py shard plan)."""
@@ -216,11 +312,12 @@ class SGD(FusedOptimizer):
         advance_step: accepted for the ranged-step protocol (SGD keeps no step counter).
         advance: (ctr, batch, n) data-counter advance folded into this launch (as :meth:`step`)."""
         g = self.param_groups[0]
+        self._no_ranges_when_clipping()
         spaces, loose = self._flat_groups()
         if len(spaces) != 1 or loose:
             raise ValueError("step_range needs all parameters in one flat space")
         sp = spaces[0][0]
-        mom = self._bufs(sp, ["momentum"])["momentum"] if g["momentum"] != 0 else None
+        mom =self._bufs(sp, ["momentum"])["momentum"] if g["momentum"] != 0 else None
         if sp.device.type != "cuda":
             _sgd_range_cpu(sp, start, end, g, mom, self._first, self._grad_scale)
             return
@@ -291,8 +388,9 @@ class Adam(FusedOptimizer):
     decoupled = False
     _STATE_NAMES = ("exp_avg", "exp_avg_sq")
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None):
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
+                                      max_grad_norm=max_grad_norm))
         if len(self.param_groups) > 1:
             raise ValueError("fused Adam supports a single param group")
 
@@ -318,11 +416,13 @@ class Adam(FusedOptimizer):
             from ..ops import kernels as K
             st = self._step_dev_inc(sp.device)
             bufs = self._bufs(sp, ["exp_avg", "exp_avg_sq"])
+            clip = self._clip_dev(sp, loose) if self.clips else None
             K.adam_(sp.master, sp.grad, bufs["exp_avg"], bufs["exp_avg_sq"], sp.shadow, g["lr"], 0.0, b1, b2,
                     g["eps"], g["weight_decay"], self.decoupled, self._grad_scale,
-                    lr_dev=self.lr_tensor(sp.device), step_dev=st)
+                    lr_dev=self.lr_tensor(sp.device), step_dev=st, clip_dev=clip)
         if loose:
-            _torch_adam(loose, g, self.state, self._grad_scale, self.decoupled)
+            coef = self._clip_loose(loose) if self.clips else 1.0
+            _torch_adam(loose, g, self.state, self._grad_scale * coef, self.decoupled)
         return loss
 
     def supports_ranges(self) -> bool:
@@ -330,7 +430,7 @@ class Adam(FusedOptimizer):
         advances the bias-correction step once, then every stage's :meth:`step_range` runs with
         ``advance_step=False``, so a step split into ranges equals one whole step."""
         spaces, loose = self._flat_groups()
-        return len(spaces) == 1 and not loose and spaces[0][0].device.type == "cuda"
+        return len(spaces) == 1 and not loose and spaces[0][0].device.type == "cuda" and not self.clips
 
     @torch.no_grad()
     def begin_ranges(self):
@@ -345,7 +445,7 @@ class Adam(FusedOptimizer):
     def supports_shard_range(self) -> bool:
         """One :meth:`step_range` per step over this rank's chunk (engine/dp.py shard plan)."""
         spaces, loose = self._flat_groups()
-        return len(spaces) == 1 and not loose and spaces[0][0].device.type == "cuda"
+        return len(spaces) == 1 and not loose and spaces[0][0].device.type == "cuda" and not self.clips
 
     @torch.no_grad()
     def step_range(self, start: int, end: int, max_blocks: int = 0, advance_step: bool = True):
@@ -355,6 +455,7 @@ class Adam(FusedOptimizer):
         :meth:`begin_ranges`) reuses it."""
         g = self.param_groups[0]
         b1, b2 = g["betas"]
+        self._no_ranges_when_clipping()
         spaces, loose = self._flat_groups()
         if len(spaces) != 1 or loose:
             raise ValueError("step_range needs all parameters in one flat space")
@@ -385,8 +486,8 @@ class AdamW(Adam):
     kind = "adamw"
     decoupled = True
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
-        super().__init__(params, lr, betas, eps, weight_decay)
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=None):
+        super().__init__(params, lr, betas, eps, weight_decay, max_grad_norm)
 
 
 def _torch_adam(params, g, state, grad_scale, decoupled):
@@ -428,3 +529,14 @@ def from_torch(opt: torch.optim.Optimizer) -> FusedOptimizer:
         return SGD(params, lr=g["lr"], momentum=g["momentum"], dampening=g["dampening"],
                    weight_decay=g["weight_decay"], nesterov=g["nesterov"])
     raise TypeError(f"no fused equivalent for {type(opt).__name__}")
+
+
+def with_max_grad_norm(opt: FusedOptimizer, max_grad_norm) -> FusedOptimizer:
+    """A fresh fused optimizer of the same class, parameters and hyper-parameters as ``opt`` that
+    clips the global gradient norm at ``max_grad_norm`` (None: does not clip)."""
+    g = opt.param_groups[0]
+    kw = {k: g[k] for k in opt.defaults}
+    kw["max_grad_norm"] = None if max_grad_norm is None else float(max_grad_norm)
+    new = type(opt)([p for gr in opt.param_groups for p in gr["params"]], **kw)
+    new.set_grad_scale(opt._grad_scale)
+    return new

@@ -166,6 +166,11 @@ class KubeModel(ABC):
                 opt = from_torch(opt)
             except TypeError:
                 pass
+        if self._step_max_norm is not None and getattr(opt, "clips", None) is False:
+            # step(max_grad_norm=) turned clipping on: the fresh optimizer clips alike, so the
+            # resident one (and its graphs) is kept below
+            from ..optim import with_max_grad_norm
+            opt = with_max_grad_norm(opt, self._step_max_norm)
         old = self.optimizer
         if old is not None and opt is not None and _same_but_lr(old, opt):
             lr = opt.param_groups[0]["lr"]
@@ -695,16 +700,59 @@ class KubeModel(ABC):
     PEER_CHECK_EVERY = 16   # verify the peer data plane's checksums every N grad-sync steps
     COMM_TIMING = 50        # sample the in-graph all-reduce every N steps
 
-    def step(self, x, y, loss_fn=None, forward=None):
+    def _set_max_grad_norm(self, v):
+        """``step(max_grad_norm=v)``: hand the threshold to the optimizer.  A fused optimizer built
+        without clipping is rebuilt with it (same parameters and hyper-parameters, fresh state: its
+        step has other launches, so its graphs are dropped); one that clips only refills its device
+        scalar.  Returns True when the (non-fused) optimizer needs torch's clip before its step."""
+        opt = self.optimizer
+        from ..optim import FusedOptimizer
+        if not isinstance(opt, FusedOptimizer):
+            return True
+        if opt.clips:
+            if opt.param_groups[0]["max_grad_norm"] != float(v):
+                opt.set_max_grad_norm(v)
+            if self._step_max_norm is not None:
+                self._step_max_norm = float(v)
+            return False
+        if opt._step_host > 0 or not opt._first:
+            raise ValueError("step(max_grad_norm=) on an optimizer that already stepped without clipping: "
+                             "pass it from the first step, or build the optimizer with max_grad_norm=")
+        from ..optim import with_max_grad_norm
+        self._graphs.clear()   # (none yet unless a step was captured dry)
+        self._drop_shards()
+        self.optimizer = with_max_grad_norm(opt, v)
+        self._step_max_norm = float(v)
+        return False
+
+    def last_grad_norm(self) -> float:
+        """Global norm of the last step's averaged gradient, before clipping (one device read).
+        Needs a clipping optimizer (``max_grad_norm``)."""
+        opt = self.optimizer
+        if not getattr(opt, "clips", False):
+            if self._last_norm is None:
+                raise ValueError("no gradient norm: the step does not clip (pass max_grad_norm)")
+            return float(self._last_norm)
+        return float(opt.grad_norm_tensor().item())
+
+    _last_norm = None        # CPU path with a stock torch optimizer: torch's returned norm
+    _step_max_norm = None    # threshold given through step(): kept across _config_optimizer
+
+    def step(self, x, y, loss_fn=None, forward=None, max_grad_norm=None):
         """forward + loss + backward + optimizer step for one batch; on the GPU the first
         call for a given batch shape captures a hipGraph (engine/dp.py) that later calls
         replay.  In a K=1 grad-sync round the gradients are all-reduced over the worker
         group inside the step.  Returns the (device) loss tensor.  forward: optional
         ``forward(network, x, y) -> loss`` replacing ``loss_fn(network(x), y)`` — e.g. on-device
         batch preparation (masking) followed by a model call with extra arguments; it is part
-        of the captured graph, so it must be a function of x, y and device state only."""
+        of the captured graph, so it must be a function of x, y and device state only.
+        max_grad_norm: clip the global gradient norm to this value inside the step (between
+        the gradient all-reduce and the update; ``last_grad_norm()`` reads the norm).  Pass it
+        from the first step on: clipping on / off is part of the graph key and of the optimizer,
+        a changed value only refills a device scalar."""
         from ..nn import backward_loss, cross_entropy
         loss_fn = loss_fn or cross_entropy
+        torch_clip = self._set_max_grad_norm(max_grad_norm) if max_grad_norm is not None else False
         if self.device is None or self.device.type != "cuda" or os.environ.get("KUBEML_NO_GRAPH") == "1":
             self.optimizer.zero_grad()
             loss = forward(self._network, x, y) if forward is not None else loss_fn(self(x), y)
@@ -712,12 +760,17 @@ class KubeModel(ABC):
             if self._sync_mode == "grad":
                 self._allreduce_grads_eager()
                 self._synced_steps += 1
+            if torch_clip:     # a stock torch optimizer: clip between the all-reduce and its step
+                self._last_norm = torch.nn.utils.clip_grad_norm_(
+                    [p for g in self.optimizer.param_groups for p in g["params"]], float(max_grad_norm))
             self.optimizer.step()
             return loss
+        if torch_clip:
+            raise ValueError("step(max_grad_norm=) on the GPU needs a fused optimizer (SGD / Adam / AdamW)")
         grad = self._sync_mode == "grad"
         comm = self._grad_comm if grad else None
         key = (tuple(x.shape), tuple(y.shape), x.dtype, y.dtype, id(forward or loss_fn), grad,
-               id(comm) if comm is not None else None)
+               id(comm) if comm is not None else None, bool(getattr(self.optimizer, "clips", False)))
         g = self._graphs.get(key)
         if g is None:
             g = self._build_step(key, x, y, loss_fn, comm, forward)

@@ -37,6 +37,8 @@ def main():
     ap.add_argument("--layers", type=int, default=12)
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--force-comm", action="store_true", help="RCCL path even with one rank (rehearsal)")
+    ap.add_argument("--max-grad-norm", type=float, default=None, metavar="F",
+                    help="clip the global gradient norm at F inside the step (one norm launch + the fused AdamW)")
     a = ap.parse_args()
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         import torch
@@ -76,7 +78,7 @@ def main():
     if comm:
         ModelAverager(m).broadcast_(from_env(), 0)
     m.train()
-    opt = AdamW(m.parameters(), lr=1e-4, weight_decay=0.01)
+    opt = AdamW(m.parameters(), lr=1e-4, weight_decay=0.01, max_grad_norm=a.max_grad_norm)
     opt.set_grad_scale(1.0 / world)
     B, L, P, V = a.batch, a.seq, a.preds, 30522
     g = torch.Generator(device=dev).manual_seed(1 + rank)
@@ -134,6 +136,9 @@ def main():
                "data": "synthetic tokens, random init", "graph": not a.no_graph, "overlap_segments": len(segs),
                "loss_first_last": [round(first, 4), round(float(loss.detach()), 4)],
                "gemm": "gemm.hip (wgrad, FFN2 dgrad + GELU backward) / hipBLASLt (plain fwd, dgrad: gemm_tuning.json)"}
+        if a.max_grad_norm is not None:
+            out["max_grad_norm"] = a.max_grad_norm
+            out["last_grad_norm"] = round(float(opt.grad_norm_tensor(dev)), 4)
         if in_sync is not None:
             out["ranks_in_sync"] = in_sync
         print(json.dumps(out), flush=True)
