@@ -5,6 +5,41 @@
 #pragma once
 #include "kml_common.h"
 
+// float4 `i` of one flat range: load, the torch.optim.SGD recurrence, store master / momentum / bf16
+// shadow.  The one element update of every fused-SGD launch: k_sgd and the riders reach it through
+// kml_sgd_range with one (lr, wd) per launch, k_sgd_groups (optim.hip) with its granule's pair, so
+// an element of group k comes out bit for bit as from a single-group launch with group k's values
+__device__ __forceinline__ void kml_sgd_vec4(float* __restrict__ w, const float* __restrict__ g,
+                                             float* __restrict__ mom, bf16_t* __restrict__ shadow, float lr, float wd,
+                                             float momentum, float dampening, int nesterov, int first,
+                                             float grad_scale, long long i) {
+  float4 W = reinterpret_cast<float4*>(w)[i];
+  const float4 G = reinterpret_cast<const float4*>(g)[i];
+  float wv[4] = {W.x, W.y, W.z, W.w}, gv[4] = {G.x, G.y, G.z, G.w};
+  float mv[4] = {0, 0, 0, 0};
+  if (mom && momentum != 0.f) {
+    const float4 Mv = reinterpret_cast<float4*>(mom)[i];
+    mv[0] = Mv.x; mv[1] = Mv.y; mv[2] = Mv.z; mv[3] = Mv.w;
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    float d = gv[k] * grad_scale + wd * wv[k];
+    if (mom && momentum != 0.f) {
+      mv[k] = first ? d : momentum * mv[k] + (1.f - dampening) * d;
+      d = nesterov ? d + momentum * mv[k] : mv[k];
+    }
+    wv[k] -= lr * d;
+  }
+  reinterpret_cast<float4*>(w)[i] = make_float4(wv[0], wv[1], wv[2], wv[3]);
+  if (mom && momentum != 0.f) reinterpret_cast<float4*>(mom)[i] = make_float4(mv[0], mv[1], mv[2], mv[3]);
+  if (shadow) {
+    uint2 s;
+    s.x = pack_bf2(wv[0], wv[1]);
+    s.y = pack_bf2(wv[2], wv[3]);
+    reinterpret_cast<uint2*>(shadow)[i] = s;
+  }
+}
+
 // elements [0, n) of one flat range, visited by virtual thread t0 of `stride` (float4 body, then
 // the scalar tail); lr and first already resolved from device memory by the caller
 __device__ __forceinline__ void kml_sgd_range(float* __restrict__ w, const float* __restrict__ g,
@@ -12,33 +47,8 @@ __device__ __forceinline__ void kml_sgd_range(float* __restrict__ w, const float
                                               float momentum, float dampening, int nesterov, int first,
                                               float grad_scale, long long n, long long t0, long long stride) {
   const long long n4 = n >> 2;
-  for (long long i = t0; i < n4; i += stride) {
-    float4 W = reinterpret_cast<float4*>(w)[i];
-    const float4 G = reinterpret_cast<const float4*>(g)[i];
-    float wv[4] = {W.x, W.y, W.z, W.w}, gv[4] = {G.x, G.y, G.z, G.w};
-    float mv[4] = {0, 0, 0, 0};
-    if (mom && momentum != 0.f) {
-      const float4 Mv = reinterpret_cast<float4*>(mom)[i];
-      mv[0] = Mv.x; mv[1] = Mv.y; mv[2] = Mv.z; mv[3] = Mv.w;
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      float d = gv[k] * grad_scale + wd * wv[k];
-      if (mom && momentum != 0.f) {
-        mv[k] = first ? d : momentum * mv[k] + (1.f - dampening) * d;
-        d = nesterov ? d + momentum * mv[k] : mv[k];
-      }
-      wv[k] -= lr * d;
-    }
-    reinterpret_cast<float4*>(w)[i] = make_float4(wv[0], wv[1], wv[2], wv[3]);
-    if (mom && momentum != 0.f) reinterpret_cast<float4*>(mom)[i] = make_float4(mv[0], mv[1], mv[2], mv[3]);
-    if (shadow) {
-      uint2 s;
-      s.x = pack_bf2(wv[0], wv[1]);
-      s.y = pack_bf2(wv[2], wv[3]);
-      reinterpret_cast<uint2*>(shadow)[i] = s;
-    }
-  }
+  for (long long i = t0; i < n4; i += stride)
+    kml_sgd_vec4(w, g, mom, shadow, lr, wd, momentum, dampening, nesterov, first, grad_scale, i);
   // scalar tail
   for (long long i = (n4 << 2) + t0; i < n; i += stride) {
     float d = g[i] * grad_scale + wd * w[i];
@@ -50,6 +60,13 @@ __device__ __forceinline__ void kml_sgd_range(float* __restrict__ w, const float
     if (shadow) shadow[i] = f2bf(w[i]);
   }
 }
+
+// ---- parameter groups (k_sgd_groups / k_adam_groups, optim.hip) --------------------------------
+// Regions of the flat space are 64-element aligned, so the group of an element is one byte per
+// 64-element granule (gid[element >> 6]) and the groups' values a small fp32 device table
+// hp[G][2] = (lr, weight_decay), read at run time like the single lr scalar.
+constexpr int KML_MAX_GROUPS = 8;
+constexpr int KML_GRANULE_SHIFT = 6;
 
 // ---- peer-shard collective slices carried as riders (parallel/peer.py ShardRider) ---------------
 // At N > 1 the sharded update (ZeRO-1 over IPC-mapped HBM, comm.hip k_zs_*) of the parameters

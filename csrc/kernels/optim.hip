@@ -43,6 +43,92 @@ __global__ void k_sgd(float* __restrict__ w, const float* __restrict__ g, float*
                 blockIdx.x * (long long)blockDim.x + threadIdx.x, (long long)gridDim.x * blockDim.x);
 }
 
+// The groups' (lr, weight_decay) pairs, once per block into LDS; entries past G read as zeros and
+// a lookup masks the byte to the table's 8 entries, so no byte of gid can index outside it.
+__device__ __forceinline__ void load_group_table(float2* sh, const float* __restrict__ hp, int G) {
+  if (threadIdx.x < KML_MAX_GROUPS)
+    sh[threadIdx.x] = (int)threadIdx.x < G ? make_float2(hp[2 * threadIdx.x], hp[2 * threadIdx.x + 1])
+                                           : make_float2(0.f, 0.f);
+  __syncthreads();
+}
+
+// group of float4 `i` of a range that starts at element elem0 of the space
+__device__ __forceinline__ int group_of(const unsigned char* __restrict__ gid, long long elem0, long long i) {
+  return gid[(elem0 + 4 * i) >> KML_GRANULE_SHIFT] & (KML_MAX_GROUPS - 1);
+}
+
+// k_sgd with one (lr, weight_decay) per 64-element granule: the same single streaming launch and,
+// through kml_sgd_vec4, the same element update.  n is a multiple of 64: no scalar tail.
+__global__ void k_sgd_groups(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ mom,
+                             bf16_t* __restrict__ shadow, const unsigned char* __restrict__ gid,
+                             const float* __restrict__ hp, int G, long long elem0, float momentum, float dampening,
+                             int nesterov, const float* __restrict__ first_ptr, int first_host, float grad_scale,
+                             long long n, float* __restrict__ adv_ctr, float adv_batch, float adv_n,
+                             const float* __restrict__ clip_ptr) {
+  __shared__ float2 sh_hp[KML_MAX_GROUPS];
+  if (adv_ctr && blockIdx.x == 0 && threadIdx.x == 0) {  // the folded data-counter advance, as k_sgd
+    adv_ctr[1] += 1.f;
+    float st = adv_ctr[2] + adv_batch;
+    if (st >= adv_n) st -= adv_n;
+    adv_ctr[2] = st;
+  }
+  load_group_table(sh_hp, hp, G);
+  const int first = first_ptr ? (*first_ptr != 0.f) : first_host;
+  if (clip_ptr) grad_scale *= *clip_ptr;
+  const long long n4 = n >> 2;
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n4; i += stride) {
+    const float2 h = sh_hp[group_of(gid, elem0, i)];
+    kml_sgd_vec4(w, g, mom, shadow, h.x, h.y, momentum, dampening, nesterov, first, grad_scale, i);
+  }
+}
+
+// The torch.optim.Adam / AdamW element update (L2 or decoupled decay) of float4 `i`, already loaded
+// as W / G / M / V, and the stores of master, moments and bf16 shadow.  Shared by k_adam (one lr /
+// wd per launch) and k_adam_groups (its granule's), so both give the same bits for the same values.
+// step_size = lr / (1 - b1^t), rbc2 = rsqrt(1 - b2^t)
+__device__ __forceinline__ void adam_vec4(float* __restrict__ w, float* __restrict__ m, float* __restrict__ v,
+                                          bf16_t* __restrict__ shadow, const float4& W, const float4& G,
+                                          const float4& M, const float4& V, float lr, float wd, float step_size,
+                                          float rbc2, float b1, float b2, float eps, int decoupled, float grad_scale,
+                                          long long i) {
+  float wv[4] = {W.x, W.y, W.z, W.w}, gv[4] = {G.x, G.y, G.z, G.w};
+  float mv[4] = {M.x, M.y, M.z, M.w}, vv[4] = {V.x, V.y, V.z, V.w};
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    // The roundings are spelled out.  Left to -ffp-contract=fast, which product of
+    // b * x + (1 - b) * y is fused, and whether sqrt(v) * rbc2 + eps is, depends on the surrounding
+    // code (the vectoriser pairs some of the products first), so two kernels inlining this body
+    // could round differently.  These are the forms k_adam has always compiled to, element by
+    // element: its results must not change.  In particular the first three elements of a float4
+    // round sqrt(v) * rbc2 before adding eps (that product was paired with step_size * m), the
+    // fourth fuses the two.
+    float gg = gv[k] * grad_scale;
+    if (decoupled) wv[k] *= __builtin_fmaf(-lr, wd, 1.f);
+    else gg = __builtin_fmaf(wd, wv[k], gg);
+    mv[k] = __builtin_fmaf(b1, mv[k], (1.f - b1) * gg);
+    vv[k] = __builtin_fmaf(b2, vv[k], (1.f - b2) * gg * gg);
+    float denom;
+    if (k < 3) {
+      float q = sqrtf(vv[k]) * rbc2;
+      asm volatile("" : "+v"(q));   // a rounded product of its own (contract pragmas are ignored)
+      denom = q + eps;
+    } else {
+      denom = __builtin_fmaf(sqrtf(vv[k]), rbc2, eps);
+    }
+    wv[k] -= step_size * mv[k] / denom;
+  }
+  reinterpret_cast<float4*>(w)[i] = make_float4(wv[0], wv[1], wv[2], wv[3]);
+  reinterpret_cast<float4*>(m)[i] = make_float4(mv[0], mv[1], mv[2], mv[3]);
+  reinterpret_cast<float4*>(v)[i] = make_float4(vv[0], vv[1], vv[2], vv[3]);
+  if (shadow) {
+    uint2 s;
+    s.x = pack_bf2(wv[0], wv[1]);
+    s.y = pack_bf2(wv[2], wv[3]);
+    reinterpret_cast<uint2*>(shadow)[i] = s;
+  }
+}
+
 __global__ void k_adam(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m,
                        float* __restrict__ v, bf16_t* __restrict__ shadow, const float* __restrict__ lr_ptr,
                        const float* __restrict__ step_ptr, float lr_host, float step_host, float b1, float b2,
@@ -76,27 +162,8 @@ __global__ void k_adam(float* __restrict__ w, const float* __restrict__ g, float
     for (int u = 0; u < U; ++u) {
       const long long i = i0 + u * stride;
       if (i >= n4) break;
-      float wv[4] = {W[u].x, W[u].y, W[u].z, W[u].w}, gv[4] = {G[u].x, G[u].y, G[u].z, G[u].w};
-      float mv[4] = {M[u].x, M[u].y, M[u].z, M[u].w}, vv[4] = {V[u].x, V[u].y, V[u].z, V[u].w};
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        float gg = gv[k] * grad_scale;
-        if (decoupled) wv[k] *= (1.f - lr * wd);
-        else gg += wd * wv[k];
-        mv[k] = b1 * mv[k] + (1.f - b1) * gg;
-        vv[k] = b2 * vv[k] + (1.f - b2) * gg * gg;
-        const float denom = sqrtf(vv[k]) * rbc2 + eps;
-        wv[k] -= step_size * mv[k] / denom;
-      }
-      reinterpret_cast<float4*>(w)[i] = make_float4(wv[0], wv[1], wv[2], wv[3]);
-      reinterpret_cast<float4*>(m)[i] = make_float4(mv[0], mv[1], mv[2], mv[3]);
-      reinterpret_cast<float4*>(v)[i] = make_float4(vv[0], vv[1], vv[2], vv[3]);
-      if (shadow) {
-        uint2 s;
-        s.x = pack_bf2(wv[0], wv[1]);
-        s.y = pack_bf2(wv[2], wv[3]);
-        reinterpret_cast<uint2*>(shadow)[i] = s;
-      }
+      adam_vec4(w, m, v, shadow, W[u], G[u], M[u], V[u], lr, wd, step_size, rbc2, b1, b2, eps, decoupled,
+                grad_scale, i);
     }
   }
   for (long long i = (n4 << 2) + blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += stride) {
@@ -109,6 +176,51 @@ __global__ void k_adam(float* __restrict__ w, const float* __restrict__ g, float
     wi -= step_size * m[i] / (sqrtf(v[i]) * rbc2 + eps);
     w[i] = wi;
     if (shadow) shadow[i] = f2bf(wi);
+  }
+}
+
+// k_adam with one (lr, weight_decay) per 64-element granule: the same single streaming launch, the
+// same two-float4 unroll and, through adam_vec4, the same element update.  Each group's step size
+// lr / (1 - b1^t) is formed once per block, as k_adam forms its one.  n is a multiple of 64.
+__global__ void k_adam_groups(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m,
+                              float* __restrict__ v, bf16_t* __restrict__ shadow,
+                              const unsigned char* __restrict__ gid, const float* __restrict__ hp, int G,
+                              long long elem0, const float* __restrict__ step_ptr, float step_host, float b1,
+                              float b2, float eps, int decoupled, float grad_scale, long long n,
+                              const float* __restrict__ clip_ptr) {
+  __shared__ float2 sh_hp[KML_MAX_GROUPS];
+  __shared__ float sh_ss[KML_MAX_GROUPS];
+  if (clip_ptr) grad_scale *= *clip_ptr;
+  const float t = step_ptr ? *step_ptr : step_host;
+  const float bc1 = 1.f - __powf(b1, t), bc2 = 1.f - __powf(b2, t);
+  const float rbc2 = rsqrtf(bc2);
+  if (threadIdx.x < KML_MAX_GROUPS) sh_ss[threadIdx.x] = (int)threadIdx.x < G ? hp[2 * threadIdx.x] / bc1 : 0.f;
+  load_group_table(sh_hp, hp, G);
+  const long long n4 = n >> 2;
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  constexpr int U = 2;
+  for (long long i0 = blockIdx.x * (long long)blockDim.x + threadIdx.x; i0 < n4; i0 += U * stride) {
+    float4 W[U], Gr[U], M[U], V[U];
+    int grp[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const long long i = i0 + u * stride;
+      if (i < n4) {
+        W[u] = reinterpret_cast<float4*>(w)[i];
+        Gr[u] = reinterpret_cast<const float4*>(g)[i];
+        M[u] = reinterpret_cast<float4*>(m)[i];
+        V[u] = reinterpret_cast<float4*>(v)[i];
+        grp[u] = group_of(gid, elem0, i);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const long long i = i0 + u * stride;
+      if (i >= n4) break;
+      const float2 h = sh_hp[grp[u]];
+      adam_vec4(w, m, v, shadow, W[u], Gr[u], M[u], V[u], h.x, h.y, sh_ss[grp[u]], rbc2, b1, b2, eps, decoupled,
+                grad_scale, i);
+    }
   }
 }
 
@@ -249,6 +361,43 @@ KML_API int kml_adam(float* w, const float* g, float* m, float* v, bf16_t* shado
   if (max_blocks > 0 && grid > (unsigned)max_blocks) grid = (unsigned)max_blocks;
   hipLaunchKernelGGL(k_adam, dim3(grid), dim3(256), 0, s, w, g, m, v, shadow, lr_ptr,
                      step_ptr, lr, step, b1, b2, eps, wd, decoupled, grad_scale, n, clip_ptr);
+  KML_LAUNCH_CHECK();
+}
+
+// what every grouped launch needs: whole granules (n % 64 == 0, the range starts on one), 16-byte
+// aligned buffers (a null optional buffer passes) and 1..8 groups
+static inline bool kml_groups_ok(long long n, long long elem0, int G, const void* gid, const void* hp,
+                                 const void* a, const void* b, const void* c, const void* d, const void* e) {
+  const uintptr_t bits = (uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d | (uintptr_t)e;
+  return n >= 0 && elem0 >= 0 && (n & 63) == 0 && (elem0 & 63) == 0 && G >= 1 && G <= KML_MAX_GROUPS && gid && hp &&
+         a && b && (bits & 15) == 0;
+}
+
+// kml_sgd with per-granule (lr, weight_decay): gid is the byte table of the whole space (one group
+// id per 64 elements), elem0 the offset of w / g / mom / shadow into that space, hp the fp32 device
+// table hp[G][2].  Everything else as kml_sgd.
+KML_API int kml_sgd_groups(float* w, const float* g, float* mom, bf16_t* shadow, const unsigned char* gid,
+                           const float* hp, int G, long long elem0, float momentum, float dampening, int nesterov,
+                           const float* first_ptr, int first, float grad_scale, long long n, int max_blocks,
+                           float* adv_ctr, float adv_batch, float adv_n, const float* clip_ptr, hipStream_t s) {
+  if (!kml_groups_ok(n, elem0, G, gid, hp, w, g, mom, shadow, nullptr)) return (int)hipErrorInvalidValue;
+  unsigned grid = kml_stream_grid((n + 3) / 4, 256);
+  if (max_blocks > 0 && grid > (unsigned)max_blocks) grid = (unsigned)max_blocks;
+  hipLaunchKernelGGL(k_sgd_groups, dim3(grid), dim3(256), 0, s, w, g, mom, shadow, gid, hp, G, elem0, momentum,
+                     dampening, nesterov, first_ptr, first, grad_scale, n, adv_ctr, adv_batch, adv_n, clip_ptr);
+  KML_LAUNCH_CHECK();
+}
+
+// kml_adam with per-granule (lr, weight_decay); gid / hp / G / elem0 as kml_sgd_groups
+KML_API int kml_adam_groups(float* w, const float* g, float* m, float* v, bf16_t* shadow, const unsigned char* gid,
+                            const float* hp, int G, long long elem0, const float* step_ptr, float step, float b1,
+                            float b2, float eps, int decoupled, float grad_scale, long long n, int max_blocks,
+                            const float* clip_ptr, hipStream_t s) {
+  if (!m || !v || !kml_groups_ok(n, elem0, G, gid, hp, w, g, m, v, shadow)) return (int)hipErrorInvalidValue;
+  unsigned grid = kml_stream_grid((n + 3) / 4, 256);
+  if (max_blocks > 0 && grid > (unsigned)max_blocks) grid = (unsigned)max_blocks;
+  hipLaunchKernelGGL(k_adam_groups, dim3(grid), dim3(256), 0, s, w, g, m, v, shadow, gid, hp, G, elem0, step_ptr,
+                     step, b1, b2, eps, decoupled, grad_scale, n, clip_ptr);
   KML_LAUNCH_CHECK();
 }
 

@@ -47,6 +47,19 @@ def optimizer_can_shard(optimizer) -> bool:
                 or getattr(optimizer, "supports_shard_range", lambda: False)())
 
 
+def optimizer_grouped(optimizer) -> bool:
+    """True when the optimizer has several parameter groups (per-group lr / weight decay)."""
+    return bool(getattr(optimizer, "grouped", False))
+
+
+def _scalar_sgd(optimizer) -> bool:
+    """The fused SGD whose one (lr, weight decay) a foreign launch can bake in: the SGD riders and
+    the in-collective update of the shard transport.  A grouped optimizer has a pair per granule
+    and takes the route Adam takes instead: the update is a ``step`` / ``step_range`` of its own."""
+    return (getattr(optimizer, "kind", None) == "sgd" and optimizer.supports_ranges()
+            and not optimizer_grouped(optimizer))
+
+
 def make_train_step(model: torch.nn.Module, space, optimizer, loss_fn: Callable, x: torch.Tensor,
                     y: torch.Tensor, *, pre: Optional[Callable[[], None]] = None,
                     post: Optional[Callable[[], None]] = None, group=None, world: int = 1,
@@ -110,15 +123,14 @@ def make_train_step(model: torch.nn.Module, space, optimizer, loss_fn: Callable,
         # the sharded update of the stages whose gradients are final early (ResNet: layer4 + fc,
         # then layer3) rides in later backward launches of the same queue (_shard_ride)
         ride_shard = (forward is None and hasattr(model, "comm_ride_plan") and
-                      getattr(optimizer, "kind", None) == "sgd" and optimizer.supports_ranges() and
-                      bool(model.comm_ride_plan()))
+                      _scalar_sgd(optimizer) and bool(model.comm_ride_plan()))
         from ..parallel.plan import CommPlan
         plan = CommPlan("peer", "shard", plan.wire, plan.max_blocks,
                         source=plan.source + ("" if ride_shard else " (shardride -> shard: no ride plan / fused SGD)"))
     if plan is not None and plan.schedule == "shardov":
         # per-stage shard steps need stage-contiguous gradient ranges and the fused SGD
         staged_shard = (forward is None and hasattr(model, "stages") and hasattr(model, "stage_params") and
-                        getattr(optimizer, "kind", None) == "sgd" and optimizer.supports_ranges())
+                        _scalar_sgd(optimizer))
         from ..parallel.plan import CommPlan
         plan = CommPlan("peer", "shard", plan.wire, plan.max_blocks,
                         source=plan.source + ("" if staged_shard else " (shardov -> shard: no stages / fused SGD)"))
@@ -242,9 +254,20 @@ def make_train_step(model: torch.nn.Module, space, optimizer, loss_fn: Callable,
             return loss
     if ride is None:
         ride = os.environ.get("KUBEML_RIDE", "1") == "1"
-    riding = bool(ride and fwd_bwd is not None and not comm and shard is None and seg_opt is None
-                  and forward is None and hasattr(model, "ride_plan") and getattr(optimizer, "kind", None) == "sgd"
-                  and optimizer.supports_ranges() and space.grad.is_cuda and bool(model.ride_plan()))
+    ride_ok = bool(ride and fwd_bwd is not None and not comm and shard is None and seg_opt is None
+                   and forward is None and hasattr(model, "ride_plan") and space.grad.is_cuda)
+    ride_ok = bool(ride_ok and model.ride_plan())
+    riding = bool(ride_ok and _scalar_sgd(optimizer))
+    if optimizer_grouped(optimizer):
+        # one line per step built, and only where the grouped optimizer's route is the unfused one
+        sgd = getattr(optimizer, "kind", None) == "sgd" and optimizer.supports_ranges()
+        if shard is not None:
+            _log.warning("parameter groups: unfused route, the shard plan reduces into the own gradient chunk and "
+                         "updates it with the optimizer's step_range%s",
+                         " (not inside the collective: that update takes one lr / weight decay)" if sgd else "")
+        elif ride_ok and sgd:
+            _log.warning("parameter groups: unfused route, the update is the optimizer's own launch after the "
+                         "backward (SGD riders take one lr / weight decay)")
     if riding:
         fwd_bwd, opt_step = _ride(model, space, optimizer, fwd_bwd, post, lambda: fold, scale)
     shard_step = on_replay = seg_shard = None
@@ -252,7 +275,7 @@ def make_train_step(model: torch.nn.Module, space, optimizer, loss_fn: Callable,
     shard_ride_info = None
     if shard is not None:
         blocks = plan.max_blocks
-        fused_sgd = getattr(optimizer, "kind", None) == "sgd" and optimizer.supports_ranges()
+        fused_sgd = _scalar_sgd(optimizer)
         # the parameters the step reads from the fp32 master (BN / LN affine, biases) are re-read
         # from their owners after every step: the ZeRO-1 master is current only on own chunks
         shard.set_fresh([space.range_of([p]) for p in model.parameters() if p.requires_grad and p.dim() == 1])
@@ -286,6 +309,7 @@ def make_train_step(model: torch.nn.Module, space, optimizer, loss_fn: Callable,
                 shard.reduce_scatter(None, max_blocks=blocks, stamp=s0)
                 optimizer.set_grad_scale(scale)
                 optimizer.step_range(shard.lo, shard.hi, max_blocks=blocks)
+                getattr(optimizer, "finish_ranges", lambda: None)()   # grouped SGD: its first-step flag
                 if fold is not None:
                     from ..ops import kernels as K
                     K.advance_counter_(*fold)

@@ -207,6 +207,12 @@ class FlatParamSpace:
         o, n = self.offsets[i]
         return o, -(-n // ALIGN) * ALIGN
 
+    def region_of(self, p):
+        """(offset, padded element count) of parameter ``p``'s 64-aligned storage region, or None
+        when ``p`` is not in this space."""
+        i = self._index.get(id(p)) if getattr(p, "_kml_flat", None) is self else None
+        return None if i is None else self._region(i)
+
     def _zero_params(self, idx):
         """Zero the grad regions of the given parameter indices (merged runs, one launch per
         ``kml_zero_ranges_max()`` runs; the whole buffer when that is fewer launches)."""

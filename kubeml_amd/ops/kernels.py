@@ -1720,6 +1720,75 @@ def adam_(w, g, m, v, shadow, lr, step, b1=0.9, b2=0.999, eps=1e-8, wd=0.0, deco
              int(decoupled), float(grad_scale), n, int(max_blocks), _p(clip_dev), _s())
 
 
+MAX_PARAM_GROUPS = 8     # KML_MAX_GROUPS
+GROUP_GRANULE = 64       # elements per group-id byte (nn/flat.py ALIGN)
+
+
+def _chk_groups(name, w, bufs, gid, hp, elem0):
+    """Argument checks of a grouped launch (nothing reaches the kernel otherwise); returns G."""
+    _chk(w, F32, "w")
+    if gid.dtype != torch.uint8 or not gid.is_cuda or not gid.is_contiguous() or gid.device != w.device:
+        raise ValueError(f"{name}: gid must be a contiguous uint8 tensor on the parameters' device")
+    _chk(hp, F32, "hp")
+    if hp.dim() != 2 or hp.shape[1] != 2 or hp.device != w.device:
+        raise ValueError(f"{name}: hp must be an fp32 [G, 2] table of (lr, weight_decay) on the parameters' device")
+    G = int(hp.shape[0])
+    if not 1 <= G <= MAX_PARAM_GROUPS:
+        raise ValueError(f"{name}: {G} parameter groups (1 to {MAX_PARAM_GROUPS} supported)")
+    n, elem0 = w.numel(), int(elem0)
+    if n % GROUP_GRANULE:
+        raise ValueError(f"{name}: {n} elements are not whole {GROUP_GRANULE}-element granules")
+    if elem0 < 0 or elem0 % GROUP_GRANULE:
+        raise ValueError(f"{name}: the range must start on a {GROUP_GRANULE}-element granule (elem0 = {elem0})")
+    if (elem0 + n) // GROUP_GRANULE > gid.numel():
+        raise ValueError(f"{name}: gid has {gid.numel()} granules, the range ends at {(elem0 + n) // GROUP_GRANULE}")
+    for nm, t, dt in bufs:
+        if t is None:
+            continue
+        _chk(t, dt, nm)
+        if t.numel() != n or t.device != w.device:
+            raise ValueError(f"{name}: {nm} must match w ({n} elements, same device)")
+        if t.data_ptr() % 16:
+            raise ValueError(f"{name}: {nm} must be 16-byte aligned")
+    return G
+
+
+def sgd_groups_(w, g, mom, shadow, gid, hp, elem0=0, momentum=0.0, dampening=0.0, nesterov=False, first=False,
+                grad_scale=1.0, first_dev=None, max_blocks=0, advance=None, clip_dev=None):
+    """:func:`sgd_` with the learning rate and weight decay of each 64-element granule taken from
+    the fp32 device table ``hp`` ([G, 2] rows of (lr, weight_decay), G <= 8) through the granule's
+    byte in ``gid`` (uint8, one per 64 elements of the whole flat space).  ``elem0`` is the offset
+    of ``w`` in that space (a multiple of 64, as is ``w.numel()``).  Still one launch; an element of
+    group k comes out bit for bit as from ``sgd_`` with group k's values."""
+    G = _chk_groups("sgd_groups_", w, (("w", w, F32), ("g", g, F32), ("mom", mom, F32), ("shadow", shadow, BF16)),
+                    gid, hp, elem0)
+    _chk_clip(clip_dev, w)
+    ctr, ab, an = None, 0.0, 0.0
+    if advance is not None:
+        ctr, ab, an = advance
+        _chk(ctr, F32, "ctr")
+        if ctr.numel() < 3 or ctr.device != w.device:
+            raise ValueError("advance counter must be a [3] fp32 tensor on the parameters' device")
+        ab, an = float(ab), float(an)
+    HIP.call("kml_sgd_groups", "p p p p p p i l f f i p i f l i p f f p s", _p(w), _p(g), _p(mom), _p(shadow),
+             _p(gid), _p(hp), G, int(elem0), float(momentum), float(dampening), int(nesterov), _p(first_dev),
+             int(first), float(grad_scale), w.numel(), int(max_blocks), _p(ctr), ab, an, _p(clip_dev), _s())
+
+
+def adam_groups_(w, g, m, v, shadow, gid, hp, step, elem0=0, b1=0.9, b2=0.999, eps=1e-8, decoupled=False,
+                 grad_scale=1.0, step_dev=None, max_blocks=0, clip_dev=None):
+    """:func:`adam_` with per-granule (lr, weight_decay): ``gid`` / ``hp`` / ``elem0`` as
+    :func:`sgd_groups_`.  One launch; group k's elements are bit-identical to ``adam_`` with its values."""
+    G = _chk_groups("adam_groups_", w, (("w", w, F32), ("g", g, F32), ("m", m, F32), ("v", v, F32),
+                                        ("shadow", shadow, BF16)), gid, hp, elem0)
+    if m is None or v is None:
+        raise ValueError("adam_groups_: the moment buffers m and v are required")
+    _chk_clip(clip_dev, w)
+    HIP.call("kml_adam_groups", "p p p p p p p i l p f f f f i f l i p s", _p(w), _p(g), _p(m), _p(v), _p(shadow),
+             _p(gid), _p(hp), G, int(elem0), _p(step_dev), float(step), float(b1), float(b2), float(eps),
+             int(decoupled), float(grad_scale), w.numel(), int(max_blocks), _p(clip_dev), _s())
+
+
 def increment_(t, by=1.0):
     HIP.call("kml_increment", "p f s", _p(t), float(by), _s())
 

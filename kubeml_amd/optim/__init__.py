@@ -27,9 +27,17 @@ its gradient scale — no extra pass over the gradient.  The threshold is a devi
 is fixed at construction (it decides the step's launches).  ``grad_norm_tensor`` is the
 norm of the last step's averaged gradient.
 
+Parameter groups may differ in ``lr`` and ``weight_decay`` (the no-decay idiom for biases and
+norm weights, layer-wise LR decay); every other hyper-parameter is one value for the optimizer.
+A grouped step is still one launch (``kml_sgd_groups`` / ``kml_adam_groups``): a byte per
+64-element granule of the flat space names its group and a small fp32 device table holds the
+groups' (lr, weight_decay), so a captured step follows ``set_lr([...])`` as it follows the single
+LR scalar.  A single-group optimizer launches exactly what it always did.
+:func:`no_decay_groups` builds the usual two groups of a module.
+
 ``from_torch(opt)`` converts a user's ``torch.optim.SGD/Adam/AdamW`` (what
 ``KubeModel.configure_optimizers`` returns in reference code) into the fused one
-with identical hyper-parameters.
+with identical hyper-parameters, group by group.
 """
 from __future__ import annotations
 
@@ -37,7 +45,10 @@ from typing import Dict, List
 
 import torch
 
-__all__ = ["SGD", "Adam", "AdamW", "from_torch", "with_max_grad_norm", "FusedOptimizer"]
+__all__ = ["SGD", "Adam", "AdamW", "from_torch", "with_max_grad_norm", "no_decay_groups", "FusedOptimizer"]
+
+MAX_GROUPS = 8            # rows of the kernels' hyper-parameter table (KML_MAX_GROUPS)
+_PER_GROUP = ("lr", "weight_decay")     # what may differ between parameter groups
 
 
 def _spaces(params):
@@ -68,9 +79,107 @@ class FusedOptimizer(torch.optim.Optimizer):
         self._max_norm_dev: Dict[torch.device, torch.Tensor] = {}
         self._norm_out: Dict[torch.device, torch.Tensor] = {}
         self._norm_host = None     # CPU / loose-parameter path: the last step's norm
+        self._gid_dev: Dict[int, torch.Tensor] = {}    # id(space) -> uint8 group id per granule
+        self._hp_dev: Dict[int, torch.Tensor] = {}     # id(space) -> fp32 [G, 2] (lr, weight_decay)
+        self._hp_host: Dict[int, list] = {}            # id(space) -> the rows hp holds
         mgn = self.defaults.get("max_grad_norm")
         if mgn is not None and not float(mgn) > 0.0:
             raise ValueError("max_grad_norm must be a positive number or None")
+        self._check_groups()
+
+    # --- parameter groups ---------------------------------------------------------------
+    @property
+    def grouped(self) -> bool:
+        """True with more than one parameter group (per-group ``lr`` / ``weight_decay``)."""
+        return len(self.param_groups) > 1
+
+    def _check_groups(self):
+        """Groups may differ in lr and weight_decay only, there are at most MAX_GROUPS of them,
+        and on a GPU all their parameters share one flat space (the one launch's range)."""
+        groups = self.param_groups
+        if len(groups) > MAX_GROUPS:
+            raise ValueError(f"{len(groups)} parameter groups: the fused optimizers take at most {MAX_GROUPS}")
+        for key in self.defaults:
+            if key in _PER_GROUP:
+                continue
+            for g in groups[1:]:
+                a, b = groups[0][key], g[key]
+                if (tuple(a) != tuple(b)) if isinstance(a, (tuple, list)) else (a != b):
+                    raise ValueError(f"parameter groups differ in {key!r}: only lr and weight_decay may differ "
+                                     f"between the groups of a fused optimizer")
+        if self.grouped:
+            spaces, loose = self._flat_groups()
+            if any(p.is_cuda for g in groups for p in g["params"]) and (len(spaces) != 1 or loose):
+                raise ValueError("a GPU optimizer with several parameter groups needs every parameter in one "
+                                 "flat space (nn.flatten_module)")
+
+    def _group_rows(self):
+        return [[float(g["lr"]), float(g["weight_decay"])] for g in self.param_groups]
+
+    def add_param_group(self, param_group):
+        """torch's, then the checks of the constructor; the cached group tables are rebuilt."""
+        super().add_param_group(param_group)
+        if hasattr(self, "_gid_dev"):          # (torch's constructor adds the first groups itself)
+            self._gid_dev.clear()
+            self._hp_dev.clear()
+            self._hp_host.clear()
+            self._check_groups()
+
+    def group_ids(self, sp) -> torch.Tensor:
+        """uint8 CPU tensor, one group index per 64-element granule of flat space ``sp`` (regions
+        are 64-aligned; a region's padding belongs to its parameter's group).  Granules of
+        parameters of the space that are in no group of this optimizer stay at 0: the launch
+        covers the whole space, as the single-group launch does, so they see group 0's values
+        (their gradient is zero unless something else writes it)."""
+        from ..nn.flat import ALIGN
+        gid = torch.zeros(sp.numel // ALIGN, dtype=torch.uint8)
+        for k, g in enumerate(self.param_groups):
+            for p in g["params"]:
+                region = sp.region_of(p)
+                if region is None:
+                    raise ValueError("parameter groups need every parameter in one flat space")
+                o, n = region
+                gid[o // ALIGN:(o + n) // ALIGN] = k
+        return gid
+
+    def group_tables(self, sp):
+        """(gid, hp) device tensors of the grouped launches over GPU space ``sp``: the granule
+        bytes and the fp32 [G, 2] rows of (lr, weight_decay).  Scratch like the clip scalars, not
+        optimizer state.  An eager step refreshes hp when ``param_groups[k]["lr"]`` or
+        ``["weight_decay"]`` were written directly (an LR scheduler); a captured step reads the
+        table as it stands, so between replays use :meth:`set_lr` or call this method."""
+        key = id(sp)
+        rows = self._group_rows()
+        if key not in self._gid_dev:
+            spaces, loose = self._flat_groups()
+            if len(spaces) != 1 or loose or spaces[0][0] is not sp:
+                raise ValueError("a GPU optimizer with several parameter groups needs every parameter in one "
+                                 "flat space")
+            self._gid_dev[key] = self.group_ids(sp).to(sp.device)
+            self._hp_dev[key] = torch.tensor(rows, dtype=torch.float32).to(sp.device)
+            self._hp_host[key] = rows
+        elif rows != self._hp_host[key] and not torch.cuda.is_current_stream_capturing():
+            self._hp_dev[key].copy_(torch.tensor(rows, dtype=torch.float32))
+            self._hp_host[key] = rows
+        return self._gid_dev[key], self._hp_dev[key]
+
+    def _elem_values(self, sp, start, end):
+        """(lr, weight_decay) per element of [start, end) of a CPU flat space, as fp32 vectors."""
+        from ..nn.flat import ALIGN
+        hp = torch.tensor(self._group_rows(), dtype=torch.float32)
+        idx = self.group_ids(sp).long().repeat_interleave(ALIGN)[start:end]
+        return hp[idx, 0], hp[idx, 1]
+
+    def _members(self, params):
+        """[(group, its parameters among ``params``)], in group order."""
+        ids = {id(p) for p in params}
+        return [(g, [p for p in g["params"] if id(p) in ids]) for g in self.param_groups]
+
+    @staticmethod
+    def _check_granules(start, end):
+        if start % 64 or (end - start) % 64:
+            raise ValueError(f"a grouped step_range covers whole 64-element granules from an aligned start "
+                             f"(got [{start}, {end}))")
 
     # --- global-norm clipping ---------------------------------------------------------
     @property
@@ -156,11 +265,26 @@ class FusedOptimizer(torch.optim.Optimizer):
             self._lr_dev[device] = t
         return t
 
-    def set_lr(self, lr: float):
-        for g in self.param_groups:
-            g["lr"] = lr
+    def set_lr(self, lr):
+        """A number sets every group's LR; a sequence sets one LR per group (in group order).
+        The device scalar (group 0's LR) and the grouped launches' table follow, so a captured
+        step runs with the new values without re-capture."""
+        if isinstance(lr, (list, tuple)) or (isinstance(lr, torch.Tensor) and lr.dim() > 0):
+            lrs = [float(v) for v in lr]
+            if len(lrs) != len(self.param_groups):
+                raise ValueError(f"set_lr: {len(lrs)} learning rates for {len(self.param_groups)} parameter groups")
+            for g, v in zip(self.param_groups, lrs):
+                g["lr"] = v
+            lr = lrs[0]
+        else:
+            for g in self.param_groups:
+                g["lr"] = lr
         for t in self._lr_dev.values():
             t.fill_(float(lr))
+        rows = self._group_rows()
+        for key, t in self._hp_dev.items():
+            t.copy_(torch.tensor(rows, dtype=torch.float32))
+            self._hp_host[key] = rows
 
     def set_grad_scale(self, s: float):
         """Folded into the step: the DP all-reduce SUMs, the optimizer averages."""
@@ -226,6 +350,8 @@ class FusedOptimizer(torch.optim.Optimizer):
             if self.clips:            # scratch of the norm launch, not optimizer state
                 self.max_norm_tensor(sp.device)
                 self._norm_out_tensor(sp.device)
+            if self.grouped:          # the grouped launches' tables: scratch as well
+                self.group_tables(sp)
         return self
 
     def state_tensors(self) -> List[torch.Tensor]:
@@ -254,8 +380,6 @@ class SGD(FusedOptimizer):
                  max_grad_norm=None):
         super().__init__(params, dict(lr=lr, momentum=momentum, dampening=dampening,
                                       weight_decay=weight_decay, nesterov=nesterov, max_grad_norm=max_grad_norm))
-        if len(self.param_groups) > 1:
-            raise ValueError("fused SGD supports a single param group")
 
     def fuse_advance(self, ctr, batch, n) -> bool:
         """Can ``step(advance=(ctr, batch, n))`` advance the on-device data-sampler counter
@@ -280,15 +404,22 @@ class SGD(FusedOptimizer):
             mom = self._bufs(sp, ["momentum"])["momentum"] if g["momentum"] != 0 else None
             first = self.first_tensor(sp.device) if mom is not None else None
             clip = self._clip_dev(sp, loose) if self.clips else None
-            K.sgd_(sp.master, sp.grad, mom, sp.shadow, g["lr"], wd=g["weight_decay"], momentum=g["momentum"],
-                   dampening=g["dampening"], nesterov=g["nesterov"], first=self._first,
-                   grad_scale=self._grad_scale, lr_dev=self.lr_tensor(sp.device), first_dev=first,
-                   advance=advance if k == 0 else None, clip_dev=clip)
+            if self.grouped:
+                gid, hp = self.group_tables(sp)
+                K.sgd_groups_(sp.master, sp.grad, mom, sp.shadow, gid, hp, 0, momentum=g["momentum"],
+                              dampening=g["dampening"], nesterov=g["nesterov"], first=self._first,
+                              grad_scale=self._grad_scale, first_dev=first, advance=advance, clip_dev=clip)
+            else:
+                K.sgd_(sp.master, sp.grad, mom, sp.shadow, g["lr"], wd=g["weight_decay"], momentum=g["momentum"],
+                       dampening=g["dampening"], nesterov=g["nesterov"], first=self._first,
+                       grad_scale=self._grad_scale, lr_dev=self.lr_tensor(sp.device), first_dev=first,
+                       advance=advance if k == 0 else None, clip_dev=clip)
             if first is not None:
                 K.fill_(first, 0.0)
         if loose:
             coef = self._clip_loose(loose) if self.clips else 1.0
-            _torch_sgd(loose, g, self.state, self._grad_scale * coef)
+            for gr, ps in self._members(loose):
+                _torch_sgd(ps, gr, self.state, self._grad_scale * coef)
         self._first = False
         return loss
 
@@ -318,12 +449,28 @@ class SGD(FusedOptimizer):
             raise ValueError("step_range needs all parameters in one flat space")
         sp = spaces[0][0]
         mom =self._bufs(sp, ["momentum"])["momentum"] if g["momentum"] != 0 else None
+        if self.grouped:
+            self._check_granules(start, end)
         if sp.device.type != "cuda":
+            if self.grouped:      # the same ops with each element's own lr and weight decay
+                lr, wd = self._elem_values(sp, start, end)
+                g = dict(g, lr=lr, weight_decay=wd)
             _sgd_range_cpu(sp, start, end, g, mom, self._first, self._grad_scale)
             return
         sp.finish_grads_range(start, end)
         from ..ops import kernels as K
         first = self.first_tensor(sp.device) if mom is not None else None
+        if self.grouped:
+            if end > start:
+                gid, hp = self.group_tables(sp)
+                K.sgd_groups_(sp.master[start:end], sp.grad[start:end], None if mom is None else mom[start:end],
+                              None if sp.shadow is None else sp.shadow[start:end], gid, hp, start,
+                              momentum=g["momentum"], dampening=g["dampening"], nesterov=g["nesterov"],
+                              first=self._first, grad_scale=self._grad_scale, first_dev=first,
+                              max_blocks=max_blocks or _RANGE_BLOCKS, advance=advance)
+            elif advance is not None:
+                K.advance_counter_(*advance)
+            return
         K.sgd_(sp.master[start:end], sp.grad[start:end], None if mom is None else mom[start:end],
                None if sp.shadow is None else sp.shadow[start:end], g["lr"], wd=g["weight_decay"],
                momentum=g["momentum"], dampening=g["dampening"], nesterov=g["nesterov"], first=self._first,
@@ -350,7 +497,10 @@ def _sgd_range_cpu(sp, start, end, g, mom, first, grad_scale):
     counter, which a range update must not bump while other stages' backward still runs."""
     w, gr = sp.master.data[start:end], sp.grad.data[start:end]
     d = gr * grad_scale if grad_scale != 1.0 else gr          # op for op as _torch_sgd
-    if g["weight_decay"]:
+    per_elem = isinstance(g["lr"], torch.Tensor)    # a grouped optimizer: lr / weight decay vectors
+    if per_elem:
+        d = d + g["weight_decay"] * w
+    elif g["weight_decay"]:
         d = d.add(w, alpha=g["weight_decay"])
     if mom is not None:
         m = mom.data[start:end]
@@ -359,7 +509,10 @@ def _sgd_range_cpu(sp, start, end, g, mom, first, grad_scale):
         else:
             m.mul_(g["momentum"]).add_(d, alpha=1 - g["dampening"])
         d = d.add(m, alpha=g["momentum"]) if g["nesterov"] else m
-    w.add_(d, alpha=-g["lr"])
+    if per_elem:
+        w.sub_(g["lr"] * d)
+    else:
+        w.add_(d, alpha=-g["lr"])
     if sp.shadow is not None:
         sp.shadow.data[start:end].copy_(w)
 
@@ -391,8 +544,6 @@ class Adam(FusedOptimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None):
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
                                       max_grad_norm=max_grad_norm))
-        if len(self.param_groups) > 1:
-            raise ValueError("fused Adam supports a single param group")
 
     def step_tensor(self, device):
         t = self._step_dev.get(device)
@@ -417,12 +568,18 @@ class Adam(FusedOptimizer):
             st = self._step_dev_inc(sp.device)
             bufs = self._bufs(sp, ["exp_avg", "exp_avg_sq"])
             clip = self._clip_dev(sp, loose) if self.clips else None
-            K.adam_(sp.master, sp.grad, bufs["exp_avg"], bufs["exp_avg_sq"], sp.shadow, g["lr"], 0.0, b1, b2,
-                    g["eps"], g["weight_decay"], self.decoupled, self._grad_scale,
-                    lr_dev=self.lr_tensor(sp.device), step_dev=st, clip_dev=clip)
+            if self.grouped:
+                gid, hp = self.group_tables(sp)
+                K.adam_groups_(sp.master, sp.grad, bufs["exp_avg"], bufs["exp_avg_sq"], sp.shadow, gid, hp, 0.0, 0,
+                               b1, b2, g["eps"], self.decoupled, self._grad_scale, step_dev=st, clip_dev=clip)
+            else:
+                K.adam_(sp.master, sp.grad, bufs["exp_avg"], bufs["exp_avg_sq"], sp.shadow, g["lr"], 0.0, b1, b2,
+                        g["eps"], g["weight_decay"], self.decoupled, self._grad_scale,
+                        lr_dev=self.lr_tensor(sp.device), step_dev=st, clip_dev=clip)
         if loose:
             coef = self._clip_loose(loose) if self.clips else 1.0
-            _torch_adam(loose, g, self.state, self._grad_scale * coef, self.decoupled)
+            for gr, ps in self._members(loose):
+                _torch_adam(ps, gr, self.state, self._grad_scale * coef, self.decoupled)
         return loss
 
     def supports_ranges(self) -> bool:
@@ -456,6 +613,8 @@ class Adam(FusedOptimizer):
         g = self.param_groups[0]
         b1, b2 = g["betas"]
         self._no_ranges_when_clipping()
+        if self.grouped:
+            self._check_granules(start, end)
         spaces, loose = self._flat_groups()
         if len(spaces) != 1 or loose:
             raise ValueError("step_range needs all parameters in one flat space")
@@ -468,7 +627,14 @@ class Adam(FusedOptimizer):
             st = self.step_tensor(sp.device)
         sp.finish_grads_range(start, end)
         bufs = self._bufs(sp, ["exp_avg", "exp_avg_sq"])
-        if end > start:
+        if self.grouped:
+            if end > start:
+                gid, hp = self.group_tables(sp)
+                K.adam_groups_(sp.master[start:end], sp.grad[start:end], bufs["exp_avg"][start:end],
+                               bufs["exp_avg_sq"][start:end], None if sp.shadow is None else sp.shadow[start:end],
+                               gid, hp, 0.0, start, b1, b2, g["eps"], self.decoupled, self._grad_scale, step_dev=st,
+                               max_blocks=max_blocks or (0 if advance_step else _RANGE_BLOCKS))
+        elif end > start:
             K.adam_(sp.master[start:end], sp.grad[start:end], bufs["exp_avg"][start:end],
                     bufs["exp_avg_sq"][start:end], None if sp.shadow is None else sp.shadow[start:end], g["lr"], 0.0,
                     b1, b2, g["eps"], g["weight_decay"], self.decoupled, self._grad_scale,
@@ -516,27 +682,42 @@ def _torch_adam(params, g, state, grad_scale, decoupled):
 
 
 def from_torch(opt: torch.optim.Optimizer) -> FusedOptimizer:
-    """Fused equivalent of a stock torch optimizer (same params and hyper-parameters)."""
+    """Fused equivalent of a stock torch optimizer: the same parameter groups with the same
+    hyper-parameters.  Groups may differ in lr and weight_decay; a difference in anything else
+    (betas, eps, momentum, ...) has no fused form and raises ValueError (never dropped silently)."""
     if isinstance(opt, FusedOptimizer):
         return opt
-    params = [p for g in opt.param_groups for p in g["params"]]
-    g = opt.param_groups[0]
     if isinstance(opt, torch.optim.AdamW):
-        return AdamW(params, lr=g["lr"], betas=g["betas"], eps=g["eps"], weight_decay=g["weight_decay"])
-    if isinstance(opt, torch.optim.Adam):
-        return Adam(params, lr=g["lr"], betas=g["betas"], eps=g["eps"], weight_decay=g["weight_decay"])
-    if isinstance(opt, torch.optim.SGD):
-        return SGD(params, lr=g["lr"], momentum=g["momentum"], dampening=g["dampening"],
-                   weight_decay=g["weight_decay"], nesterov=g["nesterov"])
-    raise TypeError(f"no fused equivalent for {type(opt).__name__}")
+        cls, keys = AdamW, ("lr", "betas", "eps", "weight_decay")
+    elif isinstance(opt, torch.optim.Adam):
+        cls, keys = Adam, ("lr", "betas", "eps", "weight_decay")
+    elif isinstance(opt, torch.optim.SGD):
+        cls, keys = SGD, ("lr", "momentum", "dampening", "weight_decay", "nesterov")
+    else:
+        raise TypeError(f"no fused equivalent for {type(opt).__name__}")
+    groups = [dict({k: g[k] for k in keys}, params=list(g["params"])) for g in opt.param_groups]
+    return cls(groups, **{k: opt.param_groups[0][k] for k in keys})
 
 
 def with_max_grad_norm(opt: FusedOptimizer, max_grad_norm) -> FusedOptimizer:
-    """A fresh fused optimizer of the same class, parameters and hyper-parameters as ``opt`` that
-    clips the global gradient norm at ``max_grad_norm`` (None: does not clip)."""
-    g = opt.param_groups[0]
-    kw = {k: g[k] for k in opt.defaults}
-    kw["max_grad_norm"] = None if max_grad_norm is None else float(max_grad_norm)
-    new = type(opt)([p for gr in opt.param_groups for p in gr["params"]], **kw)
+    """A fresh fused optimizer of the same class, parameter groups and hyper-parameters as ``opt``
+    that clips the global gradient norm at ``max_grad_norm`` (None: does not clip)."""
+    mgn = None if max_grad_norm is None else float(max_grad_norm)
+    groups = [dict({k: g[k] for k in opt.defaults}, params=list(g["params"]), max_grad_norm=mgn)
+              for g in opt.param_groups]
+    kw = {k: opt.param_groups[0][k] for k in opt.defaults}
+    kw["max_grad_norm"] = mgn
+    new = type(opt)(groups, **kw)
     new.set_grad_scale(opt._grad_scale)
     return new
+
+
+def no_decay_groups(module: torch.nn.Module, weight_decay: float):
+    """The usual two parameter groups of ``module`` for an optimizer's first argument: weights
+    (``ndim > 1``) at ``weight_decay``, then biases and BN / LayerNorm weights (``ndim <= 1``) at 0."""
+    decay, no_decay = [], []
+    for p in module.parameters():
+        if p.requires_grad:
+            (no_decay if p.ndim <= 1 else decay).append(p)
+    groups = [{"params": decay, "weight_decay": float(weight_decay)}, {"params": no_decay, "weight_decay": 0.0}]
+    return [g for g in groups if g["params"]]

@@ -358,6 +358,15 @@ def _handle_of(ptr: int) -> bytes:
     return bytes(h)
 
 
+def _one_group(optimizer):
+    """The in-collective fused SGD (and its rider slices) bakes one scalar lr / weight decay into
+    the launch: an optimizer with several parameter groups must come through ``step_range`` on the
+    reduced chunk instead (engine/dp.py routes it there)."""
+    if len(optimizer.param_groups) > 1:
+        raise ValueError("the update fused into the shard collective takes one parameter group; a grouped "
+                         "optimizer updates its chunk with step_range after reduce_scatter(None)")
+
+
 class PeerShard:
     """ZeRO-1 data-parallel update of one flat parameter space over a one-node group.
 
@@ -468,6 +477,7 @@ class PeerShard:
         wd = momentum = dampening = 0.0
         nesterov = 0
         if fused:
+            _one_group(optimizer)
             g = optimizer.param_groups[0]
             wd, momentum, dampening, nesterov = g["weight_decay"], g["momentum"], g["dampening"], int(g["nesterov"])
             lr = optimizer.lr_tensor(sp.device)
@@ -571,6 +581,7 @@ class PeerShard:
                 raise ValueError("rider RS: the own chunk must hold whole fp32x4 vectors")
             a, b, nv = lo - s0, hi - s0, (hi - lo) // 4
             data = arr(*[int(v) + 4 * s0 for v in self._grads])
+            _one_group(optimizer)
             g = optimizer.param_groups[0]
             lr = optimizer.lr_tensor(sp.device)
             mom = first = None

@@ -173,11 +173,11 @@ class KubeModel(ABC):
             opt = with_max_grad_norm(opt, self._step_max_norm)
         old = self.optimizer
         if old is not None and opt is not None and _same_but_lr(old, opt):
-            lr = opt.param_groups[0]["lr"]
+            lrs = [g["lr"] for g in opt.param_groups]      # one LR per group
             if hasattr(old, "set_lr"):
-                old.set_lr(lr)
+                old.set_lr(lrs if len(lrs) > 1 else lrs[0])
             else:
-                for g in old.param_groups:
+                for g, lr in zip(old.param_groups, lrs):
                     g["lr"] = lr
             opt = old
         elif old is not None and opt is not old:

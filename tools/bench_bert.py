@@ -39,6 +39,9 @@ def main():
     ap.add_argument("--force-comm", action="store_true", help="RCCL path even with one rank (rehearsal)")
     ap.add_argument("--max-grad-norm", type=float, default=None, metavar="F",
                     help="clip the global gradient norm at F inside the step (one norm launch + the fused AdamW)")
+    ap.add_argument("--no-decay-groups", action="store_true",
+                    help="the BERT recipe's two parameter groups (optim.no_decay_groups): biases and LayerNorm "
+                         "weights out of the weight decay; the step is then the grouped AdamW launch")
     a = ap.parse_args()
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         import torch
@@ -78,7 +81,11 @@ def main():
     if comm:
         ModelAverager(m).broadcast_(from_env(), 0)
     m.train()
-    opt = AdamW(m.parameters(), lr=1e-4, weight_decay=0.01, max_grad_norm=a.max_grad_norm)
+    params = m.parameters()
+    if a.no_decay_groups:
+        from kubeml_amd.optim import no_decay_groups
+        params = no_decay_groups(m, 0.01)
+    opt = AdamW(params, lr=1e-4, weight_decay=0.01, max_grad_norm=a.max_grad_norm)
     opt.set_grad_scale(1.0 / world)
     B, L, P, V = a.batch, a.seq, a.preds, 30522
     g = torch.Generator(device=dev).manual_seed(1 + rank)
@@ -136,6 +143,9 @@ def main():
                "data": "synthetic tokens, random init", "graph": not a.no_graph, "overlap_segments": len(segs),
                "loss_first_last": [round(first, 4), round(float(loss.detach()), 4)],
                "gemm": "gemm.hip (wgrad, FFN2 dgrad + GELU backward) / hipBLASLt (plain fwd, dgrad: gemm_tuning.json)"}
+        if a.no_decay_groups:
+            out["param_groups"] = [{"weight_decay": g["weight_decay"], "params": len(g["params"])}
+                                   for g in opt.param_groups]
         if a.max_grad_norm is not None:
             out["max_grad_norm"] = a.max_grad_norm
             out["last_grad_norm"] = round(float(opt.grad_norm_tensor(dev)), 4)
