@@ -1836,6 +1836,161 @@ def scale_by_coef_(g, out):
     HIP.call("kml_scale_by_coef", "p p l s", _p(g), _p(out) + 8, g.numel(), _s())
 
 
+# ---- layer-wise adaptive optimizers (LAMB / LARS, csrc/kernels/layerwise.hip) ----------------
+
+LAYER_CHUNK = 8192       # KML_LAYER_CHUNK: elements of one chunk of the segmented reduction, at most
+
+
+def layer_chunks(space_offsets, numel):
+    """The chunk table of a flat space for the layer-wise launches, in plain Python.
+
+    ``space_offsets`` is ``FlatParamSpace.offsets``: one ``(offset, elements)`` per tensor, regions
+    64-aligned and packed in order; ``numel`` the space's (padded) size.  Returns ``(chunks, ranges)``:
+    ``chunks`` rows ``(start, length, tensor)`` cutting every tensor's padded region into pieces of
+    at most ``LAYER_CHUNK`` elements, each a multiple of 64 and inside one tensor, a tensor's chunks
+    consecutive; ``ranges`` one ``(first chunk, chunks)`` per tensor."""
+    numel = int(numel)
+    if numel % GROUP_GRANULE or numel >= 2 ** 31:
+        raise ValueError(f"layer_chunks: a flat space of {numel} elements (whole 64-element granules, "
+                         f"fewer than 2^31)")
+    chunks, ranges = [], []
+    end = 0
+    for t, (o, n) in enumerate(space_offsets):
+        o, n = int(o), int(n)
+        padded = -(-n // GROUP_GRANULE) * GROUP_GRANULE
+        if o % GROUP_GRANULE or n < 0 or o < end or o + padded > numel:
+            raise ValueError(f"layer_chunks: tensor {t} at ({o}, {n}) is not a 64-aligned region in order "
+                             f"inside {numel} elements")
+        first = len(chunks)
+        for s in range(o, o + padded, LAYER_CHUNK):
+            chunks.append((s, min(LAYER_CHUNK, o + padded - s), t))
+        ranges.append((first, len(chunks) - first))
+        end = o + padded
+    return chunks, ranges
+
+
+def layer_tables(space_offsets, numel, device):
+    """:func:`layer_chunks` as the int32 device tensors the launches read: ``(chunks [C, 3],
+    ranges [T, 2])``."""
+    chunks, ranges = layer_chunks(space_offsets, numel)
+    if not chunks:
+        raise ValueError("layer_tables: the flat space holds no parameter element")
+    return (torch.tensor(chunks, dtype=torch.int32).to(device), torch.tensor(ranges, dtype=torch.int32).to(device))
+
+
+def _chk_layer(name, w, bufs, chunks, ranges, hp, part, ratio):
+    """Argument checks of a layer-wise launch, every one a ValueError (nothing reaches the kernel
+    otherwise); returns (C, T).  ranges / part None: the launch does not read them."""
+    def dense(t, dt, what):
+        if not isinstance(t, torch.Tensor) or t.dtype != dt or not t.is_cuda or not t.is_contiguous() \
+                or t.device != w.device:
+            raise ValueError(f"{name}: {what} must be a contiguous {dt} tensor on the parameters' device")
+    if not isinstance(w, torch.Tensor) or not w.is_cuda:
+        raise ValueError(f"{name}: w must be a GPU tensor")
+    n = w.numel()
+    if n % GROUP_GRANULE or n >= 2 ** 31:
+        raise ValueError(f"{name}: {n} elements are not whole {GROUP_GRANULE}-element granules below 2^31")
+    for nm, t, dt in bufs:
+        if t is None:
+            continue
+        dense(t, dt, nm)
+        if t.numel() != n:
+            raise ValueError(f"{name}: {nm} must match w ({n} elements)")
+        if t.data_ptr() % 16:
+            raise ValueError(f"{name}: {nm} must be 16-byte aligned")
+    dense(chunks, torch.int32, "chunks")
+    if chunks.dim() != 2 or chunks.shape[1] != 3 or chunks.shape[0] < 1:
+        raise ValueError(f"{name}: chunks must be an int32 [C, 3] table of (start, length, tensor)")
+    C = int(chunks.shape[0])
+    dense(hp, F32, "hp")
+    if hp.dim() != 2 or hp.shape[1] != 4 or hp.shape[0] < 1:
+        raise ValueError(f"{name}: hp must be an fp32 [T, 4] table of (lr, weight_decay, adapt, unused)")
+    if hp.data_ptr() % 16:
+        raise ValueError(f"{name}: hp must be 16-byte aligned")
+    T = int(hp.shape[0])
+    dense(ratio, F32, "ratio")
+    if ratio.dim() != 1 or ratio.shape[0] != T:
+        raise ValueError(f"{name}: ratio must be an fp32 [{T}] tensor (one trust ratio per row of hp)")
+    if ranges is not None:
+        dense(ranges, torch.int32, "ranges")
+        if ranges.dim() != 2 or tuple(ranges.shape) != (T, 2):
+            raise ValueError(f"{name}: ranges must be an int32 [{T}, 2] table of (first chunk, chunks)")
+    if part is not None:
+        dense(part, F32, "part")
+        if part.numel() < 2 * C or part.data_ptr() % 8:
+            raise ValueError(f"{name}: part must hold {2 * C} floats (two partial sums per chunk), 8-byte aligned")
+    return C, T
+
+
+def _chk_scalar(name, what, t, w):
+    if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != F32 or t.numel() < 1 or t.device != w.device):
+        raise ValueError(f"{name}: {what} must be an fp32 scalar on the parameters' device")
+
+
+def lamb_moments_(w, g, m, v, chunks, ranges, hp, part, ratio, step, b1=0.9, b2=0.999, eps=1e-6, grad_scale=1.0,
+                  step_dev=None, clip_dev=None, max_blocks=0):
+    """LAMB, launch 1 of 2: the moments ``m`` / ``v`` advance in place and ``ratio[t]`` receives tensor
+    t's trust ratio ``|w_t| / |u_t|`` (1 where ``hp[t, 2]`` (adapt) is 0 or a norm is 0; NaN norms give
+    NaN).  ``chunks`` / ``ranges`` from :func:`layer_tables`; ``hp`` fp32 [T, 4] rows of (lr,
+    weight_decay, adapt, unused); ``part`` fp32 scratch of 2 floats per chunk.  ``step`` (``step_dev``
+    when given) is this step's count t >= 1.  Deterministic: ordered partial sums, no float atomics,
+    the same bits for every ``max_blocks``."""
+    C, T = _chk_layer("lamb_moments_", w, (("w", w, F32), ("g", g, F32), ("m", m, F32), ("v", v, F32)), chunks,
+                      ranges, hp, part, ratio)
+    if g is None or m is None or v is None or ranges is None or part is None:
+        raise ValueError("lamb_moments_: g, m, v, ranges and part are required")
+    _chk_scalar("lamb_moments_", "step_dev", step_dev, w)
+    _chk_scalar("lamb_moments_", "clip_dev", clip_dev, w)
+    cnt = _COUNTERS.take(w.device, 1)
+    HIP.call("kml_lamb_moments", "p p p p p i p i p p f d d f f p p p p l i s", _p(w), _p(g), _p(m), _p(v),
+             _p(chunks), C, _p(ranges), T, _p(hp), _p(step_dev), float(step), float(b1), float(b2), float(eps),
+             float(grad_scale), _p(clip_dev), _p(part), _p(cnt), _p(ratio), w.numel(), int(max_blocks), _s())
+
+
+def lamb_apply_(w, m, v, shadow, chunks, hp, ratio, step, b1=0.9, b2=0.999, eps=1e-6, step_dev=None, max_blocks=0):
+    """LAMB, launch 2 of 2: ``w -= lr_t * ratio[t] * u`` with u recomputed from the moments
+    :func:`lamb_moments_` stored (same step count and betas), and the bf16 ``shadow`` refreshed."""
+    C, T = _chk_layer("lamb_apply_", w, (("w", w, F32), ("m", m, F32), ("v", v, F32), ("shadow", shadow, BF16)),
+                      chunks, None, hp, None, ratio)
+    if m is None or v is None:
+        raise ValueError("lamb_apply_: the moment buffers m and v are required")
+    _chk_scalar("lamb_apply_", "step_dev", step_dev, w)
+    HIP.call("kml_lamb_apply", "p p p p p i i p p p f d d f l i s", _p(w), _p(m), _p(v), _p(shadow), _p(chunks), C, T,
+             _p(hp), _p(ratio), _p(step_dev), float(step), float(b1), float(b2), float(eps), w.numel(),
+             int(max_blocks), _s())
+
+
+def lars_norms_(w, g, chunks, ranges, hp, part, ratio, trust_coefficient=1e-3, eps=1e-8, grad_scale=1.0,
+                clip_dev=None, max_blocks=0):
+    """LARS, launch 1 of 2: ``ratio[t] = trust_coefficient * |w_t| / (|g'_t| + wd_t * |w_t| + eps)``
+    with ``g' = grad_scale * clip * g`` (1 where adapt is 0 or a norm is 0; NaN norms give NaN).
+    Tables as :func:`lamb_moments_`; deterministic in the same way."""
+    C, T = _chk_layer("lars_norms_", w, (("w", w, F32), ("g", g, F32)), chunks, ranges, hp, part, ratio)
+    if g is None or ranges is None or part is None:
+        raise ValueError("lars_norms_: g, ranges and part are required")
+    _chk_scalar("lars_norms_", "clip_dev", clip_dev, w)
+    cnt = _COUNTERS.take(w.device, 1)
+    HIP.call("kml_lars_norms", "p p p i p i p f f f p p p p l i s", _p(w), _p(g), _p(chunks), C, _p(ranges), T, _p(hp),
+             float(trust_coefficient), float(eps), float(grad_scale), _p(clip_dev), _p(part), _p(cnt), _p(ratio),
+             w.numel(), int(max_blocks), _s())
+
+
+def lars_apply_(w, g, mom, shadow, chunks, hp, ratio, momentum=0.9, dampening=0.0, nesterov=False, first=False,
+                grad_scale=1.0, first_dev=None, clip_dev=None, max_blocks=0):
+    """LARS, launch 2 of 2: momentum SGD (torch's recurrence, as :func:`sgd_`) on
+    ``d = ratio[t] * (g' + wd_t * w)`` with tensor t's lr, and the bf16 ``shadow`` refreshed.  ``mom``
+    may be None when ``momentum`` is 0; ``first`` / ``first_dev`` as :func:`sgd_`."""
+    C, T = _chk_layer("lars_apply_", w, (("w", w, F32), ("g", g, F32), ("mom", mom, F32), ("shadow", shadow, BF16)),
+                      chunks, None, hp, None, ratio)
+    if g is None or (mom is None and float(momentum) != 0.0):
+        raise ValueError("lars_apply_: g is required, and the momentum buffer when momentum != 0")
+    _chk_scalar("lars_apply_", "first_dev", first_dev, w)
+    _chk_scalar("lars_apply_", "clip_dev", clip_dev, w)
+    HIP.call("kml_lars_apply", "p p p p p i i p p f f i p i f p l i s", _p(w), _p(g), _p(mom), _p(shadow), _p(chunks),
+             C, T, _p(hp), _p(ratio), float(momentum), float(dampening), int(nesterov), _p(first_dev), int(first),
+             float(grad_scale), _p(clip_dev), w.numel(), int(max_blocks), _s())
+
+
 def kavg_pack_(state, i64, i64_off, n_i64, count_idx, participate):
     """K-AVG round prologue on the flat state buffer (see optim.hip): int64 buffers into
     their fp32 slots, participation flag into the count slot."""

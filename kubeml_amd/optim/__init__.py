@@ -35,6 +35,10 @@ groups' (lr, weight_decay), so a captured step follows ``set_lr([...])`` as it f
 LR scalar.  A single-group optimizer launches exactly what it always did.
 :func:`no_decay_groups` builds the usual two groups of a module.
 
+``LAMB`` / ``LARS`` (:mod:`kubeml_amd.optim.layerwise`) are the layer-wise adaptive optimizers of the
+large-batch recipes: two launches per step (per-tensor norms, then the update), a table row per
+tensor instead of the granule bytes, everything else as above.
+
 ``from_torch(opt)`` converts a user's ``torch.optim.SGD/Adam/AdamW`` (what
 ``KubeModel.configure_optimizers`` returns in reference code) into the fused one
 with identical hyper-parameters, group by group.
@@ -45,7 +49,8 @@ from typing import Dict, List
 
 import torch
 
-__all__ = ["SGD", "Adam", "AdamW", "from_torch", "with_max_grad_norm", "no_decay_groups", "FusedOptimizer"]
+__all__ = ["SGD", "Adam", "AdamW", "LAMB", "LARS", "from_torch", "with_max_grad_norm", "no_decay_groups",
+           "layerwise_groups", "FusedOptimizer"]
 
 MAX_GROUPS = 8            # rows of the kernels' hyper-parameter table (KML_MAX_GROUPS)
 _PER_GROUP = ("lr", "weight_decay")     # what may differ between parameter groups
@@ -66,6 +71,8 @@ def _spaces(params):
 
 class FusedOptimizer(torch.optim.Optimizer):
     kind = "base"
+    _per_group = _PER_GROUP      # the keys that may differ between this class's parameter groups
+    _max_groups = MAX_GROUPS     # None: no limit (a table row per tensor, not per group)
 
     def __init__(self, params, defaults):
         super().__init__(params, defaults)
@@ -97,17 +104,17 @@ class FusedOptimizer(torch.optim.Optimizer):
         """Groups may differ in lr and weight_decay only, there are at most MAX_GROUPS of them,
         and on a GPU all their parameters share one flat space (the one launch's range)."""
         groups = self.param_groups
-        if len(groups) > MAX_GROUPS:
+        if self._max_groups is not None and len(groups) > self._max_groups:
             raise ValueError(f"{len(groups)} parameter groups: the fused optimizers take at most {MAX_GROUPS}")
         for key in self.defaults:
-            if key in _PER_GROUP:
+            if key in self._per_group:
                 continue
             for g in groups[1:]:
                 a, b = groups[0][key], g[key]
                 if (tuple(a) != tuple(b)) if isinstance(a, (tuple, list)) else (a != b):
-                    raise ValueError(f"parameter groups differ in {key!r}: only lr and weight_decay may differ "
-                                     f"between the groups of a fused optimizer")
-        if self.grouped:
+                    raise ValueError(f"parameter groups differ in {key!r}: only {' and '.join(self._per_group)} "
+                                     f"may differ between the groups of a fused optimizer")
+        if self.grouped and self._max_groups is not None:
             spaces, loose = self._flat_groups()
             if any(p.is_cuda for g in groups for p in g["params"]) and (len(spaces) != 1 or loose):
                 raise ValueError("a GPU optimizer with several parameter groups needs every parameter in one "
@@ -721,3 +728,6 @@ def no_decay_groups(module: torch.nn.Module, weight_decay: float):
             (no_decay if p.ndim <= 1 else decay).append(p)
     groups = [{"params": decay, "weight_decay": float(weight_decay)}, {"params": no_decay, "weight_decay": 0.0}]
     return [g for g in groups if g["params"]]
+
+
+from .layerwise import LAMB, LARS, layerwise_groups  # noqa: E402  (needs FusedOptimizer above)
