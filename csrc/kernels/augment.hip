@@ -9,6 +9,9 @@
 // Randomness is a counter-based hash of (seed, step, sample) where seed/step are read
 // from device memory, so a hipGraph replay draws fresh crops every step.
 // Reference transform chain: function_resnet34.py:17-30 (train) / :27-30 (val).
+// kml_augment_mix is the same launch with mixup / CutMix: a per-step mix plan drawn from the
+// same counters, a second gather (mixup) or a choice of sample (CutMix) per pixel, and packed
+// (label, partner label, lam) targets for the soft cross-entropy (loss.hip).
 #include "kml_common.h"
 
 namespace {
@@ -30,6 +33,41 @@ struct AugArgs {
   float mean[4], inv_std[4];
 };
 
+// normalised channels v[0 .. C) of source sample sidx at output pixel (x, y), under that
+// sample's own crop / flip draw
+__device__ __forceinline__ void sample_pixel(const AugArgs& a, unsigned seed, unsigned step, long long sidx, int x,
+                                             int y, float* v) {
+  int dx = 0, dy = 0, fl = 0;
+  if (a.train) {
+    const unsigned h = hash3(seed, step, (unsigned)sidx);
+    const int span = 2 * a.pad + 1;
+    dy = (int)(h % span) - a.pad;
+    dx = (int)((h / span) % span) - a.pad;
+    fl = a.flip ? (int)((h >> 24) & 1) : 0;
+  }
+  int sx = fl ? (a.W - 1 - x) : x;
+  sx += dx;
+  const int sy = y + dy;
+  if ((unsigned)sx < (unsigned)a.W && (unsigned)sy < (unsigned)a.H) {
+    const unsigned char* p = a.src + ((sidx * a.H + sy) * a.W + sx) * a.C;
+    for (int c = 0; c < a.C && c < 4; ++c) v[c] = ((float)p[c] * (1.f / 255.f) - a.mean[c]) * a.inv_std[c];
+  } else {
+    // zero padding happens BEFORE normalisation in the reference chain (pad on the uint8 image)
+    for (int c = 0; c < a.C && c < 4; ++c) v[c] = (0.f - a.mean[c]) * a.inv_std[c];
+  }
+}
+
+// v[0 .. 8) -> the pixel's CP channels (pad channels 0): one 16-byte store when CP == 8
+__device__ __forceinline__ void store_pixel(bf16_t* o, int CP, const float* v) {
+  if (CP == 8) {
+    uint4 q;
+    q.x = pack_bf2(v[0], v[1]); q.y = pack_bf2(v[2], v[3]); q.z = pack_bf2(v[4], v[5]); q.w = pack_bf2(v[6], v[7]);
+    *reinterpret_cast<uint4*>(o) = q;
+  } else {
+    for (int c = 0; c < CP; ++c) o[c] = f2bf(c < 8 ? v[c] : 0.f);
+  }
+}
+
 // one thread per output pixel (all CP channels -> one 16-byte store when CP == 8)
 __global__ void k_augment(AugArgs a) {
   const long long total = (long long)a.B * a.H * a.W;
@@ -41,43 +79,166 @@ __global__ void k_augment(AugArgs a) {
     const int y = (int)((t / a.W) % a.H);
     const int b = (int)(t / ((long long)a.W * a.H));
     const long long sidx = (start + b) % a.N;
-    int dx = 0, dy = 0, fl = 0;
-    if (a.train) {
-      const unsigned h = hash3(seed, step, (unsigned)sidx);
-      const int span = 2 * a.pad + 1;
-      dy = (int)(h % span) - a.pad;
-      dx = (int)((h / span) % span) - a.pad;
-      fl = a.flip ? (int)((h >> 24) & 1) : 0;
-    }
-    int sx = fl ? (a.W - 1 - x) : x;
-    sx += dx;
-    const int sy = y + dy;
     float v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if ((unsigned)sx < (unsigned)a.W && (unsigned)sy < (unsigned)a.H) {
-      const unsigned char* p = a.src + ((sidx * a.H + sy) * a.W + sx) * a.C;
-      for (int c = 0; c < a.C && c < 4; ++c) v[c] = ((float)p[c] * (1.f / 255.f) - a.mean[c]) * a.inv_std[c];
-    } else {
-      // zero padding happens BEFORE normalisation in the reference chain (pad on the uint8 image)
-      for (int c = 0; c < a.C && c < 4; ++c) v[c] = (0.f - a.mean[c]) * a.inv_std[c];
-    }
-    bf16_t* o = a.dst + t * a.CP;
-    if (a.CP == 8) {
-      uint4 q;
-      q.x = pack_bf2(v[0], v[1]); q.y = pack_bf2(v[2], v[3]); q.z = pack_bf2(v[4], v[5]); q.w = pack_bf2(v[6], v[7]);
-      *reinterpret_cast<uint4*>(o) = q;
-    } else {
-      for (int c = 0; c < a.CP; ++c) o[c] = f2bf(c < 8 ? v[c] : 0.f);
-    }
+    sample_pixel(a, seed, step, sidx, x, y, v);
+    store_pixel(a.dst + t * a.CP, a.CP, v);
     if (x == 0 && y == 0 && a.labels_dst) a.labels_dst[b] = a.labels_src[sidx];
   }
 }
 
+// ---- mixup / CutMix ------------------------------------------------------------------------
+// One mix plan per step, a function of (seed, step) alone, so every block of the augment launch
+// (and kml_mix_plan) derives the same one and a graph replay draws a new one.  Its draws are
+// hash3(seed ^ MIX_SALT, step, k): the salted seed keeps them apart from the per-sample
+// crop / flip draws hash3(seed, step, sample).
+enum { MIX_NONE = 0, MIX_MIXUP = 1, MIX_CUTMIX = 2 };
+struct MixCfg { float mixup_alpha, cutmix_alpha, mix_prob, switch_prob; };
+struct MixPlan {
+  int mode, r;          // r: sample b is mixed with batch row (b + r) % B
+  float lam;            // weight of the sample's own label
+  int x0, y0, x1, y1;   // CutMix box [x0, x1) x [y0, y1), clipped to the image
+  int applied;
+};
+
+constexpr unsigned MIX_SALT = 0x4D495853u;
+constexpr int MIX_GAMMA_TRIES = 16;
+// draw indices: fixed ones, then one block of 3 * MIX_GAMMA_TRIES + 1 per gamma variate
+enum { MIX_K_APPLY = 0, MIX_K_SWITCH = 1, MIX_K_SHIFT = 2, MIX_K_CX = 3, MIX_K_CY = 4, MIX_K_GAMMA = 8 };
+
+__device__ __forceinline__ unsigned mix_bits(unsigned seed, unsigned step, unsigned k) {
+  return hash3(seed ^ MIX_SALT, step, k);
+}
+// uniform in the open interval (0, 1): 23 bits, exact in fp32
+__device__ __forceinline__ float mix_u01(unsigned seed, unsigned step, unsigned k) {
+  return ((float)(mix_bits(seed, step, k) >> 9) + 0.5f) * (1.f / 8388608.f);
+}
+
+// log of a Gamma(a, 1) variate, a > 0: Marsaglia-Tsang rejection for a >= 1, and
+// G(a) = G(a + 1) * U^(1/a) below 1 (taken in the log domain: U^(1/a) underflows fp32 for small
+// a).  One try accepts with probability > 0.95; after MIX_GAMMA_TRIES rejections (< 1e-20) the
+// variate is d = a - 1/3, the centre of the proposal, so the loop is bounded.
+__device__ float mix_log_gamma(unsigned seed, unsigned step, unsigned k0, float a) {
+  const float a1 = a < 1.f ? a + 1.f : a;
+  const float d = a1 - (1.f / 3.f), c = rsqrtf(9.f * d);
+  float g = d;
+  for (int i = 0; i < MIX_GAMMA_TRIES; ++i) {
+    const float u1 = mix_u01(seed, step, k0 + 3 * i), u2 = mix_u01(seed, step, k0 + 3 * i + 1);
+    const float u3 = mix_u01(seed, step, k0 + 3 * i + 2);
+    const float n = sqrtf(-2.f * __logf(u1)) * __builtin_amdgcn_cosf(u2);   // Box-Muller; v_cos takes revolutions
+    const float t = 1.f + c * n;
+    if (t <= 0.f) continue;
+    const float v = t * t * t;
+    if (__logf(u3) < 0.5f * n * n + d - d * v + d * __logf(v)) { g = d * v; break; }
+  }
+  float lg = __logf(g);
+  if (a < 1.f) lg += __logf(mix_u01(seed, step, k0 + 3 * MIX_GAMMA_TRIES)) / a;
+  return lg;
+}
+
+__device__ MixPlan mix_plan(unsigned seed, unsigned step, int B, int H, int W, const MixCfg& m) {
+  MixPlan p = {MIX_NONE, 0, 1.f, 0, 0, 0, 0, 0};
+  const bool mu = m.mixup_alpha > 0.f, cm = m.cutmix_alpha > 0.f;
+  if (B < 2 || !(mu || cm)) return p;
+  p.r = 1 + (int)(mix_bits(seed, step, MIX_K_SHIFT) % (unsigned)(B - 1));
+  if (!(mix_u01(seed, step, MIX_K_APPLY) < m.mix_prob)) return p;
+  p.applied = 1;
+  const bool cut = cm && (!mu || mix_u01(seed, step, MIX_K_SWITCH) < m.switch_prob);
+  // lam ~ Beta(alpha, alpha) = Ga / (Ga + Gb) = 1 / (1 + exp(log Gb - log Ga))
+  const float alpha = cut ? m.cutmix_alpha : m.mixup_alpha;
+  const float la = mix_log_gamma(seed, step, MIX_K_GAMMA, alpha);
+  const float lb = mix_log_gamma(seed, step, MIX_K_GAMMA + 3 * MIX_GAMMA_TRIES + 1, alpha);
+  const float lam = 1.f / (1.f + __expf(lb - la));
+  if (!cut) {
+    p.mode = MIX_MIXUP;
+    p.lam = lam;
+    return p;
+  }
+  const float ratio = sqrtf(1.f - lam);
+  const int cw = (int)((float)W * ratio), ch = (int)((float)H * ratio);
+  const int cx = (int)(mix_bits(seed, step, MIX_K_CX) % (unsigned)W);
+  const int cy = (int)(mix_bits(seed, step, MIX_K_CY) % (unsigned)H);
+  p.mode = MIX_CUTMIX;
+  p.x0 = max(cx - cw / 2, 0); p.x1 = min(cx + cw / 2, W);
+  p.y0 = max(cy - ch / 2, 0); p.y1 = min(cy + ch / 2, H);
+  p.lam = 1.f - (float)((p.x1 - p.x0) * (p.y1 - p.y0)) / (float)(H * W);   // from the clipped box
+  return p;
+}
+
+// k_augment with the step's mix plan (one thread computes it, LDS broadcasts it).  mixup: the
+// sample's and the partner's pixel, each under its own crop / flip, blended in fp32 before the
+// one store; CutMix: inside the box the partner's pixel at the same output coordinate.  The
+// thread of pixel (0, 0) writes the packed target (label, partner label, lam).
+__global__ void k_augment_mix(AugArgs a, float* __restrict__ targets, MixCfg m) {
+  const long long total = (long long)a.B * a.H * a.W;
+  const unsigned seed = (unsigned)a.ctr[0], step = (unsigned)a.ctr[1];
+  const long long start = (long long)a.ctr[2];
+  __shared__ MixPlan plan;
+  if (threadIdx.x == 0) plan = mix_plan(seed, step, a.B, a.H, a.W, m);
+  __syncthreads();
+  const MixPlan p = plan;
+  // start % N + batch row < 2^32: the two sample indices take 32-bit divisions
+  const unsigned s0 = (unsigned)(start % a.N);
+  for (long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x; t < total;
+       t += (long long)gridDim.x * blockDim.x) {
+    const int x = (int)(t % a.W);
+    const int y = (int)((t / a.W) % a.H);
+    const int b = (int)(t / ((long long)a.W * a.H));
+    const int pb = b + p.r < a.B ? b + p.r : b + p.r - a.B;   // r < B
+    const long long sidx = (s0 + (unsigned)b) % (unsigned)a.N;
+    const long long pidx = (s0 + (unsigned)pb) % (unsigned)a.N;
+    float v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (p.mode == MIX_CUTMIX) {
+      const bool inside = x >= p.x0 && x < p.x1 && y >= p.y0 && y < p.y1;
+      sample_pixel(a, seed, step, inside ? pidx : sidx, x, y, v);
+    } else {
+      sample_pixel(a, seed, step, sidx, x, y, v);
+      if (p.mode == MIX_MIXUP) {
+        float w[4] = {0, 0, 0, 0};
+        sample_pixel(a, seed, step, pidx, x, y, w);
+        // blend the two pixels as k_augment would store them (bf16): the mixed batch is then the
+        // blend of two plain batches up to its one final rounding
+        const unsigned a2[2] = {pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3])};
+        const unsigned b2[2] = {pack_bf2(w[0], w[1]), pack_bf2(w[2], w[3])};
+        const float om = 1.f - p.lam;
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+          v[2 * c] = fmaf(p.lam, lo_bf(a2[c]), om * lo_bf(b2[c]));
+          v[2 * c + 1] = fmaf(p.lam, hi_bf(a2[c]), om * hi_bf(b2[c]));
+        }
+      }
+    }
+    store_pixel(a.dst + t * a.CP, a.CP, v);
+    if (x == 0 && y == 0) {
+      float* tg = targets + 3 * (long long)b;
+      tg[0] = (float)a.labels_src[sidx];
+      tg[1] = (float)a.labels_src[pidx];
+      tg[2] = p.lam;
+    }
+  }
+}
+
+// plans of steps ctr[1] .. ctr[1] + n - 1 as rows (mode, r, lam, x0, y0, x1, y1, applied)
+__global__ void k_mix_plan(const float* __restrict__ ctr, float* __restrict__ out, int n, int B, int H, int W,
+                           MixCfg m) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const MixPlan p = mix_plan((unsigned)ctr[0], (unsigned)ctr[1] + (unsigned)i, B, H, W, m);
+  float* o = out + 8 * (long long)i;
+  o[0] = (float)p.mode; o[1] = (float)p.r; o[2] = p.lam;
+  o[3] = (float)p.x0; o[4] = (float)p.y0; o[5] = (float)p.x1; o[6] = (float)p.y1;
+  o[7] = (float)p.applied;
+}
+
+static bool mix_cfg_ok(const MixCfg& m) {
+  return m.mixup_alpha >= 0.f && m.cutmix_alpha >= 0.f && m.mixup_alpha < INFINITY && m.cutmix_alpha < INFINITY &&
+         m.mix_prob >= 0.f && m.mix_prob <= 1.f && m.switch_prob >= 0.f && m.switch_prob <= 1.f;
+}
+
 }  // namespace
 
-KML_API int kml_augment(const unsigned char* src, const long long* labels_src, bf16_t* dst, long long* labels_dst,
+static AugArgs aug_args(const unsigned char* src, const long long* labels_src, bf16_t* dst, long long* labels_dst,
                         const float* ctr, int N, int H, int W, int C, int CP, int B, int pad, int flip, int train,
-                        const float* mean, const float* std, hipStream_t s) {
-  if (C > 4 || CP < C) return (int)hipErrorInvalidValue;
+                        const float* mean, const float* std) {
   AugArgs a;
   a.src = src; a.labels_src = labels_src; a.dst = dst; a.labels_dst = labels_dst; a.ctr = ctr;
   a.N = N; a.H = H; a.W = W; a.C = C; a.CP = CP; a.B = B; a.pad = pad; a.flip = flip; a.train = train;
@@ -85,8 +246,43 @@ KML_API int kml_augment(const unsigned char* src, const long long* labels_src, b
     a.mean[i] = i < C ? mean[i] : 0.f;
     a.inv_std[i] = i < C ? 1.f / std[i] : 0.f;
   }
+  return a;
+}
+
+KML_API int kml_augment(const unsigned char* src, const long long* labels_src, bf16_t* dst, long long* labels_dst,
+                        const float* ctr, int N, int H, int W, int C, int CP, int B, int pad, int flip, int train,
+                        const float* mean, const float* std, hipStream_t s) {
+  if (C > 4 || CP < C) return (int)hipErrorInvalidValue;
+  const AugArgs a = aug_args(src, labels_src, dst, labels_dst, ctr, N, H, W, C, CP, B, pad, flip, train, mean, std);
   long long total = (long long)B * H * W;
   hipLaunchKernelGGL(k_augment, dim3(kml_stream_grid(total, 256)), dim3(256), 0, s, a);
+  KML_LAUNCH_CHECK();
+}
+
+// kml_augment with the step's mixup / CutMix plan; targets: fp32 [B, 3] rows (label, partner
+// label, lam) for kml_ce_soft_*.  An alpha of 0 switches that mode off; mix_prob: probability that
+// a step mixes at all; switch_prob: share of CutMix when both alphas are > 0.
+KML_API int kml_augment_mix(const unsigned char* src, const long long* labels_src, bf16_t* dst, float* targets,
+                            const float* ctr, int N, int H, int W, int C, int CP, int B, int pad, int flip, int train,
+                            const float* mean, const float* std, float mixup_alpha, float cutmix_alpha,
+                            float mix_prob, float switch_prob, hipStream_t s) {
+  const MixCfg m = {mixup_alpha, cutmix_alpha, mix_prob, switch_prob};
+  if (C < 1 || C > 4 || CP < C || N < 1 || B < 1 || H < 1 || W < 1 || pad < 0 || !labels_src || !targets ||
+      !mix_cfg_ok(m))
+    return (int)hipErrorInvalidValue;
+  const AugArgs a = aug_args(src, labels_src, dst, nullptr, ctr, N, H, W, C, CP, B, pad, flip, train, mean, std);
+  long long total = (long long)B * H * W;
+  hipLaunchKernelGGL(k_augment_mix, dim3(kml_stream_grid(total, 256)), dim3(256), 0, s, a, targets, m);
+  KML_LAUNCH_CHECK();
+}
+
+// out: fp32 [n, 8] rows (mode, r, lam, x0, y0, x1, y1, applied), the plans kml_augment_mix uses
+// at steps ctr[1] .. ctr[1] + n - 1 for a batch of B images of H x W (tests, debugging)
+KML_API int kml_mix_plan(const float* ctr, float* out, int n, int B, int H, int W, float mixup_alpha,
+                         float cutmix_alpha, float mix_prob, float switch_prob, hipStream_t s) {
+  const MixCfg m = {mixup_alpha, cutmix_alpha, mix_prob, switch_prob};
+  if (n < 1 || B < 1 || H < 1 || W < 1 || !mix_cfg_ok(m)) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_mix_plan, dim3((n + 255) / 256), dim3(256), 0, s, ctr, out, n, B, H, W, m);
   KML_LAUNCH_CHECK();
 }
 

@@ -565,19 +565,90 @@ class _CEFn(Function):
 _CE_BIAS_FUSE = True    # the head's bias gradient comes out of the cross-entropy backward
 
 
-def cross_entropy(logits, labels, ignore_index=-100, return_correct=False, classes=None):
+class _CESoftFn(Function):
+    """_CEFn against a soft target (label smoothing and / or packed mixup / CutMix rows)."""
+
+    @staticmethod
+    def forward(ctx, logits, target, ignore_index, classes, eps, lin=None):
+        from ..ops import kernels as K
+        out3, ws, tgt = K.ce_soft_fwd(logits, target, ignore_index, classes=classes, label_smoothing=eps)
+        ctx.save = (logits, tgt, ws, out3, ignore_index, classes, eps)
+        ctx.out3 = out3
+        ctx.lin = lin
+        return out3[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        from ..ops import kernels as K
+        logits, tgt, ws, out3, ig, classes, eps = ctx.save
+        lin, dbias, acc = ctx.lin, None, True   # the head's bias gradient, as in _CEFn.backward
+        if (lin is not None and getattr(lin, "bias", None) is not None and _CE_BIAS_FUSE
+                and getattr(lin, "_kml_route", None) != "conv"
+                and lin.out_pad == logits.shape[1] and K.ce_bias_fusable(logits)):
+            dbias, acc = grad_out(lin.bias)
+            object.__setattr__(lin, "_kml_bias_done", True)
+        d = K.ce_soft_bwd(logits, tgt, ws, out3, grad_out=g.reshape(1).float().contiguous(), ignore_index=ig,
+                          classes=classes, label_smoothing=eps, dbias=dbias, accumulate=acc)
+        ctx.save = ctx.lin = None
+        return d, None, None, None, None, None
+
+
+def _check_soft(logits, target, classes, eps):
+    from ..ops.kernels import MAX_PACKED_CLASSES
+    if not 0.0 <= eps < 1.0:
+        raise ValueError(f"label_smoothing must be in [0, 1), got {eps}")
+    if target.is_floating_point():
+        if target.dim() != 2 or tuple(target.shape) != (logits.shape[0], 3):
+            raise ValueError(f"a float target must be packed [B, 3] rows of (y, y2, lam), got {tuple(target.shape)}")
+        if (logits.shape[1] if classes is None else classes) > MAX_PACKED_CLASSES:
+            raise ValueError("packed targets store the labels as fp32: classes must be <= 2**24")
+
+
+def _cross_entropy_cpu(logits, target, ignore_index, return_correct, eps):
+    """torch ops with the kernels' semantics: mean over the valid rows."""
+    C = logits.shape[1]
+    if target.is_floating_point():
+        y, y2, lam = target[:, 0], target[:, 1], target[:, 2].float()
+        valid = (y >= 0) & (y < C) & (y2 >= 0) & (y2 < C)
+        yv, y2v, lamv = y[valid].long(), y2[valid].long(), lam[valid].unsqueeze(1)
+        q = lamv * F.one_hot(yv, C).float() + (1.0 - lamv) * F.one_hot(y2v, C).float()
+        rows = logits[valid].float()
+        loss = F.cross_entropy(rows, q, label_smoothing=eps) if rows.shape[0] else logits.sum() * 0.0
+        correct = (rows.argmax(1) == yv).sum().float()
+    else:
+        loss = F.cross_entropy(logits.float(), target, ignore_index=ignore_index, label_smoothing=eps)
+        valid = target != ignore_index
+        correct = (logits.argmax(1) == target)[valid].sum().float()
+    return (loss, correct) if return_correct else loss
+
+
+def cross_entropy(logits, target, ignore_index=-100, return_correct=False, classes=None, label_smoothing=0.0):
     """Mean softmax cross-entropy (fused HIP kernel on GPU).  With return_correct the
     device-side argmax==label count of the same pass is returned as well.  ``classes``:
     the real class count when ``logits`` rows are padded past it (a ``keep_pad`` Linear
-    output; the pad columns are ignored and get a zero gradient)."""
+    output; the pad columns are ignored and get a zero gradient).
+
+    ``target`` is int64 ``[B]`` labels or packed fp32 ``[B, 3]`` rows ``(y, y2, lam)`` — what
+    ``sdk.vision.prepare`` returns under mixup / CutMix.  The row's target distribution is
+    ``(1 - label_smoothing) * (lam * onehot(y) + (1 - lam) * onehot(y2)) + label_smoothing / C``;
+    a packed row with ``y`` or ``y2`` outside ``[0, C)`` is left out like an ignored label, and
+    ``correct`` counts ``argmax == y``.  Integer labels without smoothing take the hard-label
+    kernels."""
+    eps = float(label_smoothing)
+    _check_soft(logits, target, classes, eps)
     if not logits.is_cuda:
         if classes is not None:
             logits = logits[:, :classes]
-        loss = F.cross_entropy(logits.float(), labels, ignore_index=ignore_index)
-        if return_correct:
-            valid = labels != ignore_index
-            return loss, (logits.argmax(1) == labels)[valid].sum().float()
-        return loss
+        return _cross_entropy_cpu(logits, target, ignore_index, return_correct, eps)
+    if eps != 0.0 or target.is_floating_point():
+        lin = getattr(logits, "_kml_linear", None)
+        if torch.is_grad_enabled() and logits.requires_grad:
+            loss = _CESoftFn.apply(logits.contiguous(), target, ignore_index, classes, eps, lin)
+            return (loss, loss.grad_fn.out3[1]) if return_correct else loss
+        from ..ops import kernels as K
+        out3, _, _ = K.ce_soft_fwd(logits.contiguous(), target, ignore_index, classes=classes, label_smoothing=eps)
+        return (out3[0], out3[1]) if return_correct else out3[0]
+    labels = target
     if return_correct:
         from ..ops import kernels as K
         if torch.is_grad_enabled() and logits.requires_grad:
@@ -605,9 +676,16 @@ def backward_loss(loss):
 
 
 class CrossEntropyLoss(tnn.Module):
-    def __init__(self, ignore_index=-100):
-        super().__init__()
-        self.ignore_index = ignore_index
+    """:func:`cross_entropy` as a module.  Create it once (in the function's ``__init__``) and
+    pass the same object to every ``KubeModel.step(x, t, loss_fn=...)``: the identity of the
+    loss function is part of the key of the captured step graph."""
 
-    def forward(self, logits, labels):
-        return cross_entropy(logits, labels, self.ignore_index)
+    def __init__(self, ignore_index=-100, label_smoothing=0.0):
+        super().__init__()
+        if not 0.0 <= label_smoothing < 1.0:
+            raise ValueError(f"label_smoothing must be in [0, 1), got {label_smoothing}")
+        self.ignore_index = ignore_index
+        self.label_smoothing = label_smoothing
+
+    def forward(self, logits, target):
+        return cross_entropy(logits, target, self.ignore_index, label_smoothing=self.label_smoothing)

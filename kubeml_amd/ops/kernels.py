@@ -1619,6 +1619,72 @@ def ce_bwd(logits, labels, ws, out3, grad_out=None, ignore_index=-100, classes=N
     return d
 
 
+MAX_PACKED_CLASSES = 1 << 24   # packed targets store the labels as exact fp32 values
+
+
+def _soft_target(target, B, C, eps):
+    """(labels, packed) — one of them None — for the kml_ce_soft_* entry points."""
+    if not 0.0 <= eps < 1.0:
+        raise ValueError(f"label_smoothing must be in [0, 1), got {eps}")
+    if target.is_floating_point():
+        if target.dim() != 2 or tuple(target.shape) != (B, 3):
+            raise ValueError(f"packed targets must be [B, 3] rows of (y, y2, lam), got {tuple(target.shape)}")
+        if C > MAX_PACKED_CLASSES:
+            raise ValueError(f"packed targets need classes <= 2**24, got {C}")
+        return None, target.to(F32).contiguous()
+    if target.dim() != 1 or target.shape[0] != B:
+        raise ValueError(f"labels must be [B], got {tuple(target.shape)}")
+    return target.to(torch.int64).contiguous(), None
+
+
+def ce_soft_fwd(logits, target, ignore_index=-100, classes=None, label_smoothing=0.0):
+    """:func:`ce_fwd` against the soft target ``(1-eps) * (lam*onehot(y) + (1-lam)*onehot(y2))
+    + eps/C``.  ``target``: int64 ``[B]`` labels (``y2 = y``, ``lam = 1``; ``ignore_index`` as
+    in ce_fwd) or packed fp32 ``[B, 3]`` rows ``(y, y2, lam)`` — a row with ``y`` or ``y2``
+    outside ``[0, C)`` is invalid, like an ignored one.  Returns ``(out3, ws, target)`` with
+    ``out3 = [mean loss, correct (argmax == y), valid]``."""
+    if logits.dim() != 2:
+        raise ValueError("logits must be [B, C]")
+    if not logits.is_contiguous():
+        logits = logits.contiguous()
+    dt = {BF16: 0, F32: 1}[logits.dtype]
+    B, ld = logits.shape
+    C = ld if classes is None else int(classes)
+    if C > ld:
+        raise ValueError("classes exceeds the logits row")
+    eps = float(label_smoothing)
+    labels, packed = _soft_target(target, B, C, eps)
+    ws = torch.empty(3 * B, dtype=F32, device=logits.device)
+    out3 = torch.empty(3, dtype=F32, device=logits.device)
+    ticket = _COUNTERS.take(logits.device, 1)
+    HIP.call("kml_ce_soft_fwd", "p p p p p i i i l f i p s", _p(logits), _p(labels), _p(packed), _p(ws), _p(out3),
+             B, C, ld, int(ignore_index), eps, dt, _p(ticket), _s())
+    return out3, ws, (labels if packed is None else packed)
+
+
+def ce_soft_bwd(logits, target, ws, out3, grad_out=None, ignore_index=-100, classes=None, label_smoothing=0.0,
+                dbias=None, accumulate=True):
+    """dlogits = grad_out / valid * (softmax - q) for the soft target q of :func:`ce_soft_fwd`
+    (pad columns and invalid rows 0); ``dbias`` / ``accumulate`` as in :func:`ce_bwd`."""
+    dt = {BF16: 0, F32: 1}[logits.dtype]
+    B, ld = logits.shape
+    C = ld if classes is None else int(classes)
+    eps = float(label_smoothing)
+    labels, packed = _soft_target(target, B, C, eps)
+    d = torch.empty_like(logits)
+    part = cnt = None
+    if dbias is not None:
+        _chk(dbias, F32, "dbias")
+        if not ce_bias_fusable(logits) or dbias.numel() < C:
+            raise ValueError("ce_soft_bwd: bias fusion needs bf16 logits with ld % 8 == 0, ld <= 4096")
+        part = torch.empty(_cdiv(B, 16) * _cdiv(C, 4) * 4, dtype=F32, device=logits.device)
+        cnt = _COUNTERS.take(logits.device, 1)
+    HIP.call("kml_ce_soft_bwd", "p p p p p p p i i i l f i p p p i s", _p(logits), _p(labels), _p(packed), _p(ws),
+             _p(out3), _p(grad_out), _p(d), B, C, ld, int(ignore_index), eps, dt, _p(dbias), _p(part), _p(cnt),
+             int(bool(accumulate)), _s())
+    return d
+
+
 # --------------------------------------------------------------------------------------
 # optimizers
 # --------------------------------------------------------------------------------------
@@ -2055,6 +2121,62 @@ def augment(src_u8, labels_src, ctr, B, out=None, labels_out=None, CP=8, pad=4, 
              _p(labels_out), _p(ctr), N, H, W, C, CP, B, pad, int(flip), int(train),
              mean_a.data_ptr(), std_a.data_ptr(), _s())
     return out, labels_out
+
+
+MIX_NONE, MIX_MIXUP, MIX_CUTMIX = 0, 1, 2
+
+
+def _chk_mix(mixup_alpha, cutmix_alpha, mix_prob, switch_prob):
+    for name, a in (("mixup_alpha", mixup_alpha), ("cutmix_alpha", cutmix_alpha)):
+        if not (0.0 <= a < math.inf):
+            raise ValueError(f"{name} must be a finite value >= 0, got {a}")
+    for name, p in (("mix_prob", mix_prob), ("switch_prob", switch_prob)):
+        if not 0.0 <= p <= 1.0:
+            raise ValueError(f"{name} must be in [0, 1], got {p}")
+
+
+def augment_mix(src_u8, labels_src, ctr, B, out=None, targets_out=None, CP=8, pad=4, flip=True, train=True,
+                mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), mixup_alpha=0.0, cutmix_alpha=0.0,
+                mix_prob=1.0, switch_prob=0.5):
+    """:func:`augment` with mixup / CutMix inside the same launch.  The step's mix plan (see
+    :func:`mix_plan`) is drawn from the counter ``ctr``; sample ``b`` is mixed with batch row
+    ``(b + r) % B``.  Returns the batch and packed fp32 ``[B, 3]`` targets ``(label, partner
+    label, lam)`` for ``cross_entropy``."""
+    _chk(src_u8, torch.uint8, "src", 4)
+    _chk(labels_src, torch.int64, "labels_src", 1)
+    _chk(ctr, F32, "ctr")
+    _chk_mix(mixup_alpha, cutmix_alpha, mix_prob, switch_prob)
+    N, H, W, C = src_u8.shape
+    if C > 4 or CP < C or B < 1 or labels_src.numel() < N or ctr.numel() < 3:
+        raise ValueError(f"augment_mix: source {tuple(src_u8.shape)}, CP {CP}, B {B}")
+    if out is None:
+        out = torch.empty((B, H, W, CP), dtype=BF16, device=src_u8.device)
+    if targets_out is None:
+        targets_out = torch.empty((B, 3), dtype=F32, device=src_u8.device)
+    _chk(out, BF16, "out")
+    _chk(targets_out, F32, "targets_out")
+    if out.numel() != B * H * W * CP or targets_out.numel() != 3 * B:
+        raise ValueError("augment_mix: out / targets_out do not match the batch")
+    mean_a = (torch.tensor(list(mean) + [0.0] * (4 - len(mean)), dtype=F32))
+    std_a = (torch.tensor(list(std) + [1.0] * (4 - len(std)), dtype=F32))
+    HIP.call("kml_augment_mix", "p p p p p i i i i i i i i i p p f f f f s", _p(src_u8), _p(labels_src), _p(out),
+             _p(targets_out), _p(ctr), N, H, W, C, CP, B, pad, int(flip), int(train), mean_a.data_ptr(),
+             std_a.data_ptr(), float(mixup_alpha), float(cutmix_alpha), float(mix_prob), float(switch_prob), _s())
+    return out, targets_out
+
+
+def mix_plan(ctr, n, B, H, W, mixup_alpha=0.0, cutmix_alpha=0.0, mix_prob=1.0, switch_prob=0.5):
+    """The mix plans :func:`augment_mix` draws at steps ``ctr[1] .. ctr[1] + n - 1`` for a batch
+    of ``B`` images of ``H x W``: fp32 ``[n, 8]`` rows ``(mode, r, lam, x0, y0, x1, y1, applied)``
+    with mode ``MIX_NONE`` / ``MIX_MIXUP`` / ``MIX_CUTMIX`` and the CutMix box ``[x0, x1) x [y0, y1)``."""
+    _chk(ctr, F32, "ctr")
+    _chk_mix(mixup_alpha, cutmix_alpha, mix_prob, switch_prob)
+    if n < 1 or B < 1 or H < 1 or W < 1 or ctr.numel() < 2:
+        raise ValueError(f"mix_plan: n {n}, B {B}, H {H}, W {W}")
+    out = torch.empty((n, 8), dtype=F32, device=ctr.device)
+    HIP.call("kml_mix_plan", "p p i i i i f f f f s", _p(ctr), _p(out), int(n), int(B), int(H), int(W),
+             float(mixup_alpha), float(cutmix_alpha), float(mix_prob), float(switch_prob), _s())
+    return out
 
 
 # --------------------------------------------------------------------------------------

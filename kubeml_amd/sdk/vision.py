@@ -22,13 +22,29 @@ IMAGENET_MEAN, IMAGENET_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
 
 
 class ImageDataset(KubeDataset):
-    """uint8 ``[N, H, W, C]`` images + integer labels; batches are ``(uint8 tensor, int64 labels)``."""
+    """uint8 ``[N, H, W, C]`` images + integer labels; batches are ``(uint8 tensor, int64 labels)``.
+
+    ``mixup_alpha`` / ``cutmix_alpha`` > 0 switch on mixup / CutMix for training batches:
+    :func:`prepare` then mixes every sample with another row of the batch (one ``lam ~
+    Beta(alpha, alpha)`` per step) and returns packed fp32 ``[B, 3]`` targets ``(label, partner
+    label, lam)`` that ``cross_entropy`` / ``CrossEntropyLoss`` accept.  ``mix_prob``: the
+    probability that a step mixes at all; ``switch_prob``: the share of CutMix steps when both
+    alphas are set."""
 
     def __init__(self, dataset: str, mean: Sequence[float] = IMAGENET_MEAN, std: Sequence[float] = IMAGENET_STD,
-                 crop_pad: int = 4, flip: bool = True):
+                 crop_pad: int = 4, flip: bool = True, mixup_alpha: float = 0.0, cutmix_alpha: float = 0.0,
+                 mix_prob: float = 1.0, switch_prob: float = 0.5):
         super().__init__(dataset)
         self.mean, self.std = tuple(mean), tuple(std)
         self.crop_pad, self.flip = crop_pad, flip
+        if mixup_alpha < 0 or cutmix_alpha < 0 or not 0 <= mix_prob <= 1 or not 0 <= switch_prob <= 1:
+            raise ValueError("mixup_alpha / cutmix_alpha must be >= 0, mix_prob / switch_prob in [0, 1]")
+        self.mixup_alpha, self.cutmix_alpha = float(mixup_alpha), float(cutmix_alpha)
+        self.mix_prob, self.switch_prob = float(mix_prob), float(switch_prob)
+
+    @property
+    def mixes(self) -> bool:
+        return self.mixup_alpha > 0 or self.cutmix_alpha > 0
 
     def collate_batch(self, data: np.ndarray, labels: np.ndarray):
         x = torch.from_numpy(np.ascontiguousarray(data))
@@ -49,8 +65,11 @@ _CTRS = {}
 
 def prepare(batch: Tuple[torch.Tensor, torch.Tensor], ds: ImageDataset, train: bool, seed: int = 0):
     """Device batch → (model input, labels).  GPU: one fused augment kernel launch;
-    CPU: the same ops in torch (NCHW float32)."""
+    CPU: the same ops in torch (NCHW float32).  A training batch of a dataset with mixup /
+    CutMix switched on comes back mixed, with packed fp32 ``[B, 3]`` targets in place of the
+    labels (see :class:`ImageDataset`); validation batches are never mixed."""
     x, y = batch
+    mix = train and getattr(ds, "mixes", False)
     if x.is_cuda:
         from ..ops import kernels as K
         key = (x.device, seed)
@@ -61,6 +80,12 @@ def prepare(batch: Tuple[torch.Tensor, torch.Tensor], ds: ImageDataset, train: b
         if x.dtype != torch.uint8:
             raise TypeError("GPU augmentation expects uint8 images")
         B = x.shape[0]
+        if mix:
+            xb, tb = K.augment_mix(x.contiguous(), y.contiguous(), ctr, B, pad=ds.crop_pad, flip=ds.flip, train=True,
+                                   mean=ds.mean, std=ds.std, mixup_alpha=ds.mixup_alpha,
+                                   cutmix_alpha=ds.cutmix_alpha, mix_prob=ds.mix_prob, switch_prob=ds.switch_prob)
+            K.advance_counter_(ctr, B, B)
+            return xb, tb
         xb, yb = K.augment(x.contiguous(), y.contiguous(), ctr, B, pad=ds.crop_pad if train else 0,
                            flip=ds.flip and train, train=train, mean=ds.mean, std=ds.std)
         K.advance_counter_(ctr, B, B)
@@ -79,4 +104,32 @@ def prepare(batch: Tuple[torch.Tensor, torch.Tensor], ds: ImageDataset, train: b
             xf[m] = xf[m].flip(-1)
     mean = torch.tensor(ds.mean[: xf.shape[1]]).view(1, -1, 1, 1)
     std = torch.tensor(ds.std[: xf.shape[1]]).view(1, -1, 1, 1)
-    return (xf - mean) / std, y
+    xn = (xf - mean) / std
+    return _mix_cpu(xn, y, ds) if mix else (xn, y)
+
+
+def _mix_cpu(x, y, ds: ImageDataset):
+    """mixup / CutMix of a normalised NCHW batch in torch ops (torch's RNG): the plan of the
+    GPU kernel — one lam, one partner shift and one box per step."""
+    B, _, H, W = x.shape
+    yf = y.float()
+    lam, r = 1.0, 0
+    if B > 1:
+        r = 1 + int(torch.randint(0, B - 1, ()))
+        if float(torch.rand(())) < ds.mix_prob:
+            cut = ds.cutmix_alpha > 0 and (ds.mixup_alpha <= 0 or float(torch.rand(())) < ds.switch_prob)
+            alpha = ds.cutmix_alpha if cut else ds.mixup_alpha
+            lam = float(torch.distributions.Beta(alpha, alpha).sample())
+            xp = x.roll(-r, 0)           # row b's partner is row (b + r) % B
+            if cut:
+                ratio = (1.0 - lam) ** 0.5
+                cw, ch = int(W * ratio), int(H * ratio)
+                cx, cy = int(torch.randint(0, W, ())), int(torch.randint(0, H, ()))
+                x0, x1 = max(cx - cw // 2, 0), min(cx + cw // 2, W)
+                y0, y1 = max(cy - ch // 2, 0), min(cy + ch // 2, H)
+                x = x.clone()
+                x[:, :, y0:y1, x0:x1] = xp[:, :, y0:y1, x0:x1]
+                lam = 1.0 - (x1 - x0) * (y1 - y0) / (H * W)
+            else:
+                x = lam * x + (1.0 - lam) * xp
+    return x, torch.stack([yf, yf.roll(-r, 0), torch.full_like(yf, lam)], 1)
