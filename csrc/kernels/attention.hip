@@ -1,14 +1,26 @@
 // attention.hip — fused multi-head attention (flash-attention style) for gfx950.
 //
 // BERT-base MLM (north-star config 5; the reference has no attention model, SURVEY
-// §2.8/§5.7): head_dim 64, non-causal, optional additive key bias (padding mask),
-// sequence length L <= any (tiles of 64, tails masked).  Scores never touch HBM:
+// §2.8/§5.7) and GPT-2 (models/gpt.py): head_dim 64, self-attention (one L for queries and
+// keys), non-causal or causal (compile-time CAUSAL), optional additive key bias (padding
+// mask), sequence length L <= any (tiles of 64, tails masked).  Scores never touch HBM:
 //
 //   fwd   : per (64 queries, b, h) block; loop over 64-key tiles: S^T = K Q^T (MFMA),
 //           online softmax in registers (exp2 domain), O^T += V^T P^T (MFMA);
 //           writes O and the per-row log-sum-exp (base 2) for backward.
 //   bwd   : dq-kernel per query tile (also computes D = rowsum(dO * O)), dkv-kernel per
 //           key tile; both recompute P from the saved LSE — no atomics, deterministic.
+//
+// CAUSAL (kml_attn_causal_fwd / _bwd): query q attends keys <= q.  The 64x64 score tiles above
+// the diagonal are never computed: a forward / dQ block (query tile xt) walks key tiles 0..xt,
+// a dKV block (key tile xt) walks query tiles xt..nqb-1 — (nkb + 1) / (2 nkb) of the tiles.
+// Tiles below the diagonal run the unmasked fast path; the diagonal tile takes the general
+// path with key > q scored -inf before the running max (forward) or given probability and dS
+// exactly 0 (backward: the LSE excludes it, so it is not recomputed as exp2(s - lse)).  The
+// causal forward moves a query column's running max on that column's scores alone, so a row's
+// output bits do not depend on the later rows sharing its wave.  Blocks stay in attn_blk order
+// (heaviest-first measured the same: profiles/r11/causal_attention.md).  The keep-bit buffer
+// keeps its (bh, key tile, query) layout; tiles above the diagonal are neither written nor read.
 //
 // Attention-probability dropout (HF BERT attention_probs_dropout_prob): keep mask
 // Z[b,h,q,key] = half16(word(seed ^ salt, step, b, h, q, key / 2), key & 1) >= p * 2^16
@@ -207,7 +219,7 @@ __device__ __forceinline__ void store4(bf16_t* p, const f32x4_t& v, float s) {
 // register trade of each kernel was measured, profiles/bert_base_r3.md)
 // DM: dropout mode (0 none, 1 hashed keep decisions, stored as bits when a.keep is set), BIAS:
 // additive key bias — compile-time like the backward kernels
-template <int OCC, int DM, bool BIAS>
+template <int OCC, int DM, bool BIAS, bool CAUSAL>
 __global__ __launch_bounds__(256, OCC) void k_attn_fwd(AttnArgs a) {
   // K/V double-buffered (40 KB: 4 blocks per CU, the VGPR occupancy): one barrier per key
   // tile, and the register-staged next tile is stored after this tile's MFMAs, a whole tile
@@ -236,19 +248,21 @@ __global__ __launch_bounds__(256, OCC) void k_attn_fwd(AttnArgs a) {
   tile_store(sK2[0], rk, tid);
   tile_store(sV2[0], rv, tid);
   const int nkb = (L + 63) / 64;
-  if (nkb > 1) {
+  const int nk = CAUSAL ? min(nkb, xt + 1) : nkb;   // key tiles this block visits (causal: 0 .. xt)
+  if (nk > 1) {
     tile_load(rk, Kb, a.ldk, 64, L, tid);
     tile_load(rv, Vb, a.ldv, 64, L, tid);
   }
   __syncthreads();
   const bf16x8_t qf0 = frag_rows(sQ, 16 * w, 0, lane), qf1 = frag_rows(sQ, 16 * w, 1, lane);
+  const int qq = q0 + 16 * w + (lane & 15);   // this lane's query
 
   float m2 = -INFINITY, lsum = 0.f;
   f32x4_t acc[4];
 #pragma unroll
   for (int d = 0; d < 4; ++d) acc[d] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
-  for (int kb = 0; kb < nkb; ++kb) {
+  for (int kb = 0; kb < nk; ++kb) {
     const char* sK = sK2[kb & 1];
     const char* sV = sV2[kb & 1];
     f32x4_t s[4];
@@ -258,11 +272,12 @@ __global__ __launch_bounds__(256, OCC) void k_attn_fwd(AttnArgs a) {
       s[t] = MFMA16(frag_rows(sK, 16 * t, 0, lane), qf0, s[t]);
       s[t] = MFMA16(frag_rows(sK, 16 * t, 1, lane), qf1, s[t]);
     }
-    // bias or key tail: scale + bias + mask every score; otherwise the max of the raw scores
-    // (scale > 0) and one fma per probability below
-    const bool gen = BIAS || kb * 64 + 64 > L;
+    // bias, key tail or the causal diagonal tile: scale + bias + mask every score; otherwise
+    // the max of the raw scores (scale > 0) and one fma per probability below
+    const bool gen = BIAS || kb * 64 + 64 > L || (CAUSAL && kb == xt);
     float mx = -INFINITY;
     if (gen) {
+      const int lim = qq - kb * 64 - 4 * g;   // causal: 16t + i > lim is a key past the query
 #pragma unroll
       for (int t = 0; t < 4; ++t)
 #pragma unroll
@@ -271,6 +286,7 @@ __global__ __launch_bounds__(256, OCC) void k_attn_fwd(AttnArgs a) {
           float v = s[t][i] * sl2;
           if (BIAS && key < L) v += bias[key] * LOG2E;
           if (key >= L) v = -INFINITY;
+          if (CAUSAL && 16 * t + i > lim) v = -INFINITY;
           s[t][i] = v;
           mx = fmaxf(mx, v);
         }
@@ -285,7 +301,9 @@ __global__ __launch_bounds__(256, OCC) void k_attn_fwd(AttnArgs a) {
     if (__any(mx > m2 + 8.f)) {
       mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
       mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-      const float mn = fmaxf(m2, mx);
+      // causal: a query column moves only on its own scores, so a row's result does not
+      // depend on the later rows that share its wave (the vote above is wave-wide)
+      const float mn = CAUSAL ? (mx > m2 + 8.f ? mx : m2) : fmaxf(m2, mx);
       const float alpha = mn == -INFINITY ? 1.f : fexp2(m2 - mn);
       lsum *= alpha;
 #pragma unroll
@@ -307,7 +325,6 @@ __global__ __launch_bounds__(256, OCC) void k_attn_fwd(AttnArgs a) {
 #pragma unroll
     for (int t = 0; t < 4; ++t) lsum += (s[t][0] + s[t][1]) + (s[t][2] + s[t][3]);
     if constexpr (DM != 0) {   // zero the dropped probabilities (1/(1-p) is applied to O at the end)
-      const int qq = q0 + 16 * w + (lane & 15);
       const unsigned bits = drop.bits16(qq, kb * 64 + 4 * g);
 #pragma unroll
       for (int t = 0; t < 4; ++t)
@@ -323,10 +340,10 @@ __global__ __launch_bounds__(256, OCC) void k_attn_fwd(AttnArgs a) {
       acc[d] = MFMA16(frag_tr(sV, 16 * d, 0, lane), p0, acc[d]);
       acc[d] = MFMA16(frag_tr(sV, 16 * d, 1, lane), p1, acc[d]);
     }
-    if (kb + 1 < nkb) {   // buffer (kb+1)&1 last held tile kb-1: every wave left it at the last barrier
+    if (kb + 1 < nk) {   // buffer (kb+1)&1 last held tile kb-1: every wave left it at the last barrier
       tile_store(sK2[(kb + 1) & 1], rk, tid);
       tile_store(sV2[(kb + 1) & 1], rv, tid);
-      if (kb + 2 < nkb) {
+      if (kb + 2 < nk) {
         tile_load(rk, Kb, a.ldk, (kb + 2) * 64, L, tid);
         tile_load(rv, Vb, a.ldv, (kb + 2) * 64, L, tid);
       }
@@ -335,7 +352,7 @@ __global__ __launch_bounds__(256, OCC) void k_attn_fwd(AttnArgs a) {
   }
   lsum += __shfl_xor(lsum, 16, 64);
   lsum += __shfl_xor(lsum, 32, 64);
-  const int q = q0 + 16 * w + (lane & 15);
+  const int q = qq;
   if (q < L) {
     const float inv = lsum > 0.f ? drop.sc / lsum : 0.f;
     bf16_t* op = a.out + (long long)(b * L + q) * a.ldout + h * 64;
@@ -349,7 +366,7 @@ __global__ __launch_bounds__(256, OCC) void k_attn_fwd(AttnArgs a) {
 // DM: dropout mode (0 none, 1 the forward's keep bits, 2 re-hashed), BIAS: additive key bias —
 // compile-time, so the per-probability code carries no uniform branches (a branch per element
 // was a scheduling barrier between the VALU work and the MFMAs around it)
-template <int OCC, int DM, bool BIAS>
+template <int OCC, int DM, bool BIAS, bool CAUSAL>
 __global__ __launch_bounds__(256, OCC) void k_attn_bwd_dq(AttnArgs a) {
   __shared__ __attribute__((aligned(16))) char sK2[2][8192];   // K/V double-buffered (k_attn_fwd)
   __shared__ __attribute__((aligned(16))) char sV2[2][8192];
@@ -395,9 +412,10 @@ __global__ __launch_bounds__(256, OCC) void k_attn_bwd_dq(AttnArgs a) {
   tile_load(rk, Kb, a.ldk, 0, L, tid);
   tile_load(rv, Vb, a.ldv, 0, L, tid);
   const int nkb = (L + 63) / 64;
+  const int nk = CAUSAL ? min(nkb, xt + 1) : nkb;   // key tiles this block visits (k_attn_fwd)
   tile_store(sK2[0], rk, tid);
   tile_store(sV2[0], rv, tid);
-  if (nkb > 1) {
+  if (nk > 1) {
     tile_load(rk, Kb, a.ldk, 64, L, tid);
     tile_load(rv, Vb, a.ldv, 64, L, tid);
   }
@@ -408,11 +426,11 @@ __global__ __launch_bounds__(256, OCC) void k_attn_bwd_dq(AttnArgs a) {
       reinterpret_cast<const unsigned short*>(a.keep + ((long long)bh * nkb * (nkb * 64) + (qok ? q : 0)) * 8 + 2 * g);
   const long long kstride = (long long)nkb * 64 * 4;   // u16 units per key tile
   unsigned knext = kbits ? kp16[0] : 0xFFFFu;
-  for (int kb = 0; kb < nkb; ++kb) {
+  for (int kb = 0; kb < nk; ++kb) {
     const char* sK = sK2[kb & 1];
     const char* sV = sV2[kb & 1];
     unsigned bits = knext;
-    if (kbits && kb + 1 < nkb) knext = kp16[(kb + 1) * kstride];
+    if (kbits && kb + 1 < nk) knext = kp16[(kb + 1) * kstride];
     if constexpr (DM == 2) bits = drop.bits16(q, kb * 64 + 4 * g);
     f32x4_t s[4], dp[4];
 #pragma unroll
@@ -424,8 +442,10 @@ __global__ __launch_bounds__(256, OCC) void k_attn_bwd_dq(AttnArgs a) {
       dp[t] = MFMA16(frag_rows(sV, 16 * t, 0, lane), df0, dp[t]);
       dp[t] = MFMA16(frag_rows(sV, 16 * t, 1, lane), df1, dp[t]);
     }
-    // dS = P (.) (dP (.) Z/(1-p) - D); bias / key tail only on the general path
-    const bool gen = BIAS || kb * 64 + 64 > L;
+    // dS = P (.) (dP (.) Z/(1-p) - D); bias / key tail / causal diagonal only on the general
+    // path.  A masked probability (key > q) is exactly 0: the LSE excludes it
+    const bool gen = BIAS || kb * 64 + 64 > L || (CAUSAL && kb == xt);
+    const int lim = q - kb * 64 - 4 * g;   // causal: 16t + i > lim is a key past the query
 #pragma unroll
     for (int t = 0; t < 4; ++t)
 #pragma unroll
@@ -435,7 +455,7 @@ __global__ __launch_bounds__(256, OCC) void k_attn_bwd_dq(AttnArgs a) {
         if (gen) {
           float v = s[t][i] * sl2;
           if (BIAS && key < L) v += bias[key] * LOG2E;
-          if (key < L) p = fexp2(v - lse);
+          if (key < L && !(CAUSAL && 16 * t + i > lim)) p = fexp2(v - lse);
         } else {
           p = fexp2(fmaf(s[t][i], sl2, -lse));
         }
@@ -452,10 +472,10 @@ __global__ __launch_bounds__(256, OCC) void k_attn_bwd_dq(AttnArgs a) {
       acc[d] = MFMA16(frag_tr(sK, 16 * d, 0, lane), d0, acc[d]);
       acc[d] = MFMA16(frag_tr(sK, 16 * d, 1, lane), d1, acc[d]);
     }
-    if (kb + 1 < nkb) {
+    if (kb + 1 < nk) {
       tile_store(sK2[(kb + 1) & 1], rk, tid);
       tile_store(sV2[(kb + 1) & 1], rv, tid);
-      if (kb + 2 < nkb) {
+      if (kb + 2 < nk) {
         tile_load(rk, Kb, a.ldk, (kb + 2) * 64, L, tid);
         tile_load(rv, Vb, a.ldv, (kb + 2) * 64, L, tid);
       }
@@ -472,7 +492,7 @@ __global__ __launch_bounds__(256, OCC) void k_attn_bwd_dq(AttnArgs a) {
 // ------------------------------------------------------------------------------ backward: dK, dV
 // DM / BIAS as k_attn_bwd_dq.  Without a bias the keys past L keep a zero bias: their dK / dV
 // rows are never stored and no other key's rows read them.
-template <int OCC, int DM, bool BIAS>
+template <int OCC, int DM, bool BIAS, bool CAUSAL>
 __global__ __launch_bounds__(256, OCC) void k_attn_bwd_dkv(AttnArgs a) {
   // double-buffered like k_attn_fwd: Q, dO, LSE, D and the keep bits of a query tile
   __shared__ __attribute__((aligned(16))) char sQ2[2][8192];
@@ -532,16 +552,22 @@ __global__ __launch_bounds__(256, OCC) void k_attn_bwd_dkv(AttnArgs a) {
       *reinterpret_cast<uint2*>(&sM2[j][1][2 * tid]) = make_uint2(mnext.y, mnext.w);
     }
   };
-  fetch(0);
+  // causal: query tiles xt .. nqb-1 (earlier queries never see this key tile); the double
+  // buffer alternates from the first visited tile
+  const int qs = CAUSAL ? xt : 0;
+  fetch(qs);
   stage(0);
-  if (nqb > 1) fetch(1);
+  if (qs + 1 < nqb) fetch(qs + 1);
   __syncthreads();
-  for (int qb = 0; qb < nqb; ++qb) {
-    const char* sQ = sQ2[qb & 1];
-    const char* sO = sO2[qb & 1];
-    const float* sL = sL2[qb & 1];
-    const float* sD = sD2[qb & 1];
-    const unsigned* sM = sM2[qb & 1][kbit >> 5];
+  for (int qb = qs; qb < nqb; ++qb) {
+    const int cur = CAUSAL ? (qb - qs) & 1 : qb & 1;
+    // causal diagonal tile: queries 16t + i < lim come before this lane's key (masked)
+    const int lim = CAUSAL && qb == xt ? kl - 4 * g : 0;
+    const char* sQ = sQ2[cur];
+    const char* sO = sO2[cur];
+    const float* sL = sL2[cur];
+    const float* sD = sD2[cur];
+    const unsigned* sM = sM2[cur][kbit >> 5];
     f32x4_t s[4], dp[4];
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
@@ -563,7 +589,10 @@ __global__ __launch_bounds__(256, OCC) void k_attn_bwd_dkv(AttnArgs a) {
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int r = 16 * t + 4 * g + i;
-        const float p = fexp2(fmaf(s[t][i], sl2, BIAS ? kb2 - lv[i] : -lv[i]));
+        float p = fexp2(fmaf(s[t][i], sl2, BIAS ? kb2 - lv[i] : -lv[i]));
+        // diagonal tile: query < key is masked, its probability (and dS) exactly 0 — not
+        // exp2(s - lse), the LSE excludes it
+        if (CAUSAL && 16 * t + i < lim) p = 0.f;
         if constexpr (DM != 0) {
           const int m = DM == 1 ? bitmask(mv[i], kbit & 31) : drop.keep1(qb * 64 + r, key);
           // dV takes P (.) Z (1/(1-p) applied at the store), dS = P (.) (dP (.) Z/(1-p) - D)
@@ -584,8 +613,8 @@ __global__ __launch_bounds__(256, OCC) void k_attn_bwd_dkv(AttnArgs a) {
       adk[d] = MFMA16(frag_tr(sQ, 16 * d, 0, lane), d0, adk[d]);
       adk[d] = MFMA16(frag_tr(sQ, 16 * d, 1, lane), d1, adk[d]);
     }
-    if (qb + 1 < nqb) {   // buffer (qb+1)&1 last held tile qb-1: every wave left it at the last barrier
-      stage((qb + 1) & 1);
+    if (qb + 1 < nqb) {   // buffer cur^1 last held tile qb-1: every wave left it at the last barrier
+      stage(CAUSAL ? cur ^ 1 : (qb + 1) & 1);
       if (qb + 2 < nqb) fetch(qb + 2);
       __syncthreads();
     }
@@ -608,9 +637,10 @@ bool aligned16(const void* p) { return (((unsigned long long)p) & 15ull) == 0; }
 // q/k/v/out: token-major [B*L, ld*] bf16, head h at column 64h (head_dim must be 64)
 // ctr/salt/pdrop: attention-probability dropout (ctr null or pdrop 0: none); keep: null or a
 // [B*H, nkb, 64*nkb] u64 buffer (nkb = ceil(L/64)) that receives the keep bits (Drop)
-KML_API int kml_attn_fwd(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* out, float* lse,
-                         const float* bias, int ldq, int ldk, int ldv, int ldout, int B, int H, int L, float scale,
-                         const float* ctr, int salt, float pdrop, unsigned char* keep, hipStream_t s) {
+template <bool CAUSAL>
+static int attn_fwd_launch(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* out, float* lse,
+                           const float* bias, int ldq, int ldk, int ldv, int ldout, int B, int H, int L, float scale,
+                           const float* ctr, int salt, float pdrop, unsigned char* keep, hipStream_t s) {
   if (L <= 0 || B <= 0 || H <= 0 || ldq % 8 || ldk % 8 || ldv % 8 || ldout % 4) return (int)hipErrorInvalidValue;
   if (!aligned16(q) || !aligned16(k) || !aligned16(v)) return (int)hipErrorInvalidValue;
   AttnArgs a{};
@@ -622,22 +652,23 @@ KML_API int kml_attn_fwd(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16
   const dim3 grid((L + 63) / 64, B * H);
   const bool dm = ctr != nullptr && pdrop > 0.f;
   if (bias) {
-    if (dm) hipLaunchKernelGGL((k_attn_fwd<4, 1, true>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((k_attn_fwd<4, 0, true>), grid, dim3(256), 0, s, a);
+    if (dm) hipLaunchKernelGGL((k_attn_fwd<4, 1, true, CAUSAL>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((k_attn_fwd<4, 0, true, CAUSAL>), grid, dim3(256), 0, s, a);
   } else {
-    if (dm) hipLaunchKernelGGL((k_attn_fwd<4, 1, false>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((k_attn_fwd<4, 0, false>), grid, dim3(256), 0, s, a);
+    if (dm) hipLaunchKernelGGL((k_attn_fwd<4, 1, false, CAUSAL>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((k_attn_fwd<4, 0, false, CAUSAL>), grid, dim3(256), 0, s, a);
   }
   KML_LAUNCH_CHECK();
 }
 
 // dq/dk/dv may point into one fused [B*L, 3*H*64] buffer (ld = 3*H*64); dsum: [B*H*L] fp32 scratch;
 // keep: the forward's keep bits (read instead of re-hashing), or null
-KML_API int kml_attn_bwd(const bf16_t* q, const bf16_t* k, const bf16_t* v, const bf16_t* o, const bf16_t* dout,
-                         const float* lse, float* dsum, const float* bias, bf16_t* dq, bf16_t* dk, bf16_t* dv,
-                         int ldq, int ldk, int ldv, int ldo, int lddo, int lddq, int lddk, int lddv, int B, int H,
-                         int L, float scale, const float* ctr, int salt, float pdrop, const unsigned char* keep,
-                         hipStream_t s) {
+template <bool CAUSAL>
+static int attn_bwd_launch(const bf16_t* q, const bf16_t* k, const bf16_t* v, const bf16_t* o, const bf16_t* dout,
+                           const float* lse, float* dsum, const float* bias, bf16_t* dq, bf16_t* dk, bf16_t* dv,
+                           int ldq, int ldk, int ldv, int ldo, int lddo, int lddq, int lddk, int lddv, int B, int H,
+                           int L, float scale, const float* ctr, int salt, float pdrop, const unsigned char* keep,
+                           hipStream_t s) {
   if (L <= 0 || ldq % 8 || ldk % 8 || ldv % 8 || ldo % 8 || lddo % 8 || lddq % 4 || lddk % 4 || lddv % 4)
     return (int)hipErrorInvalidValue;
   AttnArgs a{};
@@ -653,10 +684,13 @@ KML_API int kml_attn_bwd(const bf16_t* q, const bf16_t* k, const bf16_t* v, cons
   // (124 VGPRs, no spills), dKV at 2 (~211 VGPRs; 3 spills and doubles its time)
   const int dm = (ctr == nullptr || pdrop <= 0.f) ? 0 : (keep != nullptr ? 1 : 2);
   constexpr int DKV_OCC = 3;
-#define KML_ATTN_BWD(DM, BI)                                              \
-  do {                                                                    \
-    hipLaunchKernelGGL((k_attn_bwd_dq<4, DM, BI>), grid, dim3(256), 0, s, a);  \
-    hipLaunchKernelGGL((k_attn_bwd_dkv<DKV_OCC, DM, BI>), grid, dim3(256), 0, s, a); \
+  // causal re-hash mode (DM 2: the hash and the diagonal mask live together): one wave per SIMD
+  // less, so that no causal instantiation spills (profiles/r11/causal_attention.md)
+#define KML_ATTN_BWD(DM, BI)                                                                             \
+  do {                                                                                                   \
+    hipLaunchKernelGGL((k_attn_bwd_dq<(CAUSAL && DM == 2) ? 3 : 4, DM, BI, CAUSAL>), grid, dim3(256), 0, s, a); \
+    hipLaunchKernelGGL((k_attn_bwd_dkv<(CAUSAL && DM == 2) ? DKV_OCC - 1 : DKV_OCC, DM, BI, CAUSAL>), grid,  \
+                       dim3(256), 0, s, a);                                                              \
   } while (0)
   if (bias) {
     if (dm == 0) KML_ATTN_BWD(0, true);
@@ -669,4 +703,38 @@ KML_API int kml_attn_bwd(const bf16_t* q, const bf16_t* k, const bf16_t* v, cons
   }
 #undef KML_ATTN_BWD
   KML_LAUNCH_CHECK();
+}
+
+KML_API int kml_attn_fwd(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* out, float* lse,
+                         const float* bias, int ldq, int ldk, int ldv, int ldout, int B, int H, int L, float scale,
+                         const float* ctr, int salt, float pdrop, unsigned char* keep, hipStream_t s) {
+  return attn_fwd_launch<false>(q, k, v, out, lse, bias, ldq, ldk, ldv, ldout, B, H, L, scale, ctr, salt, pdrop, keep,
+                                s);
+}
+
+KML_API int kml_attn_bwd(const bf16_t* q, const bf16_t* k, const bf16_t* v, const bf16_t* o, const bf16_t* dout,
+                         const float* lse, float* dsum, const float* bias, bf16_t* dq, bf16_t* dk, bf16_t* dv,
+                         int ldq, int ldk, int ldv, int ldo, int lddo, int lddq, int lddk, int lddv, int B, int H,
+                         int L, float scale, const float* ctr, int salt, float pdrop, const unsigned char* keep,
+                         hipStream_t s) {
+  return attn_bwd_launch<false>(q, k, v, o, dout, lse, dsum, bias, dq, dk, dv, ldq, ldk, ldv, ldo, lddo, lddq, lddk,
+                                lddv, B, H, L, scale, ctr, salt, pdrop, keep, s);
+}
+
+// causal self-attention (query q attends keys <= q of its sequence): same arguments
+KML_API int kml_attn_causal_fwd(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* out, float* lse,
+                                const float* bias, int ldq, int ldk, int ldv, int ldout, int B, int H, int L,
+                                float scale, const float* ctr, int salt, float pdrop, unsigned char* keep,
+                                hipStream_t s) {
+  return attn_fwd_launch<true>(q, k, v, out, lse, bias, ldq, ldk, ldv, ldout, B, H, L, scale, ctr, salt, pdrop, keep,
+                               s);
+}
+
+KML_API int kml_attn_causal_bwd(const bf16_t* q, const bf16_t* k, const bf16_t* v, const bf16_t* o,
+                                const bf16_t* dout, const float* lse, float* dsum, const float* bias, bf16_t* dq,
+                                bf16_t* dk, bf16_t* dv, int ldq, int ldk, int ldv, int ldo, int lddo, int lddq,
+                                int lddk, int lddv, int B, int H, int L, float scale, const float* ctr, int salt,
+                                float pdrop, const unsigned char* keep, hipStream_t s) {
+  return attn_bwd_launch<true>(q, k, v, o, dout, lse, dsum, bias, dq, dk, dv, ldq, ldk, ldv, ldo, lddo, lddq, lddk,
+                               lddv, B, H, L, scale, ctr, salt, pdrop, keep, s);
 }

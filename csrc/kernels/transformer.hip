@@ -756,3 +756,47 @@ KML_API int kml_mlm_mask(const long long* ids, long long* xout, long long* pos, 
   hipLaunchKernelGGL(k_mlm_mask, dim3(B), dim3(256), 0, s, ids, xout, pos, lab, ctr, ticket, L, P, mask_id, vocab);
   KML_LAUNCH_CHECK();
 }
+
+// ---------------------------------------------------------------------------------------
+// Decoder language models (models/gpt.py).
+// Two-table embedding sum[t] = word[ids[t]] + pos[t % L]: k_embed_fwd without the token-type
+// row.  The backward is kml_embed_bwd with a null type table (word + position kernels).
+__global__ __launch_bounds__(256) void k_embed2_fwd(const long long* __restrict__ ids,
+                                                    const bf16_t* __restrict__ word, const bf16_t* __restrict__ pos,
+                                                    bf16_t* __restrict__ out, long long T, int L, int N) {
+  const int lane = threadIdx.x & 63;
+  const long long t = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (t >= T) return;
+  const long long w = ids[t];
+  const int p = (int)(t % L);
+  for (int c = lane * 4; c < N; c += 256) {
+    float a[4], b[4];
+    ld4(word + w * N + c, a);
+    ld4(pos + (long long)p * N + c, b);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) a[k] += b[k];
+    st4(out + t * N + c, a);
+  }
+}
+
+KML_API int kml_embed2_fwd(const long long* ids, const bf16_t* word, const bf16_t* pos, bf16_t* out, long long T,
+                           int L, int N, hipStream_t s) {
+  if (N % 4 || L < 1 || T < 1 || !ids || !word || !pos || !out) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_embed2_fwd, dim3((unsigned)((T + 3) / 4)), dim3(256), 0, s, ids, word, pos, out, T, L, N);
+  KML_LAUNCH_CHECK();
+}
+
+// next-token labels: out[b][t] = ids[b][t + 1], out[b][L - 1] = ignore
+__global__ void k_lm_shift_labels(const long long* __restrict__ ids, long long* __restrict__ out, long long T, int L,
+                                  long long ignore) {
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < T; i += stride)
+    out[i] = (int)(i % L) == L - 1 ? ignore : ids[i + 1];
+}
+
+KML_API int kml_lm_shift_labels(const long long* ids, long long* out, int B, int L, long long ignore, hipStream_t s) {
+  if (B < 1 || L < 1 || !ids || !out) return (int)hipErrorInvalidValue;
+  const long long T = (long long)B * L;
+  hipLaunchKernelGGL(k_lm_shift_labels, dim3(kml_stream_grid(T, 256)), dim3(256), 0, s, ids, out, T, L, ignore);
+  KML_LAUNCH_CHECK();
+}

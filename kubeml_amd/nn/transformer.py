@@ -73,6 +73,46 @@ class _LNFn(Function):
         return dxin, None, None, None, dres, None, None
 
 
+class _AddNormFn(Function):
+    """Pre-LN add-and-normalise: (LN(s), s) with s = dropout(x) + res, on the LayerNorm
+    kernels alone.  ``ln_fwd`` already writes s beside the normalised row; the backward hands
+    the stream gradient ds to ``ln_bwd`` as its ``dx_add`` addend, so a residual stream built
+    as a chain of these runs no add kernel forward or backward."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, mod, res, drop=None):
+        from ..ops import transformer as T
+        y, s, mean, rstd = T.ln_fwd(x, master_of(weight), master_of(bias), res=res, eps=mod.eps, drop=drop)
+        if s is x:   # no residual, no dropout: the stream is the input itself
+            s = x.view_as(x)
+        ctx.save = (s, mean, rstd)
+        ctx.mod = mod
+        ctx.has_res = res is not None
+        ctx.drop = drop
+        ctx.set_materialize_grads(False)
+        return y, s
+
+    @staticmethod
+    def backward(ctx, dy, ds):
+        from ..ops import transformer as T
+        s, mean, rstd = ctx.save
+        mod = ctx.mod
+        if dy is None:
+            raise RuntimeError("add_norm: the normalised output must take part in the loss")
+        # bias gradient of the Linear whose output is x (``_kml_in_linear``), as in _LNFn
+        lin_in = getattr(mod, "_kml_in_linear", None) if _RES_FUSE else None
+        dbias = None
+        if lin_in is not None and getattr(lin_in, "bias", None) is not None and lin_in.out_pad == s.shape[-1]:
+            dbias = grad_storage_of(lin_in.bias)
+            object.__setattr__(lin_in, "_kml_bias_done", True)
+        r = T.ln_bwd(_bf(dy).contiguous(), s, mean, rstd, master_of(mod.weight), grad_storage_of(mod.weight),
+                     grad_storage_of(mod.bias), dx_add=None if ds is None else _bf(ds).contiguous(), drop=ctx.drop,
+                     dbias_in=dbias)
+        total, dx = r if ctx.drop is not None else (r, r)   # total: dLN + ds, the stream's gradient
+        ctx.save = ctx.drop = None
+        return dx, None, None, None, (total if ctx.has_res else None), None
+
+
 class LayerNorm(tnn.LayerNorm):
     """LayerNorm over the last dim; ``forward(x, residual, dropout)`` normalises
     ``dropout(x) + residual``.  On the GPU in training the dropout runs inside the LayerNorm
@@ -95,6 +135,20 @@ class LayerNorm(tnn.LayerNorm):
         x2 = _bf(x).reshape(-1, shp[-1]).contiguous()
         r2 = None if residual is None else _bf(residual).reshape(-1, shp[-1]).contiguous()
         return _LNFn.apply(x2, self.weight, self.bias, self, r2, drop, sep).view(shp)
+
+    def add_norm(self, x, residual=None, dropout=None):
+        """Pre-LN residual step: returns ``(LN(s), s)`` with ``s = dropout(x) + residual`` (2-d
+        token-major inputs).  On the GPU one LayerNorm launch forward and one backward: the
+        sum, the dropout and the gradient sum ``dLN + ds`` all run inside them."""
+        on = dropout is not None and dropout.training and dropout.p > 0.0
+        if not x.is_cuda:
+            s = dropout(x) if on else x
+            if residual is not None:
+                s = s + residual
+            return F.layer_norm(s, self.normalized_shape, self.weight, self.bias, self.eps), s
+        drop = (dropout.rng.tensor(x.device), dropout.salt, dropout.p) if on else None
+        r2 = None if residual is None else _bf(residual).contiguous()
+        return _AddNormFn.apply(_bf(x).contiguous(), self.weight, self.bias, self, r2, drop)
 
 
 _LN_DROP_FUSE = True
@@ -175,15 +229,16 @@ class Dropout(tnn.Module):
 # ====================================================================================== attention
 class _AttnFn(Function):
     @staticmethod
-    def forward(ctx, qkv, B, H, L, bias, drop=None):
+    def forward(ctx, qkv, B, H, L, bias, drop=None, causal=False):
         from ..ops import transformer as T
         D = H * 64
         q, k, v = qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:]
         keep = T.attn_keep_buffer(B, H, L, qkv.device) if drop is not None and drop[2] > 0.0 else None
-        out, lse = T.attn_fwd(q, k, v, B, H, L, bias=bias, drop=drop, keep=keep)
+        out, lse = T.attn_fwd(q, k, v, B, H, L, bias=bias, drop=drop, keep=keep, causal=causal)
         ctx.save = (qkv, out, lse, bias, keep)
         ctx.dims = (B, H, L)
         ctx.drop = drop
+        ctx.causal = causal
         return out
 
     @staticmethod
@@ -194,19 +249,23 @@ class _AttnFn(Function):
         D = H * 64
         dqkv = torch.empty_like(qkv)
         T.attn_bwd(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], out, _bf(dout).contiguous(), lse, B, H, L, bias=bias,
-                   dq=dqkv[:, :D], dk=dqkv[:, D:2 * D], dv=dqkv[:, 2 * D:], drop=ctx.drop, keep=keep)
+                   dq=dqkv[:, :D], dk=dqkv[:, D:2 * D], dv=dqkv[:, 2 * D:], drop=ctx.drop, keep=keep,
+                   causal=ctx.causal)
         ctx.save = None
-        return dqkv, None, None, None, None, None
+        return dqkv, None, None, None, None, None, None
 
 
-def attention_reference(qkv, B, H, L, bias=None, keep=None):
+def attention_reference(qkv, B, H, L, bias=None, keep=None, causal=False):
     """fp32 torch attention on a fused [B*L, 3*H*64] buffer (CPU path / tests); keep:
-    optional [B, H, L, L] dropout multiplier (0 or 1/(1-p)) applied to the probabilities."""
+    optional [B, H, L, L] dropout multiplier (0 or 1/(1-p)) applied to the probabilities;
+    causal: lower-triangular mask (query t attends keys <= t)."""
     D = H * 64
     q, k, v = (qkv[:, i * D:(i + 1) * D].reshape(B, L, H, 64).permute(0, 2, 1, 3) for i in range(3))
     s = q @ k.transpose(-1, -2) / math.sqrt(64)
     if bias is not None:
         s = s + bias.view(B, 1, 1, L)
+    if causal:
+        s = s.masked_fill(torch.ones(L, L, dtype=torch.bool, device=s.device).triu(1), float("-inf"))
     pr = s.softmax(-1)
     if keep is not None:
         pr = pr * keep
@@ -214,10 +273,10 @@ def attention_reference(qkv, B, H, L, bias=None, keep=None):
     return o.permute(0, 2, 1, 3).reshape(B * L, D)
 
 
-def attention_reference_dropout(qkv, B, H, L, bias, p):
+def attention_reference_dropout(qkv, B, H, L, bias, p, causal=False):
     """CPU attention with probability dropout (torch RNG; same semantics as the kernel)."""
     keep = (torch.rand(B, H, L, L) >= p).float() / (1.0 - p)
-    return attention_reference(qkv, B, H, L, bias, keep=keep)
+    return attention_reference(qkv, B, H, L, bias, keep=keep, causal=causal)
 
 
 class SelfAttention(tnn.Module):
@@ -227,8 +286,9 @@ class SelfAttention(tnn.Module):
 
     def __init__(self, hidden: int = 768, heads: int = 12, prefix_self: str = "self.", prefix_out: str = "output.dense.",
                  post_ln_eps: Optional[float] = None, prefix_ln: str = "output.LayerNorm.", attn_dropout: float = 0.0,
-                 rng: Optional["RNGState"] = None):
+                 rng: Optional["RNGState"] = None, causal: bool = False):
         super().__init__()
+        self.causal = bool(causal)   # query t attends keys <= t (decoder self-attention)
         # attention-probability dropout (HF attention_probs_dropout_prob), inside the kernel
         self.attn_dropout = float(attn_dropout)
         self.rng = rng or RNGState()
@@ -273,14 +333,15 @@ class SelfAttention(tnn.Module):
         qkv = self.qkv(x)
         if not x.is_cuda:
             if self.training and self.attn_dropout > 0:
-                ctx = attention_reference_dropout(qkv, B, self.heads, L, bias, self.attn_dropout)
+                ctx = attention_reference_dropout(qkv, B, self.heads, L, bias, self.attn_dropout,
+                                                  causal=self.causal)
             else:
-                ctx = attention_reference(qkv, B, self.heads, L, bias)
+                ctx = attention_reference(qkv, B, self.heads, L, bias, causal=self.causal)
         else:
             drop = None
             if self.training and self.attn_dropout > 0:
                 drop = (self.rng.tensor(x.device), self.salt, self.attn_dropout)
-            ctx = _AttnFn.apply(qkv.contiguous(), B, self.heads, L, bias, drop)
+            ctx = _AttnFn.apply(qkv.contiguous(), B, self.heads, L, bias, drop, self.causal)
         return self.out(ctx)
 
 

@@ -56,11 +56,12 @@ def _keep_arg(keep, B, H, L, drop):
     return keep.data_ptr()
 
 
-def attn_fwd(q, k, v, B, H, L, bias=None, out=None, scale=None, drop=None, keep=None):
+def attn_fwd(q, k, v, B, H, L, bias=None, out=None, scale=None, drop=None, keep=None, causal=False):
     """q/k/v: [B*L, ld] bf16 views with head h at columns 64h..64h+63 (may be column
     slices of one fused QKV buffer).  drop: (ctr, salt, p) attention-probability dropout;
     keep: optional :func:`attn_keep_buffer` that receives the dropout keep bits, so
-    :func:`attn_bwd` reads them instead of re-hashing.  Returns (out [B*L, H*64], lse [B*H, L])."""
+    :func:`attn_bwd` reads them instead of re-hashing.  causal: query t attends keys <= t only
+    (the key tiles above the diagonal are skipped).  Returns (out [B*L, H*64], lse [B*H, L])."""
     for n, t in (("q", q), ("k", k), ("v", v)):
         _chk_view(t, n)
         if t.shape[0] != B * L or t.shape[1] < H * 64:
@@ -74,16 +75,17 @@ def attn_fwd(q, k, v, B, H, L, bias=None, out=None, scale=None, drop=None, keep=
     lse = torch.empty((B * H, L), dtype=F32, device=q.device)
     scale = 1.0 / math.sqrt(64) if scale is None else scale
     c, salt, pd = _drop_args(drop)
-    HIP.call("kml_attn_fwd", "p p p p p p i i i i i i i f p i f p s", _p(q), _p(k), _p(v), _p(out), _p(lse),
-             _p(bias), q.stride(0), k.stride(0), v.stride(0), out.stride(0), B, H, L, float(scale), c, salt, pd,
-             _keep_arg(keep, B, H, L, drop), _s())
+    HIP.call("kml_attn_causal_fwd" if causal else "kml_attn_fwd", "p p p p p p i i i i i i i f p i f p s",
+             _p(q), _p(k), _p(v), _p(out), _p(lse), _p(bias), q.stride(0), k.stride(0), v.stride(0), out.stride(0),
+             B, H, L, float(scale), c, salt, pd, _keep_arg(keep, B, H, L, drop), _s())
     return out, lse
 
 
 def attn_bwd(q, k, v, o, dout, lse, B, H, L, bias=None, dq=None, dk=None, dv=None, scale=None, drop=None,
-             keep=None):
+             keep=None, causal=False):
     """Gradients of attention; dq/dk/dv may be column views of one [B*L, 3*H*64] buffer.
-    keep: the keep-bit buffer the forward filled (same drop), or None to re-hash the mask."""
+    keep: the keep-bit buffer the forward filled (same drop), or None to re-hash the mask;
+    causal: as given to :func:`attn_fwd`."""
     dev = q.device
     if dq is None:
         dq = torch.empty((B * L, H * 64), dtype=BF16, device=dev)
@@ -100,7 +102,8 @@ def attn_bwd(q, k, v, o, dout, lse, B, H, L, bias=None, dq=None, dk=None, dv=Non
     dsum = torch.empty((B * H, L), dtype=F32, device=dev)
     scale = 1.0 / math.sqrt(64) if scale is None else scale
     c, salt, pd = _drop_args(drop)
-    HIP.call("kml_attn_bwd", "p p p p p p p p p p p i i i i i i i i i i i f p i f p s",
+    HIP.call("kml_attn_causal_bwd" if causal else "kml_attn_bwd",
+             "p p p p p p p p p p p i i i i i i i i i i i f p i f p s",
              _p(q), _p(k), _p(v), _p(o), _p(dout), _p(lse), _p(dsum), _p(bias), _p(dq), _p(dk), _p(dv),
              q.stride(0), k.stride(0), v.stride(0), o.stride(0), dout.stride(0), dq.stride(0), dk.stride(0),
              dv.stride(0), B, H, L, float(scale), c, salt, pd, _keep_arg(keep, B, H, L, drop), _s())
@@ -195,6 +198,27 @@ def embed_bwd(ids, tt, dsum, dword, dpos, dtype, L):
     N = dsum.shape[-1]
     HIP.call("kml_embed_bwd", "p p p p p p l i i s", _p(ids), _p(tt), _p(dsum), _p(dword), _p(dpos), _p(dtype), T, L,
              N, _s())
+
+
+def embed2_fwd(ids, word, pos, L):
+    """Two-table embedding (decoder LMs): word[ids] + pos[t % L].  Its backward is
+    :func:`embed_bwd` with ``tt`` and ``dtype`` None."""
+    T = ids.numel()
+    N = word.shape[-1]
+    out = torch.empty((T, N), dtype=BF16, device=ids.device)
+    HIP.call("kml_embed2_fwd", "p p p p l i i s", _p(ids), _p(word), _p(pos), _p(out), T, L, N, _s())
+    return out
+
+
+def lm_shift_labels(ids, ignore_index=-100):
+    """Next-token labels of int64 ``[B, L]`` ids: out[b, t] = ids[b, t + 1], out[b, L - 1] = ignore."""
+    if ids.dtype != I64 or ids.dim() != 2 or not ids.is_cuda:
+        raise TypeError("lm_shift_labels: int64 [B, L] GPU ids")
+    ids = ids.contiguous()
+    B, L = ids.shape
+    out = torch.empty_like(ids)
+    HIP.call("kml_lm_shift_labels", "p p i i l s", _p(ids), _p(out), B, L, int(ignore_index), _s())
+    return out
 
 
 def gather_rows(src, idx):
