@@ -1,0 +1,477 @@
+// decode.hip — one-token-at-a-time inference for the decoder LMs (models/gpt.py) on gfx950:
+//   kml_kv_append       K / V columns of a token-major fused QKV buffer -> head-major cache
+//   kml_attn_decode     one query per (sequence, head) against the cached keys, split over the key
+//                       range in chunks of a FIXED number of keys; the last block of a (b, h) to
+//                       finish folds the chunk partials in chunk order
+//   kml_gemm_skinny     y[M <= 16][N] = act(x · wᵀ + bias): every weight byte read once, the 16 x rows
+//                       are the second MFMA operand, K split over waves and blocks, folded in order
+//   kml_embed2_at       word[ids[b]] + pos[lens[b]]
+//   kml_decode_advance  greedy / Gumbel-max token choice, eos bookkeeping, lens and step advance
+// Sequence lengths, the sampling temperature, seed, step and eos live in device memory, so one
+// captured step replays for every token.  No float atomics anywhere: every reduction has a fixed
+// order (lane butterflies, wave order in LDS, chunk / split order in the fold).
+#include "kml_common.h"
+
+namespace {
+
+constexpr float LOG2E = 1.4426950408889634f;
+
+// the counter hash of transformer.hip's dropout (same mixing)
+__device__ __forceinline__ unsigned hash3(unsigned a, unsigned b, unsigned c) {
+  unsigned h = a * 0x9E3779B1u ^ (b + 0x7F4A7C15u) * 0x85EBCA77u ^ c * 0xC2B2AE3Du;
+  h ^= h >> 15; h *= 0x2C1B3C6Du; h ^= h >> 12; h *= 0x297A2D39u; h ^= h >> 15;
+  return h;
+}
+
+// Hand-off of partials to the last block of a group without fences (conv_igemm.hip's
+// group_reduce_rows): partials are stored write-through (st_part), every storing wave drains
+// before the barrier, one lane takes a relaxed agent-scope ticket, and the last of `expected`
+// blocks reads them with agent-scope loads (ld_part: past its L1 and any stale L2 line) and puts
+// the counter back to 0.  A release fence per block would write back its XCD's whole dirty L2.
+// Returns true in every thread of that last block.
+__device__ __forceinline__ void st_part(float* p, float v) {
+  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ float ld_part(const float* p) {
+  return __hip_atomic_load(const_cast<float*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ bool last_block(unsigned* __restrict__ counter, unsigned expected, unsigned* sh_last) {
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const unsigned t = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const unsigned l = (t == expected - 1u) ? 1u : 0u;
+    if (l) __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    *sh_last = l;
+  }
+  __syncthreads();
+  return *sh_last != 0u;
+}
+
+__device__ __forceinline__ void unpack8(const uint4 v, float* f) {
+  f[0] = lo_bf(v.x); f[1] = hi_bf(v.x); f[2] = lo_bf(v.y); f[3] = hi_bf(v.y);
+  f[4] = lo_bf(v.z); f[5] = hi_bf(v.z); f[6] = lo_bf(v.w); f[7] = hi_bf(v.w);
+}
+
+// ------------------------------------------------------------------------------------ KV append
+// One thread per 16 bytes: (token row, head, K | V, 8 columns).  Prefill: row t of sequence b goes
+// to cache row t; decode (Lq = 1): to cache row lens[b].  Rows outside [0, Lcap) are dropped.
+__global__ __launch_bounds__(256) void k_kv_append(const bf16_t* __restrict__ qkv, int ldq, bf16_t* __restrict__ kc,
+                                                   bf16_t* __restrict__ vc, const int* __restrict__ lens, int B, int H,
+                                                   int Lq, int Lcap, int decode) {
+  const long long total = (long long)B * Lq * H * 16;
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  const int c8 = (int)(i & 7), isv = (int)((i >> 3) & 1);
+  const long long rh = i >> 4;
+  const int h = (int)(rh % H);
+  const long long tr = rh / H;           // token row b * Lq + t
+  const int b = (int)(tr / Lq), t = (int)(tr % Lq);
+  const int row = decode ? lens[b] : t;
+  if (row < 0 || row >= Lcap) return;
+  const uint4 v = *reinterpret_cast<const uint4*>(qkv + tr * ldq + (long long)(1 + isv) * H * 64 + h * 64 + c8 * 8);
+  bf16_t* dst = (isv ? vc : kc) + (((long long)b * H + h) * Lcap + row) * 64 + c8 * 8;
+  *reinterpret_cast<uint4*>(dst) = v;
+}
+
+// ------------------------------------------------------------------------------ decode attention
+// grid (ceil(Lcap / C), B * H), 256 threads.  Block (ch, bh) owns keys ch*C .. ch*C + C - 1 of one
+// 128-byte-row key stream: lane = (key lane>>3, 16-byte column group lane&7), wave w and round i
+// take key ch*C + 32 i + 8 w + (lane>>3).  Keys past lens[b] are never loaded: their score is
+// -inf and their probability 0 by selection.  Partial per chunk: (max, sum, o[64]) in the exp2
+// domain; the last block of the (b, h) folds chunks 0 .. lens[b] / C in that order.
+constexpr int ATTN_WS = 66;   // floats per (b, h, chunk)
+
+template <int C>
+__global__ __launch_bounds__(256) void k_attn_decode(const bf16_t* __restrict__ q, int ldq,
+                                                     const bf16_t* __restrict__ kc, const bf16_t* __restrict__ vc,
+                                                     const int* __restrict__ lens, float* __restrict__ ws,
+                                                     unsigned* __restrict__ cnt, bf16_t* __restrict__ out, int ldo,
+                                                     int H, int Lcap, float scale) {
+  constexpr int R = C / 32;
+  __shared__ float sm[4], ss[4], so[4][64];
+  __shared__ unsigned sh_last;
+  const int ch = blockIdx.x, bh = blockIdx.y, nch = gridDim.x;
+  const int b = bh / H, h = bh % H;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  int len = lens[b];
+  len = len < 0 ? 0 : (len > Lcap - 1 ? Lcap - 1 : len);
+  const int n = len + 1, j0 = ch * C;
+  float* part = ws + ((long long)bh * nch + ch) * ATTN_WS;
+  if (j0 < n) {   // block-uniform: a chunk wholly past the sequence writes nothing
+    const int c8 = lane & 7, kr = lane >> 3;
+    float qf[8];
+    unpack8(*reinterpret_cast<const uint4*>(q + (long long)b * ldq + h * 64 + c8 * 8), qf);
+    const float sc = scale * LOG2E;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) qf[k] *= sc;
+    const long long base = (long long)bh * Lcap * 64 + c8 * 8;
+    float s[R];
+    uint4 kv[R];
+#pragma unroll
+    for (int i = 0; i < R; ++i) {
+      const int j = j0 + i * 32 + wv * 8 + kr;
+      kv[i] = j < n ? *reinterpret_cast<const uint4*>(kc + base + (long long)j * 64) : make_uint4(0, 0, 0, 0);
+    }
+    float mx = -INFINITY;
+#pragma unroll
+    for (int i = 0; i < R; ++i) {
+      const int j = j0 + i * 32 + wv * 8 + kr;
+      float kf[8], d = 0.f;
+      unpack8(kv[i], kf);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) d = fmaf(qf[k], kf[k], d);
+      d += __shfl_xor(d, 1, 64);
+      d += __shfl_xor(d, 2, 64);
+      d += __shfl_xor(d, 4, 64);
+      s[i] = j < n ? d : -INFINITY;
+      mx = fmaxf(mx, s[i]);
+    }
+    // V rows in flight while the maximum crosses the block
+#pragma unroll
+    for (int i = 0; i < R; ++i) {
+      const int j = j0 + i * 32 + wv * 8 + kr;
+      kv[i] = j < n ? *reinterpret_cast<const uint4*>(vc + base + (long long)j * 64) : make_uint4(0, 0, 0, 0);
+    }
+    mx = wave_max(mx);
+    if (lane == 0) sm[wv] = mx;
+    __syncthreads();
+    mx = fmaxf(fmaxf(sm[0], sm[1]), fmaxf(sm[2], sm[3]));   // finite: key j0 is valid
+    float o[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, ls = 0.f;
+#pragma unroll
+    for (int i = 0; i < R; ++i) {
+      const int j = j0 + i * 32 + wv * 8 + kr;
+      const float p = j < n ? __builtin_amdgcn_exp2f(s[i] - mx) : 0.f;
+      float vf[8];
+      unpack8(kv[i], vf);
+      ls += p;
+#pragma unroll
+      for (int k = 0; k < 8; ++k) o[k] = fmaf(p, vf[k], o[k]);
+    }
+#pragma unroll
+    for (int sh = 8; sh < 64; sh <<= 1) {
+      ls += __shfl_xor(ls, sh, 64);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) o[k] += __shfl_xor(o[k], sh, 64);
+    }
+    if (lane < 8) {
+#pragma unroll
+      for (int k = 0; k < 8; ++k) so[wv][c8 * 8 + k] = o[k];
+    }
+    if (lane == 0) ss[wv] = ls;
+    __syncthreads();
+    if (threadIdx.x < 64)
+      st_part(part + 2 + threadIdx.x,
+              ((so[0][threadIdx.x] + so[1][threadIdx.x]) + so[2][threadIdx.x]) + so[3][threadIdx.x]);
+    if (threadIdx.x == 64) {
+      st_part(part, mx);
+      st_part(part + 1, ((ss[0] + ss[1]) + ss[2]) + ss[3]);
+    }
+  }
+  if (!last_block(cnt + bh, (unsigned)nch, &sh_last)) return;
+  if (threadIdx.x >= 64) return;
+  const float* p0 = ws + (long long)bh * nch * ATTN_WS;
+  const int nv = len / C + 1;   // <= nch: len < Lcap
+  float M = -INFINITY;
+  for (int c = 0; c < nv; ++c) M = fmaxf(M, ld_part(p0 + c * ATTN_WS));
+  float S = 0.f, O = 0.f;
+  for (int c = 0; c < nv; ++c) {
+    const float w = __builtin_amdgcn_exp2f(ld_part(p0 + c * ATTN_WS) - M);
+    S = fmaf(w, ld_part(p0 + c * ATTN_WS + 1), S);
+    O = fmaf(w, ld_part(p0 + c * ATTN_WS + 2 + threadIdx.x), O);
+  }
+  out[(long long)b * ldo + h * 64 + threadIdx.x] = f2bf(O / S);
+}
+
+// ------------------------------------------------------------------------------- skinny GEMM
+// grid (ceil(N / 16), S), NW waves.  A block owns 16 weight rows and `cps` 64-wide K chunks;
+// wave w takes chunks w, w + NW, ... of them.  v_mfma_f32_16x16x32_bf16 with the weight rows as
+// the first operand and the (zero-padded to 16) x rows as the second; a lane's two fragments of a
+// chunk are 32 contiguous bytes (k = 64 c + 16 (lane>>4) + 8 j), so a wave instruction pair reads
+// 128 contiguous bytes of each of its 16 rows.  x comes straight from L2 into registers beside
+// the weights.  Result: lane holds y[m = lane&15][n0 + 4 (lane>>4) + i].  The waves are summed in wave order through LDS; with S > 1 the block's partial
+// goes to the workspace and the last block of the row group folds splits 0 .. S-1 in that order.
+// The order of every sum depends on (N, K) alone, so a row's result does not depend on M or on
+// the other rows.  Two shapes of block: 16 waves (the layer weights: K of 768 .. 3072 spread over
+// the waves of one block, so N >= 1536 needs no block split) and 4 waves (vocabulary-sized N:
+// thousands of blocks, 12 or 13 per CU, where a 16-wave block's tail would leave CUs idle).
+constexpr int SK_NONE = 0, SK_GELU = 1;
+
+template <int NW, int U>
+__global__ __launch_bounds__(NW * 64) void k_gemm_skinny(const bf16_t* __restrict__ x, int ldx,
+                                                         const bf16_t* __restrict__ w, int ldw,
+                                                         const float* __restrict__ bias, bf16_t* __restrict__ y,
+                                                         int ldy, int M, int N, int K, int cps, int act,
+                                                         float* __restrict__ ws, unsigned* __restrict__ cnt) {
+  constexpr int NT = NW * 64, E = 256;
+  __shared__ float red[NW][E];
+  __shared__ unsigned sh_last;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int r = lane & 15, g = lane >> 4;
+  const int nb = blockIdx.x, sp = blockIdx.y, S = gridDim.y;
+  const int n0 = nb * 16;
+  const int nk = (K + 63) >> 6;
+  const int c0 = sp * cps;
+  const int c1 = c0 + cps < nk ? c0 + cps : nk;
+  const bool xok = r < M, wok = n0 + r < N;
+  const bf16_t* wp = w + (long long)(wok ? n0 + r : 0) * ldw + g * 16;
+  const bf16_t* xp = x + (long long)(xok ? r : 0) * ldx + g * 16;
+  const bf16x8_t zero = {0, 0, 0, 0, 0, 0, 0, 0};
+  f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
+  for (int cb = c0 + wv; cb < c1; cb += NW * U) {
+    bf16x8_t a[U][2], bq[U][2];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int c = cb + NW * u;
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const bool ok = c < c1 && c * 64 + g * 16 + j * 8 < K;   // K % 8 == 0: a fragment is in or out
+        a[u][j] = ok && wok ? *reinterpret_cast<const bf16x8_t*>(wp + c * 64 + j * 8) : zero;
+        bq[u][j] = ok && xok ? *reinterpret_cast<const bf16x8_t*>(xp + c * 64 + j * 8) : zero;
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+#pragma unroll
+      for (int j = 0; j < 2; ++j) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[u][j], bq[u][j], acc, 0, 0, 0);
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) red[wv][i * 64 + lane] = acc[i];
+  __syncthreads();
+  // element e = 64 i + lane of the block's 16 x 16 tile, as stored above
+  auto finish = [&](int e, float v) {
+    const int m = e & 15, n = n0 + ((e & 63) >> 4) * 4 + (e >> 6);
+    if (m >= M || n >= N) return;
+    if (bias) v += bias[n];
+    if (act == SK_GELU) v = kml_gelu(v);
+    y[(long long)m * ldy + n] = f2bf(v);
+  };
+  float* mine = ws + ((long long)nb * S + sp) * E;
+  for (int e = threadIdx.x; e < E; e += NT) {
+    float v = red[0][e];
+#pragma unroll
+    for (int k = 1; k < NW; ++k) v += red[k][e];
+    if (S > 1) st_part(mine + e, v);
+    else finish(e, v);
+  }
+  if (S == 1) return;
+  if (!last_block(cnt + nb, (unsigned)S, &sh_last)) return;
+  const float* p0 = ws + (long long)nb * S * E;
+  for (int e = threadIdx.x; e < E; e += NT) {
+    float v = ld_part(p0 + e);
+    for (int s2 = 1; s2 < S; ++s2) v += ld_part(p0 + (long long)s2 * E + e);
+    finish(e, v);
+  }
+}
+
+// Block shape and K split of an (N, K) weight — a function of (N, K) alone.  Vocabulary-sized N
+// (>= 2048 row groups): blocks of 4 waves, no split.  Otherwise blocks of 16 waves; N >= 1536 gives
+// enough blocks as it is, below that K is split until ~192 blocks stream, at least 12 chunks
+// (one per wave of three quarters of the block) each.  splits > 0 overrides the split (tuning).
+struct SkinnyPlan {
+  int big, S, cps, groups;
+};
+static inline SkinnyPlan skinny_plan(int N, int K, int splits) {
+  const int nk = (K + 63) / 64, n16 = (N + 15) / 16;
+  SkinnyPlan p;
+  p.big = n16 >= 2048;
+  int S = 1;
+  if (splits > 0) {
+    S = splits;
+  } else if (!p.big && n16 < 96) {
+    S = (192 + n16 - 1) / n16;
+    if (S > nk / 12) S = nk / 12;
+  }
+  if (S > nk) S = nk;
+  if (S < 1) S = 1;
+  p.cps = (nk + S - 1) / S;
+  p.S = (nk + p.cps - 1) / p.cps;
+  p.groups = n16;
+  return p;
+}
+
+// ------------------------------------------------------------------------------- embedding at lens
+__global__ __launch_bounds__(64) void k_embed2_at(const long long* __restrict__ ids, const int* __restrict__ lens,
+                                                  const bf16_t* __restrict__ word, const bf16_t* __restrict__ pos,
+                                                  bf16_t* __restrict__ out, int N, long long vocab, int max_pos) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  long long id = ids[b];
+  id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
+  int p = lens[b];
+  p = p < 0 ? 0 : (p >= max_pos ? max_pos - 1 : p);
+  for (int c = lane * 4; c < N; c += 256) {
+    const uint2 a = *reinterpret_cast<const uint2*>(word + id * N + c);
+    const uint2 e = *reinterpret_cast<const uint2*>(pos + (long long)p * N + c);
+    uint2 o;
+    o.x = pack_bf2(lo_bf(a.x) + lo_bf(e.x), hi_bf(a.x) + hi_bf(e.x));
+    o.y = pack_bf2(lo_bf(a.y) + lo_bf(e.y), hi_bf(a.y) + hi_bf(e.y));
+    *reinterpret_cast<uint2*>(out + (long long)b * N + c) = o;
+  }
+}
+
+// ------------------------------------------------------------------------------- next token
+// ctl = [seed, step, eos (-1: none), unused] int32; temp = [temperature] fp32 (read when sample).
+// One block per sequence.  Key of column c: logit (greedy) or logit / T + Gumbel(u), u a 23-bit
+// uniform in (0, 1) from hash(seed ^ mix(b), step, c).  Largest key wins, lowest column on ties.
+// Every block reads the step before its ticket; the last one advances it.
+__global__ __launch_bounds__(256) void k_decode_advance(const bf16_t* __restrict__ logits, int ldl, int classes,
+                                                        int sample, const float* __restrict__ temp,
+                                                        int* __restrict__ ctl, long long* __restrict__ next_ids,
+                                                        long long* __restrict__ tokens, int* __restrict__ lens,
+                                                        int* __restrict__ finished, int Lcap,
+                                                        unsigned* __restrict__ ticket) {
+  __shared__ float sv[4];
+  __shared__ int si[4];
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const unsigned seed = (unsigned)ctl[0], step = (unsigned)ctl[1];
+  const int eos = ctl[2];
+  const float invT = sample ? 1.f / temp[0] : 1.f;
+  const unsigned sb = seed ^ ((unsigned)b * 0x9E3779B9u + 0x67756D62u);
+  const bf16_t* row = logits + (long long)b * ldl;
+  float best = -INFINITY;
+  int bi = 0x7fffffff;
+  for (int c0 = tid * 8; c0 < classes; c0 += 2048) {
+    float f[8];
+    unpack8(*reinterpret_cast<const uint4*>(row + c0), f);   // ldl % 8 == 0: the row covers c0 .. c0 + 7
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const int c = c0 + k;
+      float v = f[k];
+      if (sample) {
+        // (k + 1/2) 2^-23, k < 2^23: exact in fp32, never 0 or 1
+        const float u = ((float)(hash3(sb, step, (unsigned)c) >> 9) + 0.5f) * 1.1920928955078125e-7f;
+        v = fmaf(v, invT, -logf(-logf(u)));
+      }
+      if (c < classes && (v > best || (v == best && c < bi))) { best = v; bi = c; }
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(best, o, 64);
+    const int oi = __shfl_xor(bi, o, 64);
+    if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
+  }
+  if (lane == 0) { sv[wv] = best; si[wv] = bi; }
+  __syncthreads();
+  if (tid != 0) return;
+  for (int k = 1; k < 4; ++k)
+    if (sv[k] > best || (sv[k] == best && si[k] < bi)) { best = sv[k]; bi = si[k]; }
+  if (bi >= classes) bi = 0;   // a row without one comparable value (all NaN)
+  long long tok = bi;
+  if (eos >= 0 && finished[b]) tok = eos;
+  if (eos >= 0 && tok == eos) finished[b] = 1;
+  const int len = lens[b];
+  next_ids[b] = tok;
+  if (len >= -1 && len + 1 < Lcap) tokens[(long long)b * Lcap + len + 1] = tok;
+  lens[b] = len + 1 < Lcap ? (len + 1 < 0 ? 0 : len + 1) : Lcap - 1;
+  __threadfence();
+  const unsigned tk = atomicAdd(ticket, 1u);
+  if (tk == gridDim.x - 1) {
+    ctl[1] = (int)(step + 1u);
+    atomicExch(ticket, 0u);
+  }
+}
+
+}  // namespace
+
+// ========================================================================================= C ABI
+KML_API int kml_kv_append(const bf16_t* qkv, int ldq, bf16_t* kc, bf16_t* vc, const int* lens, int B, int H, int Lq,
+                          int Lcap, int decode, hipStream_t s) {
+  if (!qkv || !kc || !vc || B < 1 || H < 1 || Lq < 1 || Lcap < 64 || Lcap % 64 || ldq % 8 || ldq < 3 * H * 64)
+    return (int)hipErrorInvalidValue;
+  if (decode && (Lq != 1 || !lens)) return (int)hipErrorInvalidValue;
+  if (!decode && Lq > Lcap) return (int)hipErrorInvalidValue;
+  const long long total = (long long)B * Lq * H * 16;
+  hipLaunchKernelGGL(k_kv_append, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, qkv, ldq, kc, vc, lens, B, H,
+                     Lq, Lcap, decode);
+  KML_LAUNCH_CHECK();
+}
+
+// keys per chunk of kml_attn_decode (profiles/r12/kv_decode.md has the sweep)
+#define KML_DECODE_CHUNK 256
+
+KML_API int kml_attn_decode_chunk(void) { return KML_DECODE_CHUNK; }
+
+// floats of workspace for a (B, H, Lcap) cache, sized for the smallest chunk any entry point takes
+KML_API long long kml_attn_decode_ws_floats(int B, int H, int Lcap) {
+  return (long long)B * H * ((Lcap + 63) / 64) * ATTN_WS;
+}
+
+static int attn_decode_launch(int chunk, const bf16_t* q, int ldq, const bf16_t* kc, const bf16_t* vc, const int* lens,
+                              float* ws, unsigned* cnt, bf16_t* out, int ldo, int B, int H, int Lcap, float scale,
+                              hipStream_t s) {
+  if (!q || !kc || !vc || !lens || !ws || !cnt || !out || B < 1 || H < 1 || Lcap < 64 || Lcap % 64 || ldq % 8 ||
+      ldq < H * 64 || ldo < H * 64 || (long long)B * H > 65535)
+    return (int)hipErrorInvalidValue;
+  const dim3 grid((unsigned)((Lcap + chunk - 1) / chunk), (unsigned)(B * H));
+#define KML_AD(CC)                                                                                                  \
+  hipLaunchKernelGGL(k_attn_decode<CC>, grid, dim3(256), 0, s, q, ldq, kc, vc, lens, ws, cnt, out, ldo, H, Lcap, scale)
+  switch (chunk) {
+    case 64: KML_AD(64); break;
+    case 128: KML_AD(128); break;
+    case 256: KML_AD(256); break;
+    case 512: KML_AD(512); break;
+    default: return (int)hipErrorInvalidValue;
+  }
+#undef KML_AD
+  KML_LAUNCH_CHECK();
+}
+
+// q: row b of a [B, ldq] buffer, head h at columns 64h (the Q third of a fused QKV row);
+// kc / vc [B, H, Lcap, 64]; ws from kml_attn_decode_ws_floats; cnt: B*H zeroed tickets
+KML_API int kml_attn_decode(const bf16_t* q, int ldq, const bf16_t* kc, const bf16_t* vc, const int* lens, float* ws,
+                            unsigned* cnt, bf16_t* out, int ldo, int B, int H, int Lcap, float scale, hipStream_t s) {
+  return attn_decode_launch(KML_DECODE_CHUNK, q, ldq, kc, vc, lens, ws, cnt, out, ldo, B, H, Lcap, scale, s);
+}
+
+// the same kernel at another chunk size (64 / 128 / 256 / 512): the sweep of tools/bench_gpt_decode.py
+KML_API int kml_attn_decode_sweep(int chunk, const bf16_t* q, int ldq, const bf16_t* kc, const bf16_t* vc,
+                                  const int* lens, float* ws, unsigned* cnt, bf16_t* out, int ldo, int B, int H,
+                                  int Lcap, float scale, hipStream_t s) {
+  return attn_decode_launch(chunk, q, ldq, kc, vc, lens, ws, cnt, out, ldo, B, H, Lcap, scale, s);
+}
+
+// K splits kml_gemm_skinny takes for an (N, K) weight by default.  With S > 1 splits the caller
+// provides a workspace of ceil(N / 16) * S * 256 floats and ceil(N / 16) zeroed tickets.
+KML_API int kml_gemm_skinny_splits(int N, int K) {
+  if (N < 1 || K < 8) return 0;
+  return skinny_plan(N, K, 0).S;
+}
+
+// splits: 0 = the default plan, > 0 = that many K splits (the tuning sweep)
+KML_API int kml_gemm_skinny(const bf16_t* x, int ldx, const bf16_t* w, int ldw, const float* bias, bf16_t* y, int ldy,
+                            int M, int N, int K, int act, int splits, float* ws, unsigned* cnt, hipStream_t s) {
+  if (!x || !w || !y || M < 1 || M > 16 || N < 1 || K < 8 || K % 8 || ldx % 8 || ldw % 8 || ldx < K || ldw < K ||
+      ldy < N || (act != SK_NONE && act != SK_GELU) || splits < 0)
+    return (int)hipErrorInvalidValue;
+  const SkinnyPlan p = skinny_plan(N, K, splits);
+  if (p.S > 1 && (!ws || !cnt)) return (int)hipErrorInvalidValue;
+  if (p.S > 65535) return (int)hipErrorInvalidValue;
+  const dim3 grid((unsigned)p.groups, (unsigned)p.S);
+  if (p.big)
+    hipLaunchKernelGGL((k_gemm_skinny<4, 4>), grid, dim3(256), 0, s, x, ldx, w, ldw, bias, y, ldy, M, N, K, p.cps,
+                       act, ws, cnt);
+  else
+    hipLaunchKernelGGL((k_gemm_skinny<16, 4>), grid, dim3(1024), 0, s, x, ldx, w, ldw, bias, y, ldy, M, N, K, p.cps,
+                       act, ws, cnt);
+  KML_LAUNCH_CHECK();
+}
+
+KML_API int kml_embed2_at(const long long* ids, const int* lens, const bf16_t* word, const bf16_t* pos, bf16_t* out,
+                          int B, int N, long long vocab, int max_pos, hipStream_t s) {
+  if (!ids || !lens || !word || !pos || !out || B < 1 || N < 4 || N % 4 || vocab < 1 || max_pos < 1)
+    return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_embed2_at, dim3((unsigned)B), dim3(64), 0, s, ids, lens, word, pos, out, N, vocab, max_pos);
+  KML_LAUNCH_CHECK();
+}
+
+KML_API int kml_decode_advance(const bf16_t* logits, int ldl, int classes, int sample, const float* temp, int* ctl,
+                               long long* next_ids, long long* tokens, int* lens, int* finished, int B, int Lcap,
+                               unsigned* ticket, hipStream_t s) {
+  if (!logits || !ctl || !next_ids || !tokens || !lens || !finished || !ticket || B < 1 || classes < 1 ||
+      ldl % 8 || ldl < classes || Lcap < 1 || (sample && !temp))
+    return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_decode_advance, dim3((unsigned)B), dim3(256), 0, s, logits, ldl, classes, sample, temp, ctl,
+                     next_ids, tokens, lens, finished, Lcap, ticket);
+  KML_LAUNCH_CHECK();
+}

@@ -12,7 +12,10 @@
   ``(normalised, new stream)``: the residual sums, the hidden dropout and the gradient sums
   run inside the LayerNorm kernels, no add kernel forward or backward;
 * next-token labels from one launch (``kml_lm_shift_labels``); vocab-padded logits go to the
-  cross-entropy kernels in place.
+  cross-entropy kernels in place;
+* inference: ``generate`` / ``prefill`` / ``decode_step`` on a :class:`~kubeml_amd.nn.KVCache` —
+  the prompt through the kernels above, then one captured step per token on the decode kernels
+  (csrc/kernels/decode.hip: cache append, one-query attention, skinny GEMMs, sampling).
 
 FFN activation: the erf GELU of the GEMM epilogue (HF ``activation_function="gelu"``); GPT-2's
 tanh approximation (``gelu_new``) has no epilogue yet.
@@ -23,9 +26,10 @@ import torch
 import torch.nn as tnn
 from torch.autograd import Function
 
+from ..nn.decode import KVCache
 from ..nn.flat import grad_storage_of, shadow_of
 from ..nn.modules import Linear, cross_entropy
-from ..nn.transformer import Dropout, LayerNorm, RNGState, SelfAttention, _bf
+from ..nn.transformer import Dropout, LayerNorm, RNGState, SelfAttention, _bf, gather_rows
 
 
 class _Emb2Fn(Function):
@@ -225,6 +229,218 @@ class GPT2LMHeadModel(tnn.Module):
         logits = self.lm_head(z, keep_pad=True)
         return cross_entropy(logits, tgt.reshape(-1), ignore_index=-100, return_correct=return_correct,
                              classes=self.vocab)
+
+    # ------------------------------------------------------------------ KV-cache decoding
+    # Inference only (no autograd, no dropout whatever the module's mode).  GPU: the prompt runs
+    # the training kernels once, every later token one captured step of the decode kernels
+    # (csrc/kernels/decode.hip).  CPU: the same steps in stock torch on a cache of plain tensors.
+
+    def _closers(self):
+        tr = self.transformer
+        return list(zip(tr.h, [blk.ln_1 for blk in tr.h[1:]] + [tr.ln_f]))
+
+    def new_cache(self, B, Lcap, device=None):
+        tr = self.transformer
+        p = tr.wte.weight
+        return KVCache(len(tr.h), B, tr.h[0].attn.heads, Lcap, device or p.device, dtype=p.dtype)
+
+    @torch.no_grad()
+    def _prefill(self, ids, attention_mask, cache):
+        """Causal forward over the right-padded prompt; appends every layer's K / V; leaves
+        ``lens[b] = prompt_len[b] - 1``; returns the logits of each sequence's last prompt token."""
+        tr = self.transformer
+        B, L = ids.shape
+        if B != cache.B or L > cache.Lcap or L > tr.max_pos:
+            raise ValueError(f"prompt [{B}, {L}] does not fit the cache ({cache.B} x {cache.Lcap}) / max_pos")
+        if attention_mask is None:
+            plen = torch.full((B,), L, dtype=torch.int64, device=ids.device)
+            bias = None
+        else:
+            plen = attention_mask.long().sum(1)
+            pos = torch.arange(L, device=ids.device)[None]
+            if int(plen.min()) < 1 or not bool(((pos < plen[:, None]) == attention_mask.bool()).all()):
+                raise ValueError("prefill: the prompt must be right-padded with at least one token per sequence")
+            bias = ((1.0 - attention_mask.float()) * -10000.0).reshape(B, L).contiguous()
+        gpu = ids.is_cuda
+        H = tr.h[0].attn.heads
+        if gpu:
+            from ..nn.transformer import _AttnFn
+            from ..ops import decode as D
+            from ..ops import transformer as T
+            e = T.embed2_fwd(ids.reshape(-1).contiguous(), shadow_of(tr.wte.weight), shadow_of(tr.wpe.weight), L)
+        else:
+            from ..nn.transformer import attention_reference
+            e = (tr.wte(ids) + tr.wpe(torch.arange(L))[None]).reshape(B * L, -1)
+            if bias is not None:
+                bias = bias.to(e.dtype)
+        x, s = tr.h[0].ln_1.add_norm(e)
+        for i, (blk, ln) in enumerate(self._closers()):
+            qkv = blk.attn.qkv(x).contiguous()
+            if gpu:
+                D.kv_append(qkv, cache.k[i], cache.v[i], L)
+                ctx = _AttnFn.apply(qkv, B, H, L, bias, None, True)
+            else:
+                cache.append_cpu(i, qkv, L, decode=False)
+                ctx = attention_reference(qkv, B, H, L, bias, causal=True)
+            x2, s = blk.ln_2.add_norm(blk.attn.out(ctx), residual=s)
+            x, s = ln.add_norm(blk.mlp(x2), residual=s)
+        rows = torch.arange(B, device=ids.device) * L + plen - 1
+        z = gather_rows(x, rows)
+        cache.lens.copy_((plen - 1).to(torch.int32))
+        cache.tokens.zero_()
+        cache.tokens[:, :L] = ids * (torch.arange(L, device=ids.device)[None] < plen[:, None])
+        cache.finished.zero_()
+        return self.lm_head(z, keep_pad=True)
+
+    @torch.no_grad()
+    def _step(self, cache, advance):
+        """One decode step from ``cache.next_ids`` at position ``lens[b]``: returns the logits
+        ``[B, vocab (padded to 8 on the GPU)]``; ``advance`` also picks the next token."""
+        tr = self.transformer
+        if not cache.lens.is_cuda:
+            e = tr.wte(cache.next_ids) + tr.wpe(cache.lens.long().clamp(max=tr.max_pos - 1))
+            x, s = tr.h[0].ln_1.add_norm(e)
+            for i, (blk, ln) in enumerate(self._closers()):
+                qkv = blk.attn.qkv(x)
+                cache.append_cpu(i, qkv, 1, decode=True)
+                x2, s = blk.ln_2.add_norm(blk.attn.out(cache.attend_cpu(i, qkv)), residual=s)
+                x, s = ln.add_norm(blk.mlp(x2), residual=s)
+            logits = self.lm_head(x)
+            if advance:
+                _advance_cpu(cache, logits, cache.gen)
+            return logits
+        from ..ops import decode as D
+        e = D.embed2_at(cache.next_ids, cache.lens, shadow_of(tr.wte.weight), shadow_of(tr.wpe.weight))
+        x, s = tr.h[0].ln_1.add_norm(e)
+        for i, (blk, ln) in enumerate(self._closers()):
+            qkv = blk.attn.qkv.forward_small(x)
+            D.kv_append(qkv, cache.k[i], cache.v[i], 1, lens=cache.lens)
+            ctx = D.attn_decode(qkv, cache.k[i], cache.v[i], cache.lens, ws=cache.ws)
+            x2, s = blk.ln_2.add_norm(blk.attn.out.forward_small(ctx), residual=s)
+            m = blk.mlp.c_proj.forward_small(blk.mlp.c_fc.forward_small(x2, act="gelu"))
+            x, s = ln.add_norm(m, residual=s)
+        logits = self.lm_head.forward_small(x, keep_pad=True)
+        if advance:
+            D.decode_advance(logits, self.vocab, cache.ctl, cache.temp, cache.next_ids, cache.tokens, cache.lens,
+                             cache.finished, sample=cache.sample)
+        return logits
+
+    def _replay(self, cache, advance):
+        """The GPU step as one captured graph per (cache, advance, sampling); captured on first
+        use after an eager warm-up whose effect on the decode state is rolled back."""
+        key = (bool(advance), bool(cache.sample))
+        ent = cache._graphs.get(key)
+        if ent is None:
+            from ..engine.step import capture_graph
+            state = [cache.lens, cache.tokens, cache.next_ids, cache.finished, cache.ctl]
+            keep = [t.clone() for t in state]
+            cur = torch.cuda.current_stream()
+            side = torch.cuda.Stream()
+            side.wait_stream(cur)
+            with torch.cuda.stream(side):
+                self._step(cache, advance)   # re-appends the same K / V row: idempotent
+            cur.wait_stream(side)
+            for t, k in zip(state, keep):
+                t.copy_(k)
+            torch.cuda.synchronize()
+            g = torch.cuda.CUDAGraph()
+            with capture_graph(g, capture_error_mode="thread_local"):
+                logits = self._step(cache, advance)
+            ent = cache._graphs[key] = (g, logits)
+        ent[0].replay()
+        return ent[1]
+
+    def decode_step(self, cache):
+        """Feed ``cache.next_ids``, append its keys / values, pick the next token (greedy or
+        Gumbel-max, per the cache's sampling state) and advance ``lens``.  Returns the logits."""
+        if cache.lens.is_cuda:
+            return self._replay(cache, True)
+        return self._step(cache, True)
+
+    def prefill(self, ids, attention_mask, cache):
+        """Run the right-padded prompt, fill the cache and pick each sequence's first new token
+        (``cache.next_ids``, ``cache.tokens[b, prompt_len[b]]``).  Returns the prompt's last logits."""
+        logits = self._prefill(ids, attention_mask, cache)
+        if ids.is_cuda:
+            from ..ops import decode as D
+            D.decode_advance(logits, self.vocab, cache.ctl, cache.temp, cache.next_ids, cache.tokens, cache.lens,
+                             cache.finished, sample=cache.sample)
+        else:
+            _advance_cpu(cache, logits, cache.gen)
+        return logits
+
+    def prefill_logits(self, ids, attention_mask, cache):
+        """Teacher-forced :meth:`prefill`: fills the cache, samples nothing.  ``[B, vocab]``."""
+        return self._prefill(ids, attention_mask, cache)[:, :self.vocab]
+
+    @torch.no_grad()
+    def decode_logits(self, cache, ids):
+        """Teacher-forced :meth:`decode_step`: appends the GIVEN token ``ids[b]`` at the next
+        position of every sequence and returns its logits ``[B, vocab]`` (a new tensor)."""
+        cache.lens.add_(1).clamp_(max=cache.Lcap - 1)
+        cache.next_ids.copy_(ids.reshape(-1))
+        logits = self._replay(cache, False) if cache.lens.is_cuda else self._step(cache, False)
+        return logits[:, :self.vocab].clone()
+
+    @torch.no_grad()
+    def generate(self, ids, attention_mask=None, max_new_tokens=32, temperature=0.0, eos_token_id=None, seed=0):
+        """Continue each right-padded prompt by ``max_new_tokens`` tokens: greedy at
+        ``temperature == 0``, else Gumbel-max sampling reproducible from ``seed``.  A sequence that
+        draws ``eos_token_id`` keeps emitting it.  Returns int64 ``[B, Lprompt_max +
+        max_new_tokens]``: row b is its prompt, its new tokens, then ``eos_token_id`` (0 without
+        one) up to the common width."""
+        tr = self.transformer
+        B, L = ids.shape
+        if max_new_tokens < 1:
+            raise ValueError("max_new_tokens must be at least 1")
+        if B > 16:
+            raise ValueError(f"generate: batch {B} > 16 (the decode GEMMs take at most 16 rows)")
+        plen = torch.full((B,), L, dtype=torch.int64) if attention_mask is None else attention_mask.long().sum(1).cpu()
+        if int(plen.max()) + max_new_tokens > tr.max_pos:
+            raise ValueError(f"generate: prompt {int(plen.max())} + {max_new_tokens} new tokens exceeds max_pos "
+                             f"{tr.max_pos}")
+        Lcap = -(-(L + max_new_tokens) // 64) * 64
+        sample = temperature > 0
+        caches = self.__dict__.setdefault("_kml_decode_caches", {})
+        # the captured step holds the addresses of the bf16 shadows: a model moved or flattened
+        # again gets a new cache (and capture)
+        stamp = shadow_of(tr.wte.weight).data_ptr() if ids.is_cuda else 0
+        key = (B, Lcap, sample, ids.device, tr.wte.weight.dtype, stamp)
+        cache = caches.get(key)
+        if cache is None:
+            cache = caches[key] = self.new_cache(B, Lcap, ids.device)
+        cache.reset(seed=seed, temperature=temperature, eos_token_id=eos_token_id)
+        if ids.is_cuda:
+            for p in self.parameters():   # bf16 shadows current before the captured step reads them
+                shadow_of(p)
+        self.prefill(ids, attention_mask, cache)
+        for _ in range(max_new_tokens - 1):
+            self.decode_step(cache)
+        W = L + max_new_tokens
+        out = cache.tokens[:, :W].clone()
+        fill = 0 if eos_token_id is None else int(eos_token_id)
+        end = (plen + max_new_tokens).to(out.device)
+        out.masked_fill_(torch.arange(W, device=out.device)[None] >= end[:, None], fill)
+        return out
+
+
+def _advance_cpu(cache, logits, gen):
+    """Stock-torch twin of ``kml_decode_advance`` on a CPU cache."""
+    eos = int(cache.ctl[2])
+    if cache.sample:
+        u = torch.rand(logits.shape, generator=gen, dtype=torch.float64).clamp_(1e-300, 1.0 - 1e-16)
+        tok = (logits.double() / float(cache.temp[0]) - torch.log(-torch.log(u))).argmax(-1)
+    else:
+        tok = logits.argmax(-1)
+    if eos >= 0:
+        tok = torch.where(cache.finished.bool(), torch.full_like(tok, eos), tok)
+        cache.finished |= (tok == eos).to(torch.int32)
+    cache.next_ids.copy_(tok)
+    nxt = cache.lens.long() + 1
+    ok = nxt < cache.Lcap
+    cache.tokens[torch.arange(cache.B)[ok], nxt[ok]] = tok[ok]
+    cache.lens.copy_(nxt.clamp(max=cache.Lcap - 1).to(torch.int32))
+    cache.ctl[1] += 1
 
 
 def gpt2_small(**kw) -> GPT2LMHeadModel:

@@ -349,6 +349,40 @@ class Linear(tnn.Module):
             y._kml_linear = self   # raw linear output: a consuming cross_entropy may sum our bias grad
         return y
 
+    def forward_small(self, x, act: Optional[str] = None, keep_pad: bool = False):
+        """Inference-only forward for M <= 16 rows (a decode step: M = batch): no autograd, the
+        bf16 shadow weights, the skinny GEMM of ops/decode.py with bias and erf-GELU in its
+        epilogue.  Shapes listed in ``_SMALL_EXISTING`` (from the row count at which the skinny
+        kernel measured slower) and fused-ReLU layers take :meth:`forward` instead."""
+        with torch.no_grad():
+            rows = x.shape[0] if x.dim() == 2 else 0
+            if (not _on_gpu(x) or self.fused_relu or
+                    rows >= _SMALL_EXISTING.get((self.out_pad, self.in_pad), 17)):
+                return self.forward(x, act=act, keep_pad=keep_pad)
+            if act not in (None, "gelu"):
+                raise ValueError(f"forward_small: act {act!r}")
+            if x.dim() != 2:
+                x = x.reshape(x.shape[0], -1)
+            if x.shape[0] > 16:
+                raise ValueError(f"forward_small takes at most 16 rows, got {x.shape[0]}")
+            if x.dtype != torch.bfloat16:
+                x = x.to(torch.bfloat16)
+            if x.shape[1] != self.in_pad:
+                x = _pad_nograd(x, self.in_pad)
+            from ..ops import decode as D
+            w = shadow_of(self.weight).view(self.out_pad, self.in_pad)
+            y = D.gemm_skinny(x.contiguous(), w, None if self.bias is None else master_of(self.bias), act=act)
+            if self.out_pad != self.out_features and not keep_pad:
+                y = y[:, :self.out_features].contiguous()
+            return y
+
+
+# (out_pad, in_pad) -> fewest rows at which forward_small takes the existing route instead: where
+# the skinny kernel measured slower (profiles/r12/kv_decode.md).  GPT-2's tied decoder: the skinny
+# kernel wins at 1 and 4 rows and loses at 16 (x is re-read from L2 by 3142 blocks); 5 .. 15 rows
+# were not measured and go with 16.
+_SMALL_EXISTING: dict = {(50264, 768): 5}
+
 
 # ======================================================================================
 # BatchNorm2d (+ fused ReLU / residual)

@@ -1,0 +1,182 @@
+"""Launchers for the decode kernels (csrc/kernels/decode.hip): KV-cache append, one-query
+attention over the cache, the skinny (M <= 16) GEMM, the embedding at the device lengths and
+the next-token choice.
+
+Everything a step needs that changes per token — sequence lengths, seed / step, temperature,
+eos — is read from device memory, so one captured step replays for every token.  All launches
+go on the current HIP stream and are hipGraph-capturable (no host sync, no memset nodes).
+"""
+from __future__ import annotations
+
+import math
+
+import torch
+
+from .._native import HIP
+from .kernels import BF16, F32, _COUNTERS, _chk, _p, _s
+from .transformer import _chk_view
+
+I32 = torch.int32
+I64 = torch.int64
+
+
+def attn_decode_chunk() -> int:
+    """Keys per chunk of :func:`attn_decode` (a constant of the kernel)."""
+    return int(HIP.raw("kml_attn_decode_chunk"))
+
+
+def attn_decode_workspace(B, H, Lcap, device):
+    """fp32 workspace for the chunk partials of a (B, H, Lcap) cache."""
+    return torch.empty(int(HIP.raw("kml_attn_decode_ws_floats", B, H, Lcap)), dtype=F32, device=device)
+
+
+def _chk_cache(kc, vc, name="cache"):
+    for n, t in (("K", kc), ("V", vc)):
+        _chk(t, BF16, f"{name} {n}", ndim=4)
+    if kc.shape != vc.shape or kc.shape[3] != 64 or kc.shape[2] % 64 or kc.shape[2] < 64:
+        raise ValueError(f"{name}: K and V must be [B, H, Lcap, 64] with Lcap a multiple of 64, got "
+                         f"{tuple(kc.shape)} / {tuple(vc.shape)}")
+    return kc.shape[0], kc.shape[1], kc.shape[2]
+
+
+def _chk_lens(lens, B):
+    _chk(lens, I32, "lens", ndim=1)
+    if lens.numel() != B:
+        raise ValueError(f"lens: expected [{B}] int32, got {tuple(lens.shape)}")
+
+
+def kv_append(qkv, kc, vc, Lq, lens=None):
+    """Copy the K and V columns of a fused ``[B*Lq, 3*H*64]`` QKV buffer into the cache
+    ``kc, vc [B, H, Lcap, 64]``.  ``lens`` None: prefill, row t of sequence b goes to cache row
+    t.  ``lens`` given (``Lq == 1``): the row of sequence b goes to cache row ``lens[b]``.  Rows
+    at or past Lcap are dropped."""
+    B, H, Lcap = _chk_cache(kc, vc)
+    _chk_view(qkv, "qkv")
+    if qkv.shape[0] != B * Lq or qkv.shape[1] != 3 * H * 64:
+        raise ValueError(f"qkv: expected [{B * Lq}, {3 * H * 64}], got {tuple(qkv.shape)}")
+    if lens is not None:
+        if Lq != 1:
+            raise ValueError("kv_append: decode mode appends one row per sequence (Lq == 1)")
+        _chk_lens(lens, B)
+    elif Lq > Lcap:
+        raise ValueError(f"kv_append: {Lq} prompt rows do not fit a cache of {Lcap}")
+    HIP.call("kml_kv_append", "p i p p p i i i i i s", _p(qkv), qkv.stride(0), _p(kc), _p(vc), _p(lens), B, H, Lq,
+             Lcap, int(lens is not None), _s())
+
+
+def attn_decode(q, kc, vc, lens, ws=None, out=None, scale=None, chunk=None):
+    """softmax(q Kᵀ * scale) V over cache rows ``0..lens[b]`` for one query per (b, h).
+    q: ``[B, >= H*64]`` bf16 view, head h at columns 64h (the first third of a fused QKV row).
+    Cache rows past ``lens[b]`` are never read.  Returns ``[B, H*64]`` bf16.  ``chunk``: another
+    keys-per-chunk than the kernel's constant (64 / 128 / 256 / 512; the tuning sweep only)."""
+    B, H, Lcap = _chk_cache(kc, vc)
+    _chk_view(q, "q")
+    if q.shape[0] != B or q.shape[1] < H * 64:
+        raise ValueError(f"q: expected a [{B}, >= {H * 64}] view, got {tuple(q.shape)}")
+    _chk_lens(lens, B)
+    need = int(HIP.raw("kml_attn_decode_ws_floats", B, H, Lcap))
+    if ws is None:
+        ws = torch.empty(need, dtype=F32, device=q.device)
+    _chk(ws, F32, "ws")
+    if ws.numel() < need:
+        raise ValueError(f"ws: {ws.numel()} floats, the cache needs {need}")
+    if out is None:
+        out = torch.empty((B, H * 64), dtype=BF16, device=q.device)
+    _chk_view(out, "out")
+    if out.shape != (B, H * 64):
+        raise ValueError(f"out: expected [{B}, {H * 64}], got {tuple(out.shape)}")
+    scale = 1.0 / math.sqrt(64) if scale is None else scale
+    cnt = _COUNTERS.take(q.device, B * H)
+    if chunk is None:
+        HIP.call("kml_attn_decode", "p i p p p p p p i i i i f s", _p(q), q.stride(0), _p(kc), _p(vc), _p(lens), _p(ws),
+                 _p(cnt), _p(out), out.stride(0), B, H, Lcap, float(scale), _s())
+    else:
+        if chunk not in (64, 128, 256, 512):
+            raise ValueError("chunk must be 64, 128, 256 or 512")
+        HIP.call("kml_attn_decode_sweep", "i p i p p p p p p i i i i f s", int(chunk), _p(q), q.stride(0), _p(kc),
+                 _p(vc), _p(lens), _p(ws), _p(cnt), _p(out), out.stride(0), B, H, Lcap, float(scale), _s())
+    return out
+
+
+def gemm_skinny(x, w, bias=None, act=None, out=None, splits=None):
+    """y[M, N] = act(x[M, K] @ w[N, K]ᵀ + bias) for M <= 16: bf16 in / out, fp32 accumulate, fp32
+    bias, ``act`` None or "gelu" (erf).  x, w and out may be row-major views with a row stride
+    that is a multiple of 8.  Row m of the result does not depend on M or on the other rows.
+    ``splits``: another K split than the kernel's plan for (N, K) (the tuning sweep only)."""
+    _chk_view(x, "x")
+    _chk_view(w, "w")
+    M, K = x.shape
+    N = w.shape[0]
+    if not 1 <= M <= 16:
+        raise ValueError(f"gemm_skinny: M = {M} rows; the skinny kernel takes 1..16")
+    if w.shape[1] != K or K % 8 or K < 8:
+        raise ValueError(f"gemm_skinny: x {tuple(x.shape)} vs w {tuple(w.shape)} (K a multiple of 8)")
+    if act not in (None, "gelu"):
+        raise ValueError(f"gemm_skinny: act {act!r}")
+    if bias is not None:
+        _chk(bias, F32, "bias")
+        if bias.numel() < N:
+            raise ValueError("bias shorter than N")
+    if out is None:
+        out = torch.empty((M, N), dtype=BF16, device=x.device)
+    if out.dtype != BF16 or not out.is_cuda or out.dim() != 2 or out.stride(1) != 1 or out.shape != (M, N):
+        raise ValueError(f"out: expected a row-major bf16 [{M}, {N}] GPU view")
+    S = int(HIP.raw("kml_gemm_skinny_splits", N, K)) if splits is None else int(splits)
+    if S < 1:
+        raise ValueError(f"gemm_skinny: no plan for N = {N}, K = {K}" if splits is None else "splits must be >= 1")
+    ws = cnt = None
+    if S > 1:
+        groups = -(-N // 16)
+        ws = torch.empty(groups * S * 256, dtype=F32, device=x.device)
+        cnt = _COUNTERS.take(x.device, groups)
+    HIP.call("kml_gemm_skinny", "p i p i p p i i i i i i p p s", _p(x), x.stride(0), _p(w), w.stride(0), _p(bias),
+             _p(out), out.stride(0), M, N, K, 1 if act == "gelu" else 0, 0 if splits is None else S, _p(ws), _p(cnt),
+             _s())
+    return out
+
+
+def embed2_at(ids, lens, word, pos, out=None):
+    """out[b] = word[ids[b]] + pos[lens[b]] (bf16 tables; ids int64 [B], lens int32 [B])."""
+    _chk(ids, I64, "ids", ndim=1)
+    B = ids.numel()
+    _chk_lens(lens, B)
+    _chk(word, BF16, "word", ndim=2)
+    _chk(pos, BF16, "pos", ndim=2)
+    N = word.shape[1]
+    if pos.shape[1] != N or N % 4:
+        raise ValueError(f"embed2_at: tables {tuple(word.shape)} / {tuple(pos.shape)}")
+    if out is None:
+        out = torch.empty((B, N), dtype=BF16, device=ids.device)
+    _chk(out, BF16, "out", ndim=2)
+    if out.shape != (B, N):
+        raise ValueError(f"out: expected [{B}, {N}]")
+    HIP.call("kml_embed2_at", "p p p p p i i l i s", _p(ids), _p(lens), _p(word), _p(pos), _p(out), B, N,
+             word.shape[0], pos.shape[0], _s())
+    return out
+
+
+def decode_advance(logits, classes, ctl, temp, next_ids, tokens, lens, finished, sample):
+    """Pick the next token of every sequence from its bf16 logits row and advance the decode
+    state.  ctl int32 ``[seed, step, eos (-1: none), 0]``; temp fp32 ``[temperature]``.
+    ``sample`` False: argmax, lowest index on ties; True: Gumbel-max at ``temp[0]``.  Writes
+    ``next_ids[b]`` and ``tokens[b, lens[b] + 1]``, forces / records eos, increments ``lens[b]``
+    (saturating at Lcap - 1) and the step."""
+    _chk_view(logits, "logits")
+    B, ldw = logits.shape
+    if not 1 <= classes <= ldw:
+        raise ValueError(f"decode_advance: {classes} classes in rows of {ldw}")
+    _chk(ctl, I32, "ctl", ndim=1)
+    _chk(temp, F32, "temp", ndim=1)
+    _chk(next_ids, I64, "next_ids", ndim=1)
+    _chk(tokens, I64, "tokens", ndim=2)
+    _chk(finished, I32, "finished", ndim=1)
+    _chk_lens(lens, B)
+    if ctl.numel() < 4 or temp.numel() < 1 or next_ids.numel() != B or finished.numel() != B or tokens.shape[0] != B:
+        raise ValueError("decode_advance: state tensors do not match the batch")
+    # a row of `ldw` columns must be readable in 16-byte groups up to `classes`
+    if logits.stride(0) < -(-classes // 8) * 8:
+        raise ValueError("decode_advance: logits rows shorter than the classes padded to 8")
+    ticket = _COUNTERS.take(logits.device, 1)
+    HIP.call("kml_decode_advance", "p i i i p p p p p p i i p s", _p(logits), logits.stride(0), int(classes),
+             int(bool(sample)), _p(temp), _p(ctl), _p(next_ids), _p(tokens), _p(lens), _p(finished), B,
+             tokens.shape[1], _p(ticket), _s())

@@ -1,0 +1,233 @@
+"""KV-cache decoding of GPT-2 small (random weights) on one GPU: the decode step against the
+same step on the existing Linear route and against full recompute, the skinny GEMM against the
+existing small-M route per shape, and the decode attention over its keys-per-chunk choices.
+
+    python tools/bench_gpt_decode.py [--rounds 5] [--iters 20] [--new 256] [--out FILE.json]
+
+* decode: B in {1, 4, 16}, prompt 128, ``--new`` tokens.  (a) the captured step of ``generate``
+  (``decode_step`` replays, timed between device events after the prefill); (b) the same step
+  with every ``forward_small`` sent to ``Linear.forward``; (c) ``model(ids)`` on the whole growing
+  sequence per token, B = 1, 32 tokens, host clock ending in a synchronise.  (a) and (b) alternate
+  inside every round; the figure is the median over the rounds.
+* GEMM: the five GPT-2 small weight shapes at M in {1, 4, 8, 16}: ``gemm_skinny`` against what
+  ``Linear.forward`` launches at that M (the 1x1 implicit-GEMM conv, plus the GELU launch).  Each
+  variant walks a ring of weight copies of at least 64 MB, so no launch finds its weights in the
+  L2 the previous one filled; ``iters`` launches per captured graph, variants alternating.
+* attention: B = 4, H = 12, Lcap = 1024, n in {128, 512, 1023} keys, chunk in {64, 128, 256, 512}.
+* floor: the bf16 weight bytes one token reads, over the 6.3 TB/s the microarchitecture notes give
+  as the achievable HBM rate — derived, not measured.
+
+Prints one JSON line.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+SHAPES = [("c_attn", 2304, 768, None, True), ("attn.c_proj", 768, 768, None, True),
+          ("c_fc+gelu", 3072, 768, "gelu", True), ("mlp.c_proj", 768, 3072, None, True),
+          ("lm_head", 50264, 768, None, False)]
+
+
+class _Everything:
+    """stands in for nn.modules._SMALL_EXISTING: every shape takes the existing route from row 0"""
+
+    def get(self, key, default=None):
+        return 0
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--new", type=int, default=256)
+    ap.add_argument("--skip-model", action="store_true")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    import torch
+    if not torch.cuda.is_available():
+        print("bench_gpt_decode: needs a GPU (no fall-back)", file=sys.stderr)
+        sys.exit(2)
+    from kubeml_amd.engine.step import capture_graph
+    from kubeml_amd.nn import modules as NM
+    from kubeml_amd.ops import decode as D
+    from kubeml_amd.ops import kernels as K
+    from kubeml_amd.ops import transformer as T
+    dev = torch.device("cuda", 0)
+    BF = torch.bfloat16
+    gen = torch.Generator(device=dev).manual_seed(0)
+
+    def graphed(fn):
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            fn()
+        torch.cuda.current_stream().wait_stream(s)
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with capture_graph(g):
+            fn()
+        return g.replay
+
+    def alternate(runs, per_run):
+        """median (min, max) microseconds per launch of every variant, alternating inside a round"""
+        times = {k: [] for k in runs}
+        for k, run in runs.items():
+            run()
+        torch.cuda.synchronize()
+        for _ in range(a.rounds):
+            for k, run in runs.items():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                run()
+                e1.record()
+                e1.synchronize()
+                times[k].append(e0.elapsed_time(e1) * 1e3 / per_run)
+        return {k: {"us": round(statistics.median(v), 3), "min": round(min(v), 3), "max": round(max(v), 3)}
+                for k, v in times.items()}
+
+    res = {"device": torch.cuda.get_device_name(0), "chunk": D.attn_decode_chunk(), "rounds": a.rounds,
+           "iters": a.iters}
+
+    # ------------------------------------------------------------------ skinny GEMM vs existing
+    def existing(x, w, bias, act):
+        M, Kd = x.shape
+        N = w.shape[0]
+        y = K.conv_fwd(x.view(M, 1, 1, Kd), w.view(N, 1, 1, Kd), 1, 1, (1, 1), (0, 0), bias=bias).view(M, N)
+        return T.gelu_fwd(y) if act == "gelu" else y
+
+    gemm = []
+    for name, N, Kd, act, has_bias in SHAPES:
+        copies = max(2, min(48, -(-(64 << 20) // (N * Kd * 2))))
+        ws = [(torch.randn(N, Kd, device=dev, generator=gen) * 0.02).to(BF) for _ in range(copies)]
+        bias = torch.randn(N, device=dev, generator=gen) if has_bias else None
+        for M in (1, 4, 8, 16):
+            x = torch.randn(M, Kd, device=dev, generator=gen).to(BF)
+            out = torch.empty(M, N, dtype=BF, device=dev)
+            ring = [ws[i % copies] for i in range(a.iters)]
+
+            def sk():
+                for w in ring:
+                    D.gemm_skinny(x, w, bias, act=act, out=out)
+
+            def ex():
+                for w in ring:
+                    existing(x, w, bias, act)
+            runs = {"skinny": graphed(sk), "existing": graphed(ex)}
+            if M == 4 and N == 768:       # the K-split sweep behind the plan of the two narrow shapes
+                for S in (1, 2, 4, 8):
+                    def sks(S=S):
+                        for w in ring:
+                            D.gemm_skinny(x, w, bias, act=act, out=out, splits=S)
+                    runs[f"skinny_splits_{S}"] = graphed(sks)
+            r = alternate(runs, a.iters)
+            floor = N * Kd * 2 / 6.3e12 * 1e6
+            gemm.append({"shape": name, "N": N, "K": Kd, "M": M, "splits": int(D.HIP.raw("kml_gemm_skinny_splits", N, Kd)),
+                         **r, "weight_floor_us_derived": round(floor, 3)})
+            print(json.dumps(gemm[-1]), file=sys.stderr, flush=True)
+        del ws
+    res["gemm"] = gemm
+
+    # ------------------------------------------------------------------ decode attention, chunk sweep
+    B, H, Lcap = 4, 12, 1024
+    kc = torch.randn(B, H, Lcap, 64, device=dev, generator=gen).to(BF)
+    vc = torch.randn(B, H, Lcap, 64, device=dev, generator=gen).to(BF)
+    q = torch.randn(B, 3 * H * 64, device=dev, generator=gen).to(BF)
+    wsb = D.attn_decode_workspace(B, H, Lcap, dev)
+    o = torch.empty(B, H * 64, dtype=BF, device=dev)
+    attn = []
+    for n in (128, 512, 1023):
+        lens = torch.full((B,), n - 1, dtype=torch.int32, device=dev)
+        runs = {}
+        for c in (64, 128, 256, 512):
+            def f(c=c):
+                for _ in range(a.iters):
+                    D.attn_decode(q, kc, vc, lens, ws=wsb, out=o, chunk=c)
+            runs[str(c)] = graphed(f)
+        r = alternate(runs, a.iters)
+        attn.append({"keys": n, "B": B, "H": H, "Lcap": Lcap, "chunk_us": r})
+        print(json.dumps(attn[-1]), file=sys.stderr, flush=True)
+    res["attention"] = attn
+
+    # ------------------------------------------------------------------ the model
+    if not a.skip_model:
+        from kubeml_amd.models.gpt import gpt2_small
+        from kubeml_amd.nn import flatten_module
+        torch.manual_seed(0)
+        model = gpt2_small(dropout=0.0).to(dev).eval()
+        flatten_module(model)
+        tr = model.transformer
+        wbytes = 2 * (sum(l.out_pad * l.in_pad for blk in tr.h
+                          for l in (blk.attn.qkv, blk.attn.out, blk.mlp.c_fc, blk.mlp.c_proj)) +
+                      model.lm_head.out_pad * model.lm_head.in_pad)
+        res["weight_bytes_per_token"] = wbytes
+        res["weight_stream_floor_us_derived"] = round(wbytes / 6.3e12 * 1e6, 2)
+        prompt, new = 128, a.new
+        routes = NM._SMALL_EXISTING
+        res["small_existing_routes"] = {f"{n}x{k}": m for (n, k), m in routes.items()}
+        decode = []
+        for Bm in (1, 4, 16):
+            ids = torch.randint(0, 50257, (Bm, prompt), device=dev, generator=gen)
+            per = {}
+            caches = {}
+            for variant in ("generate", "existing_linears"):
+                NM._SMALL_EXISTING = _Everything() if variant == "existing_linears" else routes
+                caches[variant] = model.new_cache(Bm, prompt + new, dev)
+                caches[variant].reset()
+                model.prefill(ids, None, caches[variant])
+                model.decode_step(caches[variant])       # capture under this variant's routing
+            NM._SMALL_EXISTING = routes
+            times = {v: [] for v in caches}
+            for _ in range(a.rounds):
+                for variant, cache in caches.items():
+                    cache.reset()
+                    model.prefill(ids, None, cache)
+                    torch.cuda.synchronize()
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    for _ in range(new - 1):
+                        model.decode_step(cache)
+                    e1.record()
+                    e1.synchronize()
+                    times[variant].append(e0.elapsed_time(e1) * 1e3 / (new - 1))
+            for variant, v in times.items():
+                us = statistics.median(v)
+                per[variant] = {"us_per_token_step": round(us, 2), "min": round(min(v), 2), "max": round(max(v), 2),
+                                "tokens_per_s": round(Bm / us * 1e6, 1)}
+            # whole generate() call, prefill and host loop included
+            t0 = time.perf_counter()
+            model.generate(ids, max_new_tokens=new)
+            torch.cuda.synchronize()
+            per["generate_call_s"] = round(time.perf_counter() - t0, 4)
+            if Bm == 1:
+                seq = ids.clone()
+                with torch.no_grad():
+                    model(seq)
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    for _ in range(32):
+                        z = model(seq)
+                        seq = torch.cat([seq, z[-1:, :50257].float().argmax(-1, keepdim=True)], 1)
+                    torch.cuda.synchronize()
+                us = (time.perf_counter() - t0) / 32 * 1e6
+                per["recompute"] = {"us_per_token_step": round(us, 2), "tokens_per_s": round(1e6 / us, 1), "tokens": 32}
+            decode.append({"B": Bm, "prompt": prompt, "new": new, **per})
+            print(json.dumps(decode[-1]), file=sys.stderr, flush=True)
+            del caches
+            model.__dict__.pop("_kml_decode_caches", None)
+        res["decode"] = decode
+
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
