@@ -20,19 +20,23 @@
 
 namespace {
 
-__global__ void k_sgd(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ mom,
-                      bf16_t* __restrict__ shadow, const float* __restrict__ lr_ptr, float lr_host, float wd,
-                      float momentum, float dampening, int nesterov, const float* __restrict__ first_ptr,
-                      int first_host, float grad_scale, long long n, float* __restrict__ adv_ctr,
-                      float adv_batch, float adv_n, const float* __restrict__ clip_ptr) {
-  // data-sampler counter advance (k_advance's job) folded into this launch: one thread, no
-  // other block reads the counter, the next step's augment reads it after the launch boundary
+// The data-sampler counter advance (k_advance's job) folded into an SGD launch: one thread, no
+// other block reads the counter, the next step's augment reads it after the launch boundary.
+__device__ __forceinline__ void fold_advance(float* __restrict__ adv_ctr, float adv_batch, float adv_n) {
   if (adv_ctr && blockIdx.x == 0 && threadIdx.x == 0) {
     adv_ctr[1] += 1.f;
     float st = adv_ctr[2] + adv_batch;
     if (st >= adv_n) st -= adv_n;
     adv_ctr[2] = st;
   }
+}
+
+__global__ void k_sgd(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ mom,
+                      bf16_t* __restrict__ shadow, const float* __restrict__ lr_ptr, float lr_host, float wd,
+                      float momentum, float dampening, int nesterov, const float* __restrict__ first_ptr,
+                      int first_host, float grad_scale, long long n, float* __restrict__ adv_ctr,
+                      float adv_batch, float adv_n, const float* __restrict__ clip_ptr) {
+  fold_advance(adv_ctr, adv_batch, adv_n);
   const float lr = lr_ptr ? *lr_ptr : lr_host;
   // first step after a reset (torch: momentum buffer := d, no dampening).  The flag lives
   // in device memory so a graph-captured step follows reset_state() between replays.
@@ -66,12 +70,7 @@ __global__ void k_sgd_groups(float* __restrict__ w, const float* __restrict__ g,
                              long long n, float* __restrict__ adv_ctr, float adv_batch, float adv_n,
                              const float* __restrict__ clip_ptr) {
   __shared__ float2 sh_hp[KML_MAX_GROUPS];
-  if (adv_ctr && blockIdx.x == 0 && threadIdx.x == 0) {  // the folded data-counter advance, as k_sgd
-    adv_ctr[1] += 1.f;
-    float st = adv_ctr[2] + adv_batch;
-    if (st >= adv_n) st -= adv_n;
-    adv_ctr[2] = st;
-  }
+  fold_advance(adv_ctr, adv_batch, adv_n);
   load_group_table(sh_hp, hp, G);
   const int first = first_ptr ? (*first_ptr != 0.f) : first_host;
   if (clip_ptr) grad_scale *= *clip_ptr;
@@ -339,26 +338,30 @@ KML_API int kml_memset(void* p, int value, long long bytes, hipStream_t s) {
   return (int)hipMemsetAsync(p, value, (size_t)bytes, s);
 }
 
-// max_blocks > 0 caps the grid (a range update running next to latency-bound backward
-// kernels on a side stream should take a slice of the CUs, not all of them)
+// Grid of a streaming optimizer launch over n elements, a float4 per thread.  max_blocks > 0 caps
+// it (a range update running next to latency-bound backward kernels on a side stream should take
+// a slice of the CUs, not all of them).
+static inline unsigned kml_capped_grid(long long n, int max_blocks) {
+  unsigned grid = kml_stream_grid((n + 3) / 4, 256);
+  if (max_blocks > 0 && grid > (unsigned)max_blocks) grid = (unsigned)max_blocks;
+  return grid;
+}
+
 KML_API int kml_sgd(float* w, const float* g, float* mom, bf16_t* shadow, const float* lr_ptr, float lr, float wd,
                     float momentum, float dampening, int nesterov, const float* first_ptr, int first,
                     float grad_scale, long long n, int max_blocks, float* adv_ctr, float adv_batch, float adv_n,
                     const float* clip_ptr, hipStream_t s) {
-  unsigned grid = kml_stream_grid((n + 3) / 4, 256);
-  if (max_blocks > 0 && grid > (unsigned)max_blocks) grid = (unsigned)max_blocks;
+  const unsigned grid = kml_capped_grid(n, max_blocks);
   hipLaunchKernelGGL(k_sgd, dim3(grid), dim3(256), 0, s, w, g, mom, shadow, lr_ptr, lr, wd, momentum, dampening,
                      nesterov, first_ptr, first, grad_scale, n, adv_ctr, adv_batch, adv_n, clip_ptr);
   KML_LAUNCH_CHECK();
 }
 
-// max_blocks > 0 caps the grid (a range update on a side stream beside the backward, as kml_sgd)
 KML_API int kml_adam(float* w, const float* g, float* m, float* v, bf16_t* shadow, const float* lr_ptr,
                      const float* step_ptr, float lr, float step, float b1, float b2, float eps, float wd,
                      int decoupled, float grad_scale, long long n, int max_blocks, const float* clip_ptr,
                      hipStream_t s) {
-  unsigned grid = kml_stream_grid((n + 3) / 4, 256);
-  if (max_blocks > 0 && grid > (unsigned)max_blocks) grid = (unsigned)max_blocks;
+  const unsigned grid = kml_capped_grid(n, max_blocks);
   hipLaunchKernelGGL(k_adam, dim3(grid), dim3(256), 0, s, w, g, m, v, shadow, lr_ptr,
                      step_ptr, lr, step, b1, b2, eps, wd, decoupled, grad_scale, n, clip_ptr);
   KML_LAUNCH_CHECK();
@@ -381,8 +384,7 @@ KML_API int kml_sgd_groups(float* w, const float* g, float* mom, bf16_t* shadow,
                            const float* first_ptr, int first, float grad_scale, long long n, int max_blocks,
                            float* adv_ctr, float adv_batch, float adv_n, const float* clip_ptr, hipStream_t s) {
   if (!kml_groups_ok(n, elem0, G, gid, hp, w, g, mom, shadow, nullptr)) return (int)hipErrorInvalidValue;
-  unsigned grid = kml_stream_grid((n + 3) / 4, 256);
-  if (max_blocks > 0 && grid > (unsigned)max_blocks) grid = (unsigned)max_blocks;
+  const unsigned grid = kml_capped_grid(n, max_blocks);
   hipLaunchKernelGGL(k_sgd_groups, dim3(grid), dim3(256), 0, s, w, g, mom, shadow, gid, hp, G, elem0, momentum,
                      dampening, nesterov, first_ptr, first, grad_scale, n, adv_ctr, adv_batch, adv_n, clip_ptr);
   KML_LAUNCH_CHECK();
@@ -394,8 +396,7 @@ KML_API int kml_adam_groups(float* w, const float* g, float* m, float* v, bf16_t
                             float b2, float eps, int decoupled, float grad_scale, long long n, int max_blocks,
                             const float* clip_ptr, hipStream_t s) {
   if (!m || !v || !kml_groups_ok(n, elem0, G, gid, hp, w, g, m, v, shadow)) return (int)hipErrorInvalidValue;
-  unsigned grid = kml_stream_grid((n + 3) / 4, 256);
-  if (max_blocks > 0 && grid > (unsigned)max_blocks) grid = (unsigned)max_blocks;
+  const unsigned grid = kml_capped_grid(n, max_blocks);
   hipLaunchKernelGGL(k_adam_groups, dim3(grid), dim3(256), 0, s, w, g, m, v, shadow, gid, hp, G, elem0, step_ptr,
                      step, b1, b2, eps, decoupled, grad_scale, n, clip_ptr);
   KML_LAUNCH_CHECK();

@@ -453,11 +453,7 @@ def _ride(model, space, optimizer, fwd_bwd, post, get_fold, scale):
     """make_train_step's ``ride``: SgdRider slices of each ride group armed on its host convs for
     the duration of the step's backward; the end-of-step SGD covers the remaining ranges."""
     from ..ops import kernels as K
-    g = optimizer.param_groups[0]
-    dev = space.grad.device
-    mom = optimizer._bufs(space, ["momentum"])["momentum"] if g["momentum"] != 0 else None
-    first = optimizer.first_tensor(dev) if mom is not None else None
-    lr = optimizer.lr_tensor(dev)
+    op = optimizer.sgd_operands(space)
     blocks = 512   # rider blocks per launch: measured, 32 / 64 lose, 512-1024 best
     riders, covered, seen = [], [], set()       # riders: (group, SgdRider)
     groups = model.ride_plan()
@@ -475,9 +471,9 @@ def _ride(model, space, optimizer, fwd_bwd, post, get_fold, scale):
         cuts = [lo + ((hi - lo) * i // n) // 64 * 64 for i in range(n)] + [hi]
         for i, (conv, a, b) in enumerate(zip(hosts, cuts, cuts[1:])):
             r = None if b <= a else K.SgdRider(
-                space.master[a:b], space.grad[a:b], None if mom is None else mom[a:b],
-                None if space.shadow is None else space.shadow[a:b], lr, first, g["weight_decay"], g["momentum"],
-                g["dampening"], g["nesterov"], scale, blocks)
+                space.master[a:b], space.grad[a:b], None if op.mom is None else op.mom[a:b],
+                None if space.shadow is None else space.shadow[a:b], op.lr, op.first, op.wd, op.momentum,
+                op.dampening, op.nesterov, scale, blocks)
             riders.append((gi, r))
             object.__setattr__(conv, "_kml_rider", take_for(len(riders) - 1))
     rest = ride_rest(covered, space.numel)

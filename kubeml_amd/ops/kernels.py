@@ -1697,16 +1697,21 @@ def sgd_(w, g, mom, shadow, lr, wd=0.0, momentum=0.0, dampening=0.0, nesterov=Fa
     clip_dev: fp32 device scalar multiplied into grad_scale (:func:`grad_norm_`'s ``out[2:3]``)."""
     n = w.numel()
     _chk_clip(clip_dev, w)
-    ctr, ab, an = None, 0.0, 0.0
-    if advance is not None:
-        ctr, ab, an = advance
-        _chk(ctr, F32, "ctr")
-        if ctr.numel() < 3 or ctr.device != w.device:
-            raise ValueError("advance counter must be a [3] fp32 tensor on the parameters' device")
-        ab, an = float(ab), float(an)
+    ctr, ab, an = _advance_args(advance, w)
     HIP.call("kml_sgd", "p p p p p f f f f i p i f l i p f f p s", _p(w), _p(g), _p(mom), _p(shadow), _p(lr_dev),
              float(lr), float(wd), float(momentum), float(dampening), int(nesterov), _p(first_dev), int(first),
              float(grad_scale), n, int(max_blocks), _p(ctr), ab, an, _p(clip_dev), _s())
+
+
+def _advance_args(advance, w):
+    """(ctr, batch, n) of a launch's folded data-counter advance, checked; (None, 0, 0) without one."""
+    if advance is None:
+        return None, 0.0, 0.0
+    ctr, ab, an = advance
+    _chk(ctr, F32, "ctr")
+    if ctr.numel() < 3 or ctr.device != w.device:
+        raise ValueError("advance counter must be a [3] fp32 tensor on the parameters' device")
+    return ctr, float(ab), float(an)
 
 
 def _chk_clip(clip_dev, w):
@@ -1714,6 +1719,10 @@ def _chk_clip(clip_dev, w):
         _chk(clip_dev, F32, "clip_dev")
         if clip_dev.numel() < 1 or clip_dev.device != w.device:
             raise ValueError("clip_dev must be an fp32 scalar on the parameters' device")
+
+
+def _rider_set(*args):
+    HIP.call("kml_rider_set", "p p p p p p f f f i f l i", *args)
 
 
 class SgdRider:
@@ -1738,9 +1747,9 @@ class SgdRider:
 
     def arm(self):
         """The next rider-capable launch (grouped conv backward, BN backward apply) carries this update."""
-        HIP.call("kml_rider_set", "p p p p p p f f f i f l i", _p(self.w), _p(self.g), _p(self.mom),
-                 _p(self.shadow), _p(self.lr_dev), _p(self.first_dev), self.wd, self.momentum, self.dampening,
-                 int(self.nesterov), self.grad_scale, self.w.numel(), self.blocks)
+        _rider_set(_p(self.w), _p(self.g), _p(self.mom), _p(self.shadow), _p(self.lr_dev), _p(self.first_dev),
+                   self.wd, self.momentum, self.dampening, int(self.nesterov), self.grad_scale, self.w.numel(),
+                   self.blocks)
 
     def run_alone(self):
         """The same update as its own launch (its host took a path without a rider role)."""
@@ -1751,7 +1760,7 @@ class SgdRider:
     @staticmethod
     def disarm():
         """Drop an armed rider (its host launch was not issued)."""
-        HIP.call("kml_rider_set", "p p p p p p f f f i f l i", 0, 0, 0, 0, 0, 0, 0.0, 0.0, 0.0, 0, 1.0, 0, 0)
+        _rider_set(0, 0, 0, 0, 0, 0, 0.0, 0.0, 0.0, 0, 1.0, 0, 0)
 
 
 class _Riding:
@@ -1829,13 +1838,7 @@ def sgd_groups_(w, g, mom, shadow, gid, hp, elem0=0, momentum=0.0, dampening=0.0
     G = _chk_groups("sgd_groups_", w, (("w", w, F32), ("g", g, F32), ("mom", mom, F32), ("shadow", shadow, BF16)),
                     gid, hp, elem0)
     _chk_clip(clip_dev, w)
-    ctr, ab, an = None, 0.0, 0.0
-    if advance is not None:
-        ctr, ab, an = advance
-        _chk(ctr, F32, "ctr")
-        if ctr.numel() < 3 or ctr.device != w.device:
-            raise ValueError("advance counter must be a [3] fp32 tensor on the parameters' device")
-        ab, an = float(ab), float(an)
+    ctr, ab, an = _advance_args(advance, w)
     HIP.call("kml_sgd_groups", "p p p p p p i l f f i p i f l i p f f p s", _p(w), _p(g), _p(mom), _p(shadow),
              _p(gid), _p(hp), G, int(elem0), float(momentum), float(dampening), int(nesterov), _p(first_dev),
              int(first), float(grad_scale), w.numel(), int(max_blocks), _p(ctr), ab, an, _p(clip_dev), _s())

@@ -45,6 +45,7 @@ with identical hyper-parameters, group by group.
 """
 from __future__ import annotations
 
+from collections import namedtuple
 from typing import Dict, List
 
 import torch
@@ -69,26 +70,39 @@ def _spaces(params):
     return [g for g in groups.values()], loose
 
 
+class _Tables:
+    """Device tables of the launches over one GPU flat space: the fp32 hyper-parameter table ``hp``,
+    the host ``rows`` it holds, and whatever else the class's launches index (granule bytes, chunks)."""
+
+    def __init__(self, space, rows):
+        self.space, self.rows = space, rows
+        self.hp = torch.tensor(rows, dtype=torch.float32).to(space.device)
+
+    def refresh(self, rows):
+        """hp := rows when they changed.  A capturing stream reads the table as it stands."""
+        if rows != self.rows and not torch.cuda.is_current_stream_capturing():
+            self.hp.copy_(torch.tensor(rows, dtype=torch.float32))
+            self.rows = rows
+
+
 class FusedOptimizer(torch.optim.Optimizer):
+    """The step skeleton, device scalars and tables every fused optimizer shares.  A subclass gives
+    the launches over one GPU space (:meth:`_step_space`) and their torch form (:meth:`_step_loose`)."""
     kind = "base"
     _per_group = _PER_GROUP      # the keys that may differ between this class's parameter groups
     _max_groups = MAX_GROUPS     # None: no limit (a table row per tensor, not per group)
+    _STATE_NAMES = ()            # the per-element fp32 state buffers of a flat space
+    _cpu_ranges = False          # step_range also has a torch form over a CPU flat space
 
     def __init__(self, params, defaults):
         super().__init__(params, defaults)
         self._state_bufs: Dict[int, Dict[str, torch.Tensor]] = {}
-        self._lr_dev: Dict[torch.device, torch.Tensor] = {}
+        self._scalars: Dict[tuple, torch.Tensor] = {}      # (name, device) -> fp32 device tensor
+        self._tables: Dict[int, _Tables] = {}              # id(space) -> the launches' tables
         self._grad_scale = 1.0
         self._first = True
-        self._step_dev: Dict[torch.device, torch.Tensor] = {}
-        self._first_dev: Dict[torch.device, torch.Tensor] = {}
         self._step_host = 0
-        self._max_norm_dev: Dict[torch.device, torch.Tensor] = {}
-        self._norm_out: Dict[torch.device, torch.Tensor] = {}
         self._norm_host = None     # CPU / loose-parameter path: the last step's norm
-        self._gid_dev: Dict[int, torch.Tensor] = {}    # id(space) -> uint8 group id per granule
-        self._hp_dev: Dict[int, torch.Tensor] = {}     # id(space) -> fp32 [G, 2] (lr, weight_decay)
-        self._hp_host: Dict[int, list] = {}            # id(space) -> the rows hp holds
         mgn = self.defaults.get("max_grad_norm")
         if mgn is not None and not float(mgn) > 0.0:
             raise ValueError("max_grad_norm must be a positive number or None")
@@ -120,16 +134,15 @@ class FusedOptimizer(torch.optim.Optimizer):
                 raise ValueError("a GPU optimizer with several parameter groups needs every parameter in one "
                                  "flat space (nn.flatten_module)")
 
-    def _group_rows(self):
+    def _hp_rows(self, sp):
+        """The rows of the hyper-parameter table over space ``sp``: a (lr, weight_decay) per group."""
         return [[float(g["lr"]), float(g["weight_decay"])] for g in self.param_groups]
 
     def add_param_group(self, param_group):
-        """torch's, then the checks of the constructor; the cached group tables are rebuilt."""
+        """torch's, then the checks of the constructor; the cached tables are rebuilt."""
         super().add_param_group(param_group)
-        if hasattr(self, "_gid_dev"):          # (torch's constructor adds the first groups itself)
-            self._gid_dev.clear()
-            self._hp_dev.clear()
-            self._hp_host.clear()
+        if hasattr(self, "_tables"):          # (torch's constructor adds the first groups itself)
+            self._tables.clear()
             self._check_groups()
 
     def group_ids(self, sp) -> torch.Tensor:
@@ -155,25 +168,23 @@ class FusedOptimizer(torch.optim.Optimizer):
         optimizer state.  An eager step refreshes hp when ``param_groups[k]["lr"]`` or
         ``["weight_decay"]`` were written directly (an LR scheduler); a captured step reads the
         table as it stands, so between replays use :meth:`set_lr` or call this method."""
-        key = id(sp)
-        rows = self._group_rows()
-        if key not in self._gid_dev:
+        tb = self._tables.get(id(sp))
+        rows = self._hp_rows(sp)
+        if tb is None:
             spaces, loose = self._flat_groups()
             if len(spaces) != 1 or loose or spaces[0][0] is not sp:
                 raise ValueError("a GPU optimizer with several parameter groups needs every parameter in one "
                                  "flat space")
-            self._gid_dev[key] = self.group_ids(sp).to(sp.device)
-            self._hp_dev[key] = torch.tensor(rows, dtype=torch.float32).to(sp.device)
-            self._hp_host[key] = rows
-        elif rows != self._hp_host[key] and not torch.cuda.is_current_stream_capturing():
-            self._hp_dev[key].copy_(torch.tensor(rows, dtype=torch.float32))
-            self._hp_host[key] = rows
-        return self._gid_dev[key], self._hp_dev[key]
+            tb = self._tables[id(sp)] = _Tables(sp, rows)
+            tb.gid = self.group_ids(sp).to(sp.device)
+        else:
+            tb.refresh(rows)
+        return tb.gid, tb.hp
 
     def _elem_values(self, sp, start, end):
         """(lr, weight_decay) per element of [start, end) of a CPU flat space, as fp32 vectors."""
         from ..nn.flat import ALIGN
-        hp = torch.tensor(self._group_rows(), dtype=torch.float32)
+        hp = torch.tensor(self._hp_rows(sp), dtype=torch.float32)
         idx = self.group_ids(sp).long().repeat_interleave(ALIGN)[start:end]
         return hp[idx, 0], hp[idx, 1]
 
@@ -182,25 +193,71 @@ class FusedOptimizer(torch.optim.Optimizer):
         ids = {id(p) for p in params}
         return [(g, [p for p in g["params"] if id(p) in ids]) for g in self.param_groups]
 
-    @staticmethod
-    def _check_granules(start, end):
-        if start % 64 or (end - start) % 64:
-            raise ValueError(f"a grouped step_range covers whole 64-element granules from an aligned start "
-                             f"(got [{start}, {end}))")
+    # --- device scalars -------------------------------------------------------------
+    def _scalar(self, name, device, init=0.0, n=1):
+        """Get or create this optimizer's fp32 tensor ``name`` on ``device``: [n], filled with ``init``."""
+        t = self._scalars.get((name, device))
+        if t is None:
+            t = self._scalars[(name, device)] = torch.full((n,), float(init), dtype=torch.float32, device=device)
+        return t
+
+    def _scalars_named(self, name):
+        return [t for (nm, _), t in self._scalars.items() if nm == name]
+
+    def lr_tensor(self, device):
+        """fp32 device scalar the single-group launches read the learning rate from."""
+        return self._scalar("lr", device, self.param_groups[0]["lr"])
+
+    def first_tensor(self, device):
+        """fp32 device flag: 1 until the first fused step after a reset clears it."""
+        return self._scalar("first", device, 1.0)
+
+    def step_tensor(self, device):
+        """fp32 device step count of the bias corrections, advanced inside the step."""
+        return self._scalar("step", device)
+
+    def max_norm_tensor(self, device):
+        """fp32 device scalar the norm launch reads its threshold from."""
+        return self._scalar("max_norm", device, self.param_groups[0]["max_grad_norm"])
+
+    def _norm_out_tensor(self, device):
+        """fp32 [3] scratch of the norm launch: sum of squares, norm, clip coefficient."""
+        return self._scalar("norm_out", device, n=3)
+
+    def _step_dev_inc(self, device):
+        from ..ops import kernels as K
+        t = self.step_tensor(device)
+        K.increment_(t, 1.0)
+        return t
+
+    def set_lr(self, lr):
+        """A number sets every group's LR; a sequence sets one LR per group (in group order).
+        The device scalar (group 0's LR) and the launches' tables follow, so a captured
+        step runs with the new values without re-capture."""
+        if isinstance(lr, (list, tuple)) or (isinstance(lr, torch.Tensor) and lr.dim() > 0):
+            lrs = [float(v) for v in lr]
+            if len(lrs) != len(self.param_groups):
+                raise ValueError(f"set_lr: {len(lrs)} learning rates for {len(self.param_groups)} parameter groups")
+            for g, v in zip(self.param_groups, lrs):
+                g["lr"] = v
+            lr = lrs[0]
+        else:
+            for g in self.param_groups:
+                g["lr"] = lr
+        for t in self._scalars_named("lr"):
+            t.fill_(float(lr))
+        for tb in self._tables.values():
+            tb.refresh(self._hp_rows(tb.space))
+
+    def set_grad_scale(self, s: float):
+        """Folded into the step: the DP all-reduce SUMs, the optimizer averages."""
+        self._grad_scale = float(s)
 
     # --- global-norm clipping ---------------------------------------------------------
     @property
     def clips(self) -> bool:
         """True when the step clips the global gradient norm (``max_grad_norm`` given)."""
         return self.param_groups[0].get("max_grad_norm") is not None
-
-    def max_norm_tensor(self, device):
-        """fp32 device scalar the norm launch reads its threshold from."""
-        t = self._max_norm_dev.get(device)
-        if t is None:
-            t = torch.full((1,), float(self.param_groups[0]["max_grad_norm"]), dtype=torch.float32, device=device)
-            self._max_norm_dev[device] = t
-        return t
 
     def set_max_grad_norm(self, v: float):
         """Change the clip threshold (a captured step follows it without re-capture).  Only on
@@ -211,16 +268,8 @@ class FusedOptimizer(torch.optim.Optimizer):
             raise ValueError("max_grad_norm must be a positive number")
         for g in self.param_groups:
             g["max_grad_norm"] = float(v)
-        for t in self._max_norm_dev.values():
+        for t in self._scalars_named("max_norm"):
             t.fill_(float(v))
-
-    def _norm_out_tensor(self, device):
-        """fp32 [3] scratch of the norm launch: sum of squares, norm, clip coefficient."""
-        t = self._norm_out.get(device)
-        if t is None:
-            t = torch.zeros(3, dtype=torch.float32, device=device)
-            self._norm_out[device] = t
-        return t
 
     def grad_norm_tensor(self, device=None):
         """The last step's global norm of the averaged gradient (before clipping) as a one-element
@@ -247,11 +296,6 @@ class FusedOptimizer(torch.optim.Optimizer):
         K.grad_norm_(sp.grad, out, self.max_norm_tensor(sp.device), grad_scale=self._grad_scale)
         return out[2:3]
 
-    def _no_ranges_when_clipping(self):
-        # the global norm needs the whole gradient before any element is updated
-        if self.clips:
-            raise ValueError("a clipping optimizer cannot step by ranges (the norm needs the whole gradient)")
-
     def _clip_loose(self, params):
         """torch form of the norm launch for CPU spaces / loose parameters: the coefficient
         (a python float, 1.0 when nothing clips) for gradients scaled by grad_scale."""
@@ -264,39 +308,84 @@ class FusedOptimizer(torch.optim.Optimizer):
         c = self.param_groups[0]["max_grad_norm"] / (nrm + 1e-6)
         return float(torch.clamp(c, max=1.0))
 
-    # --- device scalars -------------------------------------------------------------
-    def lr_tensor(self, device):
-        t = self._lr_dev.get(device)
-        if t is None:
-            t = torch.full((1,), float(self.param_groups[0]["lr"]), dtype=torch.float32, device=device)
-            self._lr_dev[device] = t
-        return t
+    # --- the step -----------------------------------------------------------------------
+    @torch.no_grad()
+    def step(self, closure=None, **kw):
+        """One step over every parameter.  Per GPU flat space, in this order: the space's deferred
+        gradient folds, :meth:`_begin_space`, the clip launch, :meth:`_step_space`; then
+        :meth:`_finish_step`; then the torch form over CPU spaces and loose parameters.  ``kw``:
+        what the subclass's launch does once per step (SGD's ``advance``), so space 0 alone gets it."""
+        loss = closure() if closure is not None else None
+        spaces, loose = self._flat_groups()
+        devices = []
+        for k, (sp, members) in enumerate(spaces):
+            if sp.device.type != "cuda":
+                loose += members
+                continue
+            sp.finish_grads()
+            new_device = sp.device not in devices
+            if new_device:
+                devices.append(sp.device)
+            self._begin_space(sp, new_device)
+            clip = self._clip_dev(sp, loose) if self.clips else None
+            self._step_space(sp, clip, **(kw if k == 0 else {}))
+        self._finish_step(devices)
+        if loose:
+            coef = self._clip_loose(loose) if self.clips else 1.0
+            for group, params in self._members(loose):
+                self._step_loose(group, params, self._grad_scale * coef)
+        return loss
 
-    def set_lr(self, lr):
-        """A number sets every group's LR; a sequence sets one LR per group (in group order).
-        The device scalar (group 0's LR) and the grouped launches' table follow, so a captured
-        step runs with the new values without re-capture."""
-        if isinstance(lr, (list, tuple)) or (isinstance(lr, torch.Tensor) and lr.dim() > 0):
-            lrs = [float(v) for v in lr]
-            if len(lrs) != len(self.param_groups):
-                raise ValueError(f"set_lr: {len(lrs)} learning rates for {len(self.param_groups)} parameter groups")
-            for g, v in zip(self.param_groups, lrs):
-                g["lr"] = v
-            lr = lrs[0]
-        else:
-            for g in self.param_groups:
-                g["lr"] = lr
-        for t in self._lr_dev.values():
-            t.fill_(float(lr))
-        rows = self._group_rows()
-        for key, t in self._hp_dev.items():
-            t.copy_(torch.tensor(rows, dtype=torch.float32))
-            self._hp_host[key] = rows
+    def _begin_space(self, sp, new_device):
+        """Before the launches over GPU space ``sp``; new_device: the step's first space on its device."""
 
-    def set_grad_scale(self, s: float):
-        """Folded into the step: the DP all-reduce SUMs, the optimizer averages."""
-        self._grad_scale = float(s)
+    def _step_space(self, sp, clip, **kw):
+        """The update launches over GPU space ``sp``; clip: the device clip coefficient or None."""
+        raise NotImplementedError
 
+    def _step_loose(self, group, params, scale):
+        """torch form of the update for ``params`` of ``group``, gradients scaled by ``scale``."""
+        raise NotImplementedError
+
+    def _finish_step(self, devices):
+        """After the last GPU space (``devices``: theirs): the class's host bookkeeping."""
+
+    def _clear_first(self, devices=()):
+        """End of a momentum step: the first-step flag goes down, on ``devices`` and on the host."""
+        if self.param_groups[0]["momentum"] != 0:
+            from ..ops import kernels as K
+            for dev in devices:
+                K.fill_(self.first_tensor(dev), 0.0)
+        self._first = False
+
+    # ---- per-range steps (optimizer overlapped with backward, engine/dp.py) -------------
+    def supports_ranges(self) -> bool:
+        """True when :meth:`step_range` can apply the step: every parameter lives in one flat space
+        (no loose parameters; on a GPU unless the class has a CPU range path) and nothing clips."""
+        spaces, loose = self._flat_groups()
+        return (len(spaces) == 1 and not loose and not self.clips
+                and (self._cpu_ranges or spaces[0][0].device.type == "cuda"))
+
+    def supports_shard_range(self) -> bool:
+        """One :meth:`step_range` per step over this rank's chunk (engine/dp.py shard plan)."""
+        return self.supports_ranges()
+
+    def begin_ranges(self):
+        """Start of a step applied through ``step_range`` calls (no-op unless overridden)."""
+
+    def _range_space(self, start, end):
+        """The one flat space of a ``step_range`` over [start, end), after the checks they share."""
+        if self.clips:     # the global norm needs the whole gradient before any element is updated
+            raise ValueError("a clipping optimizer cannot step by ranges (the norm needs the whole gradient)")
+        spaces, loose = self._flat_groups()
+        if len(spaces) != 1 or loose:
+            raise ValueError("step_range needs all parameters in one flat space")
+        if self.grouped and (start % 64 or (end - start) % 64):
+            raise ValueError(f"a grouped step_range covers whole 64-element granules from an aligned start "
+                             f"(got [{start}, {end}))")
+        return spaces[0][0]
+
+    # --- state --------------------------------------------------------------------------
     def _flat_groups(self):
         ps = [p for g in self.param_groups for p in g["params"]]
         return _spaces(ps)
@@ -324,23 +413,10 @@ class FusedOptimizer(torch.optim.Optimizer):
         self.state.clear()
         self._first = True
         self._step_host = 0
-        for t in self._step_dev.values():
+        for t in self._scalars_named("step"):
             t.zero_()
-        for t in self._first_dev.values():
+        for t in self._scalars_named("first"):
             t.fill_(1.0)
-
-    def first_tensor(self, device):
-        """fp32 device flag: 1 until the first fused step after a reset clears it."""
-        t = self._first_dev.get(device)
-        if t is None:
-            t = torch.ones(1, dtype=torch.float32, device=device)
-            self._first_dev[device] = t
-        return t
-
-    _STATE_NAMES = ()
-
-    def begin_ranges(self):
-        """Start of a step applied through ``step_range`` calls (no-op unless overridden)."""
 
     def prepare(self):
         """Allocate every device state buffer now (not lazily inside a first step), so
@@ -349,35 +425,57 @@ class FusedOptimizer(torch.optim.Optimizer):
         for sp, _ in spaces:
             if sp.device.type != "cuda":
                 continue
-            if self._STATE_NAMES:
-                self._bufs(sp, list(self._STATE_NAMES))
+            self.state_buffers(sp)
             self.lr_tensor(sp.device)
             self.first_tensor(sp.device)
-            self._step_dev.setdefault(sp.device, torch.zeros(1, dtype=torch.float32, device=sp.device))
+            self.step_tensor(sp.device)
             if self.clips:            # scratch of the norm launch, not optimizer state
                 self.max_norm_tensor(sp.device)
                 self._norm_out_tensor(sp.device)
-            if self.grouped:          # the grouped launches' tables: scratch as well
-                self.group_tables(sp)
+            self._prepare_tables(sp)
         return self
 
-    def state_tensors(self) -> List[torch.Tensor]:
-        """Every device tensor :meth:`step` mutates."""
-        out = [t for bufs in self._state_bufs.values() for t in bufs.values()]
-        out += list(self._step_dev.values()) + list(self._first_dev.values())
-        return out
+    def _prepare_tables(self, sp):
+        if self.grouped:          # the grouped launches' tables: scratch as well
+            self.group_tables(sp)
 
-    def _bufs(self, sp, names):
-        key = id(sp)
-        d = self._state_bufs.get(key)
+    def state_tensors(self) -> List[torch.Tensor]:
+        """Every device tensor :meth:`step` mutates: the state buffers, the step count and the
+        first-step flag (not the lr, clip or table scratch)."""
+        out = [t for bufs in self._state_bufs.values() for t in bufs.values()]
+        return out + self._scalars_named("step") + self._scalars_named("first")
+
+    def state_buffers(self, sp) -> Dict[str, torch.Tensor]:
+        """The per-element fp32 state buffers of flat space ``sp`` by name (allocated on first use)."""
+        d = self._state_bufs.get(id(sp))
         if d is None:
-            d = {n: torch.zeros(sp.numel, dtype=torch.float32, device=sp.device) for n in names}
-            self._state_bufs[key] = d
+            d = {n: torch.zeros(sp.numel, dtype=torch.float32, device=sp.device) for n in self._STATE_NAMES}
+            self._state_bufs[id(sp)] = d
         return d
+
+    def host_state(self):
+        """The host side of the step bookkeeping, for a snapshot (:meth:`load_host_state` restores it)."""
+        return self._first, self._step_host
+
+    def load_host_state(self, host):
+        self._first, self._step_host = host
+
+    @property
+    def stepped(self) -> bool:
+        """True once a step was applied since construction or the last :meth:`reset_state`."""
+        return self._step_host > 0 or not self._first
+
+
+# mom, first, lr: the momentum buffer, the first-step flag and the learning-rate scalar of the space's
+# device (the first two None without momentum); then the first parameter group's scalars
+SgdOperands = namedtuple("SgdOperands", "mom first lr wd momentum dampening nesterov")
 
 
 class SGD(FusedOptimizer):
+    """``step(advance=(ctr, batch, n))`` folds the data-counter advance into the launch (see
+    :meth:`fuse_advance`)."""
     kind = "sgd"
+    _cpu_ranges = True
 
     @property
     def _STATE_NAMES(self):
@@ -396,50 +494,40 @@ class SGD(FusedOptimizer):
         spaces, _ = self._flat_groups()
         return bool(spaces and spaces[0][0].device.type == "cuda" and ctr.device == spaces[0][0].device)
 
-    @torch.no_grad()
-    def step(self, closure=None, advance=None):
-        """advance: (ctr, batch, n) folded into this step's launch (see fuse_advance)."""
-        loss = closure() if closure is not None else None
+    def sgd_operands(self, sp) -> SgdOperands:
+        """What an SGD launch over flat space ``sp`` takes from this optimizer, for the launches that
+        carry the update themselves (the shard collective, the rider slices) as for its own."""
         g = self.param_groups[0]
-        spaces, loose = self._flat_groups()
-        for k, (sp, members) in enumerate(spaces):
-            if sp.device.type != "cuda":
-                loose += members
-                continue
-            sp.finish_grads()
-            from ..ops import kernels as K
-            mom = self._bufs(sp, ["momentum"])["momentum"] if g["momentum"] != 0 else None
-            first = self.first_tensor(sp.device) if mom is not None else None
-            clip = self._clip_dev(sp, loose) if self.clips else None
-            if self.grouped:
-                gid, hp = self.group_tables(sp)
-                K.sgd_groups_(sp.master, sp.grad, mom, sp.shadow, gid, hp, 0, momentum=g["momentum"],
-                              dampening=g["dampening"], nesterov=g["nesterov"], first=self._first,
-                              grad_scale=self._grad_scale, first_dev=first, advance=advance, clip_dev=clip)
-            else:
-                K.sgd_(sp.master, sp.grad, mom, sp.shadow, g["lr"], wd=g["weight_decay"], momentum=g["momentum"],
-                       dampening=g["dampening"], nesterov=g["nesterov"], first=self._first,
-                       grad_scale=self._grad_scale, lr_dev=self.lr_tensor(sp.device), first_dev=first,
-                       advance=advance if k == 0 else None, clip_dev=clip)
-            if first is not None:
-                K.fill_(first, 0.0)
-        if loose:
-            coef = self._clip_loose(loose) if self.clips else 1.0
-            for gr, ps in self._members(loose):
-                _torch_sgd(ps, gr, self.state, self._grad_scale * coef)
-        self._first = False
-        return loss
+        mom = self.state_buffers(sp).get("momentum")
+        first = self.first_tensor(sp.device) if mom is not None else None
+        return SgdOperands(mom, first, self.lr_tensor(sp.device), g["weight_decay"], g["momentum"], g["dampening"],
+                           g["nesterov"])
 
+    def _launch(self, sp, start, end, max_blocks, clip, advance):
+        """The one SGD launch over [start, end) of GPU space ``sp``."""
+        from ..ops import kernels as K
+        op = self.sgd_operands(sp)
+        if self.grouped and end <= start:      # nothing to launch; a folded advance still happens
+            if advance is not None:
+                K.advance_counter_(*advance)
+            return
+        w, gr, mom, shadow = (None if t is None else t[start:end] for t in (sp.master, sp.grad, op.mom, sp.shadow))
+        kw = dict(momentum=op.momentum, dampening=op.dampening, nesterov=op.nesterov, first=self._first,
+                  grad_scale=self._grad_scale, first_dev=op.first, max_blocks=max_blocks, advance=advance,
+                  clip_dev=clip)
+        if self.grouped:
+            gid, hp = self.group_tables(sp)
+            K.sgd_groups_(w, gr, mom, shadow, gid, hp, start, **kw)
+        else:
+            K.sgd_(w, gr, mom, shadow, self.param_groups[0]["lr"], wd=op.wd, lr_dev=op.lr, **kw)
 
-    # ---- per-range steps (optimizer overlapped with backward, engine/dp.py) -------------
-    def supports_ranges(self) -> bool:
-        """True when every parameter lives in one flat space (no loose parameters)."""
-        spaces, loose = self._flat_groups()
-        return len(spaces) == 1 and not loose and not self.clips
+    def _step_space(self, sp, clip, advance=None):
+        self._launch(sp, 0, sp.numel, 0, clip, advance)
 
-    def supports_shard_range(self) -> bool:
-        """One :meth:`step_range` per step over this rank's chunk (engine/dp.py shard plan)."""
-        return self.supports_ranges()
+    def _step_loose(self, group, params, scale):
+        _torch_sgd(params, group, self.state, scale)
+
+    _finish_step = FusedOptimizer._clear_first
 
     @torch.no_grad()
     def step_range(self, start: int, end: int, max_blocks: int = 0, advance_step: bool = True, advance=None):
@@ -449,50 +537,24 @@ class SGD(FusedOptimizer):
         reads the same value); the union of one step's ranges must cover the space once.
         advance_step: accepted for the ranged-step protocol (SGD keeps no step counter).
         advance: (ctr, batch, n) data-counter advance folded into this launch (as :meth:`step`)."""
-        g = self.param_groups[0]
-        self._no_ranges_when_clipping()
-        spaces, loose = self._flat_groups()
-        if len(spaces) != 1 or loose:
-            raise ValueError("step_range needs all parameters in one flat space")
-        sp = spaces[0][0]
-        mom =self._bufs(sp, ["momentum"])["momentum"] if g["momentum"] != 0 else None
-        if self.grouped:
-            self._check_granules(start, end)
+        sp = self._range_space(start, end)
         if sp.device.type != "cuda":
+            g = self.param_groups[0]
             if self.grouped:      # the same ops with each element's own lr and weight decay
                 lr, wd = self._elem_values(sp, start, end)
                 g = dict(g, lr=lr, weight_decay=wd)
-            _sgd_range_cpu(sp, start, end, g, mom, self._first, self._grad_scale)
+            _sgd_range_cpu(sp, start, end, g, self.state_buffers(sp).get("momentum"), self._first, self._grad_scale)
             return
         sp.finish_grads_range(start, end)
-        from ..ops import kernels as K
-        first = self.first_tensor(sp.device) if mom is not None else None
-        if self.grouped:
-            if end > start:
-                gid, hp = self.group_tables(sp)
-                K.sgd_groups_(sp.master[start:end], sp.grad[start:end], None if mom is None else mom[start:end],
-                              None if sp.shadow is None else sp.shadow[start:end], gid, hp, start,
-                              momentum=g["momentum"], dampening=g["dampening"], nesterov=g["nesterov"],
-                              first=self._first, grad_scale=self._grad_scale, first_dev=first,
-                              max_blocks=max_blocks or _RANGE_BLOCKS, advance=advance)
-            elif advance is not None:
-                K.advance_counter_(*advance)
-            return
-        K.sgd_(sp.master[start:end], sp.grad[start:end], None if mom is None else mom[start:end],
-               None if sp.shadow is None else sp.shadow[start:end], g["lr"], wd=g["weight_decay"],
-               momentum=g["momentum"], dampening=g["dampening"], nesterov=g["nesterov"], first=self._first,
-               grad_scale=self._grad_scale, lr_dev=self.lr_tensor(sp.device), first_dev=first,
-               max_blocks=max_blocks or _RANGE_BLOCKS, advance=advance)
+        self._launch(sp, start, end, max_blocks or _RANGE_BLOCKS, None, advance)
 
     @torch.no_grad()
     def finish_ranges(self):
         """End of a step applied through :meth:`step_range`: clear the first-step flag."""
         spaces, _ = self._flat_groups()
-        sp = spaces[0][0]
-        if self.param_groups[0]["momentum"] != 0 and sp.device.type == "cuda":
-            from ..ops import kernels as K
-            K.fill_(self.first_tensor(sp.device), 0.0)
-        self._first = False
+        dev = spaces[0][0].device
+        self._clear_first([dev] if dev.type == "cuda" else [])
+
 
 # grid cap of a range update (it runs beside the backward on a side stream)
 _RANGE_BLOCKS = 64
@@ -552,53 +614,42 @@ class Adam(FusedOptimizer):
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
                                       max_grad_norm=max_grad_norm))
 
-    def step_tensor(self, device):
-        t = self._step_dev.get(device)
-        if t is None:
-            t = torch.zeros(1, dtype=torch.float32, device=device)
-            self._step_dev[device] = t
-        return t
-
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = closure() if closure is not None else None
+    def _launch(self, sp, start, end, max_blocks, clip):
+        """The one Adam launch over [start, end) of GPU space ``sp`` (none over an empty range)."""
+        from ..ops import kernels as K
         g = self.param_groups[0]
         b1, b2 = g["betas"]
-        spaces, loose = self._flat_groups()
-        self._step_host += 1
-        for sp, members in spaces:
-            if sp.device.type != "cuda":
-                loose += members
-                continue
-            sp.finish_grads()
-            from ..ops import kernels as K
-            st = self._step_dev_inc(sp.device)
-            bufs = self._bufs(sp, ["exp_avg", "exp_avg_sq"])
-            clip = self._clip_dev(sp, loose) if self.clips else None
-            if self.grouped:
-                gid, hp = self.group_tables(sp)
-                K.adam_groups_(sp.master, sp.grad, bufs["exp_avg"], bufs["exp_avg_sq"], sp.shadow, gid, hp, 0.0, 0,
-                               b1, b2, g["eps"], self.decoupled, self._grad_scale, step_dev=st, clip_dev=clip)
-            else:
-                K.adam_(sp.master, sp.grad, bufs["exp_avg"], bufs["exp_avg_sq"], sp.shadow, g["lr"], 0.0, b1, b2,
-                        g["eps"], g["weight_decay"], self.decoupled, self._grad_scale,
-                        lr_dev=self.lr_tensor(sp.device), step_dev=st, clip_dev=clip)
-        if loose:
-            coef = self._clip_loose(loose) if self.clips else 1.0
-            for gr, ps in self._members(loose):
-                _torch_adam(ps, gr, self.state, self._grad_scale * coef, self.decoupled)
-        return loss
+        bufs = self.state_buffers(sp)
+        if end <= start:
+            return
+        w, gr, m, v, shadow = (None if t is None else t[start:end]
+                               for t in (sp.master, sp.grad, bufs["exp_avg"], bufs["exp_avg_sq"], sp.shadow))
+        kw = dict(step_dev=self.step_tensor(sp.device), max_blocks=max_blocks, clip_dev=clip)
+        if self.grouped:
+            gid, hp = self.group_tables(sp)
+            K.adam_groups_(w, gr, m, v, shadow, gid, hp, 0.0, start, b1, b2, g["eps"], self.decoupled,
+                           self._grad_scale, **kw)
+        else:
+            K.adam_(w, gr, m, v, shadow, g["lr"], 0.0, b1, b2, g["eps"], g["weight_decay"], self.decoupled,
+                    self._grad_scale, lr_dev=self.lr_tensor(sp.device), **kw)
 
-    def supports_ranges(self) -> bool:
-        """Per-backward-stage updates (engine/dp.py ``opt_overlap``): :meth:`begin_ranges`
-        advances the bias-correction step once, then every stage's :meth:`step_range` runs with
-        ``advance_step=False``, so a step split into ranges equals one whole step."""
-        spaces, loose = self._flat_groups()
-        return len(spaces) == 1 and not loose and spaces[0][0].device.type == "cuda" and not self.clips
+    def _begin_space(self, sp, new_device):
+        self._step_dev_inc(sp.device)
+
+    def _step_space(self, sp, clip):
+        self._launch(sp, 0, sp.numel, 0, clip)
+
+    def _step_loose(self, group, params, scale):
+        _torch_adam(params, group, self.state, scale, self.decoupled)
+
+    def _finish_step(self, devices):
+        self._step_host += 1
 
     @torch.no_grad()
     def begin_ranges(self):
-        """Start of a step applied as several ranges: advance the step counter once."""
+        """Start of a step applied as several ranges (engine/dp.py ``opt_overlap``): advance the
+        bias-correction step once; every stage's :meth:`step_range` then runs with
+        ``advance_step=False``, so a step split into ranges equals one whole step."""
         spaces, _ = self._flat_groups()
         self._step_host += 1
         self._step_dev_inc(spaces[0][0].device)
@@ -606,53 +657,18 @@ class Adam(FusedOptimizer):
     def finish_ranges(self):
         """End of a ranged step (nothing to clear: the counter advanced in begin_ranges)."""
 
-    def supports_shard_range(self) -> bool:
-        """One :meth:`step_range` per step over this rank's chunk (engine/dp.py shard plan)."""
-        spaces, loose = self._flat_groups()
-        return len(spaces) == 1 and not loose and spaces[0][0].device.type == "cuda" and not self.clips
-
     @torch.no_grad()
     def step_range(self, start: int, end: int, max_blocks: int = 0, advance_step: bool = True):
         """The fused step over flat elements [start, end) only.  advance_step=True (a sharded
         update: this rank owns that chunk of the master and its moments, one range per step)
         advances the step counter; False (one of several stage ranges of a step, after
         :meth:`begin_ranges`) reuses it."""
-        g = self.param_groups[0]
-        b1, b2 = g["betas"]
-        self._no_ranges_when_clipping()
-        if self.grouped:
-            self._check_granules(start, end)
-        spaces, loose = self._flat_groups()
-        if len(spaces) != 1 or loose:
-            raise ValueError("step_range needs all parameters in one flat space")
-        sp = spaces[0][0]
-        from ..ops import kernels as K
+        sp = self._range_space(start, end)
         if advance_step:
             self._step_host += 1
-            st = self._step_dev_inc(sp.device)
-        else:
-            st = self.step_tensor(sp.device)
+            self._step_dev_inc(sp.device)
         sp.finish_grads_range(start, end)
-        bufs = self._bufs(sp, ["exp_avg", "exp_avg_sq"])
-        if self.grouped:
-            if end > start:
-                gid, hp = self.group_tables(sp)
-                K.adam_groups_(sp.master[start:end], sp.grad[start:end], bufs["exp_avg"][start:end],
-                               bufs["exp_avg_sq"][start:end], None if sp.shadow is None else sp.shadow[start:end],
-                               gid, hp, 0.0, start, b1, b2, g["eps"], self.decoupled, self._grad_scale, step_dev=st,
-                               max_blocks=max_blocks or (0 if advance_step else _RANGE_BLOCKS))
-        elif end > start:
-            K.adam_(sp.master[start:end], sp.grad[start:end], bufs["exp_avg"][start:end],
-                    bufs["exp_avg_sq"][start:end], None if sp.shadow is None else sp.shadow[start:end], g["lr"], 0.0,
-                    b1, b2, g["eps"], g["weight_decay"], self.decoupled, self._grad_scale,
-                    lr_dev=self.lr_tensor(sp.device), step_dev=st,
-                    max_blocks=max_blocks or (0 if advance_step else _RANGE_BLOCKS))
-
-    def _step_dev_inc(self, device):
-        from ..ops import kernels as K
-        t = self.step_tensor(device)
-        K.increment_(t, 1.0)
-        return t
+        self._launch(sp, start, end, max_blocks or (0 if advance_step else _RANGE_BLOCKS), None)
 
 
 class AdamW(Adam):

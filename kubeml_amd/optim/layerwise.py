@@ -35,14 +35,9 @@ from typing import Dict
 
 import torch
 
-from . import FusedOptimizer
+from . import FusedOptimizer, _Tables
 
 __all__ = ["LAMB", "LARS", "layerwise_groups"]
-
-
-class _Tables:
-    """Device tables and scratch of the layer-wise launches over one GPU flat space."""
-    __slots__ = ("chunks", "ranges", "hp", "part", "ratio", "rows")
 
 
 def _ratio(adapt, wn, other, value):
@@ -61,11 +56,10 @@ class _Layerwise(FusedOptimizer):
 
     def __init__(self, params, defaults):
         super().__init__(params, defaults)
-        self._lw: Dict[int, _Tables] = {}          # id(space) -> tables
         self._ratios_host: Dict[int, float] = {}   # CPU / loose path: id(p) -> last ratio
 
     # --- per-tensor table ---------------------------------------------------------------
-    def _tensor_rows(self, sp):
+    def _hp_rows(self, sp):
         """One (lr, weight_decay, adapt, 0) per tensor of ``sp``, in the space's parameter order.  A
         tensor of the space in no group of this optimizer gets zeros: its weights do not move."""
         of = {}
@@ -80,35 +74,18 @@ class _Layerwise(FusedOptimizer):
         state).  An eager step refreshes the hyper-parameter rows when ``param_groups`` were written
         directly; a captured step reads them as they stand, so between replays use :meth:`set_lr`."""
         from ..ops import kernels as K
-        tb = self._lw.get(id(sp))
-        rows = self._tensor_rows(sp)
+        tb = self._tables.get(id(sp))
+        rows = self._hp_rows(sp)
         if tb is None:
-            tb = _Tables()
+            tb = self._tables[id(sp)] = _Tables(sp, rows)
             tb.chunks, tb.ranges = K.layer_tables(sp.offsets, sp.numel, sp.device)
-            tb.hp = torch.tensor(rows, dtype=torch.float32).to(sp.device)
             tb.part = torch.zeros(2 * tb.chunks.shape[0], dtype=torch.float32, device=sp.device)
             tb.ratio = torch.ones(len(rows), dtype=torch.float32, device=sp.device)
-            tb.rows = rows
-            self._lw[id(sp)] = tb
-        elif rows != tb.rows and not torch.cuda.is_current_stream_capturing():
-            tb.hp.copy_(torch.tensor(rows, dtype=torch.float32))
-            tb.rows = rows
+        else:
+            tb.refresh(rows)
         return tb
 
-    def add_param_group(self, param_group):
-        super().add_param_group(param_group)
-        if hasattr(self, "_lw"):
-            self._lw.clear()
-
-    def set_lr(self, lr):
-        super().set_lr(lr)
-        spaces, _ = self._flat_groups()
-        for sp, _ in spaces:
-            tb = self._lw.get(id(sp))
-            if tb is not None:
-                rows = self._tensor_rows(sp)
-                tb.hp.copy_(torch.tensor(rows, dtype=torch.float32))
-                tb.rows = rows
+    _prepare_tables = layer_tables
 
     def trust_ratios(self) -> torch.Tensor:
         """The last step's trust ratio of every tensor as one fp32 tensor: on a GPU the device tensor
@@ -123,35 +100,8 @@ class _Layerwise(FusedOptimizer):
         ps = [p for g in self.param_groups for p in g["params"]]
         return torch.tensor([self._ratios_host.get(id(p), 1.0) for p in ps], dtype=torch.float32)
 
-    # --- device scalars -----------------------------------------------------------------
-    def step_tensor(self, device):
-        t = self._step_dev.get(device)
-        if t is None:
-            t = torch.zeros(1, dtype=torch.float32, device=device)
-            self._step_dev[device] = t
-        return t
-
-    def prepare(self):
-        spaces, _ = self._flat_groups()
-        for sp, _ in spaces:
-            if sp.device.type != "cuda":
-                continue
-            if self._STATE_NAMES:
-                self._bufs(sp, list(self._STATE_NAMES))
-            self.lr_tensor(sp.device)
-            self.first_tensor(sp.device)
-            self.step_tensor(sp.device)
-            if self.clips:
-                self.max_norm_tensor(sp.device)
-                self._norm_out_tensor(sp.device)
-            self.layer_tables(sp)
-        return self
-
     # --- no ranged steps: a tensor's norms need all of its gradient -------------------------
     def supports_ranges(self) -> bool:
-        return False
-
-    def supports_shard_range(self) -> bool:
         return False
 
     def step_range(self, *a, **k):
@@ -167,36 +117,27 @@ class LAMB(_Layerwise):
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, adapt=adapt,
                                       max_grad_norm=max_grad_norm))
 
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = closure() if closure is not None else None
+    def _begin_space(self, sp, new_device):
+        if new_device:          # one count per device, whatever its spaces
+            self._step_dev_inc(sp.device)
+
+    def _step_space(self, sp, clip):
+        from ..ops import kernels as K
         g = self.param_groups[0]
         b1, b2 = g["betas"]
-        spaces, loose = self._flat_groups()
+        st = self.step_tensor(sp.device)
+        bufs = self.state_buffers(sp)
+        tb = self.layer_tables(sp)
+        K.lamb_moments_(sp.master, sp.grad, bufs["exp_avg"], bufs["exp_avg_sq"], tb.chunks, tb.ranges, tb.hp,
+                        tb.part, tb.ratio, 0.0, b1, b2, g["eps"], self._grad_scale, step_dev=st, clip_dev=clip)
+        K.lamb_apply_(sp.master, bufs["exp_avg"], bufs["exp_avg_sq"], sp.shadow, tb.chunks, tb.hp, tb.ratio, 0.0,
+                      b1, b2, g["eps"], step_dev=st)
+
+    def _step_loose(self, group, params, scale):
+        _torch_lamb(params, group, self.state, scale, self._ratios_host)
+
+    def _finish_step(self, devices):
         self._step_host += 1
-        stepped = set()
-        for sp, members in spaces:
-            if sp.device.type != "cuda":
-                loose += members
-                continue
-            sp.finish_grads()
-            from ..ops import kernels as K
-            st = self.step_tensor(sp.device)
-            if sp.device not in stepped:          # one count per device, whatever its spaces
-                K.increment_(st, 1.0)
-                stepped.add(sp.device)
-            bufs = self._bufs(sp, ["exp_avg", "exp_avg_sq"])
-            clip = self._clip_dev(sp, loose) if self.clips else None
-            tb = self.layer_tables(sp)
-            K.lamb_moments_(sp.master, sp.grad, bufs["exp_avg"], bufs["exp_avg_sq"], tb.chunks, tb.ranges, tb.hp,
-                            tb.part, tb.ratio, 0.0, b1, b2, g["eps"], self._grad_scale, step_dev=st, clip_dev=clip)
-            K.lamb_apply_(sp.master, bufs["exp_avg"], bufs["exp_avg_sq"], sp.shadow, tb.chunks, tb.hp, tb.ratio, 0.0,
-                          b1, b2, g["eps"], step_dev=st)
-        if loose:
-            coef = self._clip_loose(loose) if self.clips else 1.0
-            for gr, ps in self._members(loose):
-                _torch_lamb(ps, gr, self.state, self._grad_scale * coef, self._ratios_host)
-        return loss
 
 
 class LARS(_Layerwise):
@@ -212,37 +153,23 @@ class LARS(_Layerwise):
                                       nesterov=nesterov, trust_coefficient=trust_coefficient, eps=eps, adapt=adapt,
                                       max_grad_norm=max_grad_norm))
 
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = closure() if closure is not None else None
+    def _step_space(self, sp, clip):
+        from ..ops import kernels as K
         g = self.param_groups[0]
-        spaces, loose = self._flat_groups()
-        for sp, members in spaces:
-            if sp.device.type != "cuda":
-                loose += members
-                continue
-            sp.finish_grads()
-            from ..ops import kernels as K
-            mom = self._bufs(sp, ["momentum"])["momentum"] if g["momentum"] != 0 else None
-            first = self.first_tensor(sp.device) if mom is not None else None
-            clip = self._clip_dev(sp, loose) if self.clips else None
-            tb = self.layer_tables(sp)
-            K.lars_norms_(sp.master, sp.grad, tb.chunks, tb.ranges, tb.hp, tb.part, tb.ratio,
-                          trust_coefficient=g["trust_coefficient"], eps=g["eps"], grad_scale=self._grad_scale,
-                          clip_dev=clip)
-            K.lars_apply_(sp.master, sp.grad, mom, sp.shadow, tb.chunks, tb.hp, tb.ratio, momentum=g["momentum"],
-                          dampening=g["dampening"], nesterov=g["nesterov"], first=self._first,
-                          grad_scale=self._grad_scale, first_dev=first, clip_dev=clip)
-        for dev, first in self._first_dev.items():
-            if dev.type == "cuda" and g["momentum"] != 0:
-                from ..ops import kernels as K
-                K.fill_(first, 0.0)
-        if loose:
-            coef = self._clip_loose(loose) if self.clips else 1.0
-            for gr, ps in self._members(loose):
-                _torch_lars(ps, gr, self.state, self._grad_scale * coef, self._ratios_host)
-        self._first = False
-        return loss
+        mom = self.state_buffers(sp).get("momentum")
+        first = self.first_tensor(sp.device) if mom is not None else None
+        tb = self.layer_tables(sp)
+        K.lars_norms_(sp.master, sp.grad, tb.chunks, tb.ranges, tb.hp, tb.part, tb.ratio,
+                      trust_coefficient=g["trust_coefficient"], eps=g["eps"], grad_scale=self._grad_scale,
+                      clip_dev=clip)
+        K.lars_apply_(sp.master, sp.grad, mom, sp.shadow, tb.chunks, tb.hp, tb.ratio, momentum=g["momentum"],
+                      dampening=g["dampening"], nesterov=g["nesterov"], first=self._first,
+                      grad_scale=self._grad_scale, first_dev=first, clip_dev=clip)
+
+    def _step_loose(self, group, params, scale):
+        _torch_lars(params, group, self.state, scale, self._ratios_host)
+
+    _finish_step = FusedOptimizer._clear_first
 
 
 def _torch_lamb(params, g, state, grad_scale, ratios):

@@ -478,18 +478,13 @@ class PeerShard:
         nesterov = 0
         if fused:
             _one_group(optimizer)
-            g = optimizer.param_groups[0]
-            wd, momentum, dampening, nesterov = g["weight_decay"], g["momentum"], g["dampening"], int(g["nesterov"])
-            lr = optimizer.lr_tensor(sp.device)
-            if momentum != 0:
-                mom = optimizer._bufs(sp, ["momentum"])["momentum"]
-                first = optimizer.first_tensor(sp.device)
+            mom, first, lr, wd, momentum, dampening, nesterov = optimizer.sgd_operands(sp)
         ctr, ab, an = advance if advance is not None else (None, 0.0, 0.0)
         HIP.call("kml_zs_reduce_scatter", "p p p p i i l l i p p p p f f f i p f p f f i d i p s",
                  ctypes.addressof(self._flags), ctypes.addressof(self._grads), self.region, self.ctrl, self.rank,
                  self.world, int(lo), int(hi), int(fused), sp.master.data_ptr() if fused else None,
                  mom.data_ptr() if mom is not None else None, sp.shadow.data_ptr() if fused else None,
-                 lr.data_ptr() if lr is not None else None, float(wd), float(momentum), float(dampening), nesterov,
+                 lr.data_ptr() if lr is not None else None, float(wd), float(momentum), float(dampening), int(nesterov),
                  first.data_ptr() if first is not None else None, 1.0 / self.world,
                  ctr.data_ptr() if ctr is not None else None, float(ab), float(an), int(max_blocks),
                  self.timeout_s, int(self.split), stamp, self._stream())
@@ -582,15 +577,10 @@ class PeerShard:
             a, b, nv = lo - s0, hi - s0, (hi - lo) // 4
             data = arr(*[int(v) + 4 * s0 for v in self._grads])
             _one_group(optimizer)
-            g = optimizer.param_groups[0]
-            lr = optimizer.lr_tensor(sp.device)
-            mom = first = None
-            if g["momentum"] != 0:
-                mom = optimizer._bufs(sp, ["momentum"])["momentum"]
-                first = optimizer.first_tensor(sp.device)
-            sgd = dict(w=sp.master.data_ptr() + 4 * s0, mom=None if mom is None else mom.data_ptr() + 4 * s0,
-                       lr=lr, first=first, wd=g["weight_decay"], momentum=g["momentum"], dampening=g["dampening"],
-                       nesterov=int(g["nesterov"]), grad_scale=1.0 / self.world)
+            op = optimizer.sgd_operands(sp)
+            sgd = dict(w=sp.master.data_ptr() + 4 * s0, mom=None if op.mom is None else op.mom.data_ptr() + 4 * s0,
+                       lr=op.lr, first=op.first, wd=op.wd, momentum=op.momentum, dampening=op.dampening,
+                       nesterov=int(op.nesterov), grad_scale=1.0 / self.world)
             ready, wait, done, word, adv = 2 * seg + 1, 2 * seg + 1, 2 * seg + 2, 5 + seg, 0
         elif kind == "ag":
             a, b = ch, s1 - s0
@@ -713,9 +703,7 @@ class PeerShard:
         step)."""
         sp = self.space
         g = optimizer.param_groups[0]
-        mom = optimizer._bufs(sp, ["momentum"])["momentum"] if g["momentum"] != 0 else None
-        lr = optimizer.lr_tensor(sp.device)
-        first = optimizer.first_tensor(sp.device) if mom is not None else None
+        mom, first, lr = optimizer.sgd_operands(sp)[:3]
         keep = [sp.grad, sp.shadow, sp.master, lr] + ([mom, first] if mom is not None else [])
         saved = [t.clone() for t in keep]
         ok = True

@@ -438,15 +438,10 @@ class KubeModel(ABC):
         zeroes the rest and one SUM all-reduce per state buffer gives all ranks the owners'
         values (a no-op collective when the state is already replicated)."""
         sh = self._shards.get(id(comm))
-        if sh is None or sh.region is None or self._flat is None or not hasattr(self.optimizer, "_bufs"):
+        if sh is None or sh.region is None or self._flat is None or not hasattr(self.optimizer, "state_buffers"):
             return
-        names = list(getattr(self.optimizer, "_STATE_NAMES", ()) or ())
-        if not names:
-            return
-        bufs = self.optimizer._bufs(self._flat, names)
         owned = sh.owned()
-        for name in names:
-            t = bufs[name]
+        for t in self.optimizer.state_buffers(self._flat).values():
             keep = torch.zeros_like(t)
             for lo, hi in owned:
                 keep[lo:hi].copy_(t[lo:hi])
@@ -592,7 +587,7 @@ class KubeModel(ABC):
                 # keys are the parameters themselves: copy the values, never the keys
                 st = {k: ({n: (v.detach().clone() if torch.is_tensor(v) else copy.copy(v)) for n, v in d.items()}
                           if isinstance(d, dict) else d) for k, d in opt.state.items()}
-                host = (st, getattr(opt, "_first", None), getattr(opt, "_step_host", None))
+                host = (st, opt.host_state())
             else:
                 host = copy.deepcopy(opt.state_dict())
         seen, uniq = set(), []
@@ -614,10 +609,7 @@ class KubeModel(ABC):
         if hasattr(opt, "state_tensors"):
             opt.state.clear()
             opt.state.update(host[0])
-            if host[1] is not None:
-                opt._first = host[1]
-            if host[2] is not None:
-                opt._step_host = host[2]
+            opt.load_host_state(host[1])
         else:
             opt.load_state_dict(host)
 
@@ -715,7 +707,7 @@ class KubeModel(ABC):
             if self._step_max_norm is not None:
                 self._step_max_norm = float(v)
             return False
-        if opt._step_host > 0 or not opt._first:
+        if opt.stepped:
             raise ValueError("step(max_grad_norm=) on an optimizer that already stepped without clipping: "
                              "pass it from the first step, or build the optimizer with max_grad_norm=")
         from ..optim import with_max_grad_norm

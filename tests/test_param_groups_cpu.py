@@ -241,3 +241,37 @@ def test_step_builder_keeps_grouped_sgd_off_the_scalar_routes():
     _one_group(one)
     with pytest.raises(ValueError):
         _one_group(two)
+
+
+def test_sgd_operands_and_state_tensors():
+    """The accessor hands out what the optimizer's own launches use, and state_tensors() stays the set
+    a graph snapshot restores: state buffers, step count and first flag, never lr or clip scratch."""
+    from kubeml_amd.nn import flatten_module
+    from kubeml_amd.optim import SGD
+    torch.manual_seed(0)
+    net = torch.nn.ParameterList([torch.nn.Parameter(torch.randn(n)) for n in (5, 64, 130)])
+    space = flatten_module(net)
+    assert space.numel == 320            # 64-aligned regions: 64 + 64 + 192
+    cpu = torch.device("cpu")
+    opt = SGD(net.parameters(), lr=0.1, momentum=0.9, weight_decay=0.01, nesterov=True)
+    op = opt.sgd_operands(space)
+    assert op.mom is opt.state_buffers(space)["momentum"] and op.mom.numel() == 320
+    assert op.lr is opt.lr_tensor(cpu) and float(op.lr) == pytest.approx(0.1)
+    assert op.first is opt.first_tensor(cpu) and float(op.first) == 1.0
+    assert tuple(op[3:]) == (0.01, 0.9, 0.0, True)
+    space.grad.copy_(torch.randn(320))
+    d = space.grad.add(space.master.detach(), alpha=0.01)
+    opt.step_range(0, 320)               # the first step writes the buffer the accessor returned: buf := d
+    assert opt.sgd_operands(space).mom is op.mom and torch.equal(op.mom, d)
+    plain = SGD(net.parameters(), lr=0.2)
+    op0 = plain.sgd_operands(space)
+    assert op0.mom is None and op0.first is None
+    assert op0.lr is plain.lr_tensor(cpu) and tuple(op0[3:]) == (0.0, 0.0, 0.0, False)
+
+    clip = SGD(net.parameters(), lr=0.1, momentum=0.9, max_grad_norm=1.0)
+    op = clip.sgd_operands(space)
+    scratch = [op.lr, clip.max_norm_tensor(cpu), clip._norm_out_tensor(cpu)]
+    clip.prepare()
+    held = {t.data_ptr() for t in clip.state_tensors()}
+    assert {op.mom.data_ptr(), op.first.data_ptr()} <= held
+    assert not held & {t.data_ptr() for t in scratch}
