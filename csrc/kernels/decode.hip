@@ -7,6 +7,8 @@
 //                       are the second MFMA operand, K split over waves and blocks, folded in order
 //   kml_embed2_at       word[ids[b]] + pos[lens[b]]
 //   kml_decode_advance  greedy / Gumbel-max token choice, eos bookkeeping, lens and step advance
+//   kml_decode_sample   the same choice after a repetition penalty, top-k and top-p (nucleus)
+//                       filtering of the row, every parameter read from device memory
 // Sequence lengths, the sampling temperature, seed, step and eos live in device memory, so one
 // captured step replays for every token.  No float atomics anywhere: every reduction has a fixed
 // order (lane butterflies, wave order in LDS, chunk / split order in the fold).
@@ -314,6 +316,34 @@ __global__ __launch_bounds__(64) void k_embed2_at(const long long* __restrict__ 
 // One block per sequence.  Key of column c: logit (greedy) or logit / T + Gumbel(u), u a 23-bit
 // uniform in (0, 1) from hash(seed ^ mix(b), step, c).  Largest key wins, lowest column on ties.
 // Every block reads the step before its ticket; the last one advances it.
+__device__ __forceinline__ float gumbel_key(float v, float invT, unsigned sb, unsigned step, unsigned c) {
+  // (k + 1/2) 2^-23, k < 2^23: exact in fp32, never 0 or 1
+  const float u = ((float)(hash3(sb, step, c) >> 9) + 0.5f) * 1.1920928955078125e-7f;
+  return fmaf(v, invT, -logf(-logf(u)));
+}
+
+// What one thread of block b does with the chosen column: eos, tokens, lens; the last block
+// of the grid advances the step.
+__device__ __forceinline__ void advance_tail(int b, int bi, int classes, int eos, unsigned step, int* __restrict__ ctl,
+                                             long long* __restrict__ next_ids, long long* __restrict__ tokens,
+                                             int* __restrict__ lens, int* __restrict__ finished, int Lcap,
+                                             unsigned* __restrict__ ticket) {
+  if (bi >= classes) bi = 0;   // a row without one comparable value (all NaN)
+  long long tok = bi;
+  if (eos >= 0 && finished[b]) tok = eos;
+  if (eos >= 0 && tok == eos) finished[b] = 1;
+  const int len = lens[b];
+  next_ids[b] = tok;
+  if (len >= -1 && len + 1 < Lcap) tokens[(long long)b * Lcap + len + 1] = tok;
+  lens[b] = len + 1 < Lcap ? (len + 1 < 0 ? 0 : len + 1) : Lcap - 1;
+  __threadfence();
+  const unsigned tk = atomicAdd(ticket, 1u);
+  if (tk == gridDim.x - 1) {
+    ctl[1] = (int)(step + 1u);
+    atomicExch(ticket, 0u);
+  }
+}
+
 __global__ __launch_bounds__(256) void k_decode_advance(const bf16_t* __restrict__ logits, int ldl, int classes,
                                                         int sample, const float* __restrict__ temp,
                                                         int* __restrict__ ctl, long long* __restrict__ next_ids,
@@ -337,11 +367,7 @@ __global__ __launch_bounds__(256) void k_decode_advance(const bf16_t* __restrict
     for (int k = 0; k < 8; ++k) {
       const int c = c0 + k;
       float v = f[k];
-      if (sample) {
-        // (k + 1/2) 2^-23, k < 2^23: exact in fp32, never 0 or 1
-        const float u = ((float)(hash3(sb, step, (unsigned)c) >> 9) + 0.5f) * 1.1920928955078125e-7f;
-        v = fmaf(v, invT, -logf(-logf(u)));
-      }
+      if (sample) v = gumbel_key(v, invT, sb, step, (unsigned)c);
       if (c < classes && (v > best || (v == best && c < bi))) { best = v; bi = c; }
     }
   }
@@ -356,20 +382,252 @@ __global__ __launch_bounds__(256) void k_decode_advance(const bf16_t* __restrict
   if (tid != 0) return;
   for (int k = 1; k < 4; ++k)
     if (sv[k] > best || (sv[k] == best && si[k] < bi)) { best = sv[k]; bi = si[k]; }
-  if (bi >= classes) bi = 0;   // a row without one comparable value (all NaN)
-  long long tok = bi;
-  if (eos >= 0 && finished[b]) tok = eos;
-  if (eos >= 0 && tok == eos) finished[b] = 1;
-  const int len = lens[b];
-  next_ids[b] = tok;
-  if (len >= -1 && len + 1 < Lcap) tokens[(long long)b * Lcap + len + 1] = tok;
-  lens[b] = len + 1 < Lcap ? (len + 1 < 0 ? 0 : len + 1) : Lcap - 1;
-  __threadfence();
-  const unsigned tk = atomicAdd(ticket, 1u);
-  if (tk == gridDim.x - 1) {
-    ctl[1] = (int)(step + 1u);
-    atomicExch(ticket, 0u);
+  advance_tail(b, bi, classes, eos, step, ctl, next_ids, tokens, lens, finished, Lcap, ticket);
+}
+
+// ------------------------------------------------------------------ next token, filtered
+// kml_decode_sample: k_decode_advance's choice after HF's processor chain on the row —
+// repetition penalty, (temperature,) top-k, top-p — in one launch, one block of 1024 threads per
+// sequence.  fpar = [temperature, top_p, penalty, fp32(1 / penalty)], ipar = [top_k].
+//
+// After the penalty a logit is a bf16 again, one of 65536 values, so selection is exact counting:
+//   1. bitmap of the distinct ids in tokens[b, 0 .. lens[b]] (LDS, integer or);
+//   2. histogram of the penalised row over a monotone 16-bit key (-0 folded into +0, NaN left
+//      out): 65536 16-bit counts, two to a dword (a count is at most `classes` <= 65535);
+//   3. thread t owns the 64 keys 65535 - 64 t .. 65472 - 64 t: block scans over the threads walk
+//      the value classes in descending order.  Counts give the maximum and the k-th largest
+//      value; the mass of a class is count * round(2^46 * exp2((v - vmax) log2e / T)) as a
+//      64-bit integer (fp64 exp2; the sum over a row stays under 2^62), so the prefix masses
+//      and the p * Z crossing do not depend on any order of arrival;
+//   4. a second pass over the row picks the largest key among the columns at or above the
+//      threshold value.
+// The histogram is stored transposed (dword j of chunk ch at j * 1024 + ch) so that the
+// per-thread walks of consecutive threads fall on consecutive banks.
+// info[b] = [threshold value, kept columns, kept mass / mass of all non-NaN columns, vmax].
+constexpr int SMP_THREADS = 1024;
+constexpr int SMP_MAX_CLASSES = 65535;   // 16-bit counts; the id bitmap covers 65536 bits
+constexpr int SMP_FX = 46;               // fixed-point bits of a class weight
+
+__device__ __forceinline__ bool bf_is_nan(unsigned h) { return (h & 0x7fffu) > 0x7f80u; }
+// monotone key of a non-NaN bf16: negative values 0 .. 0x7ffe, +-0 0x8000, positive up to 0xffff
+__device__ __forceinline__ unsigned bf_key(unsigned h) {
+  h = h == 0x8000u ? 0u : h;
+  return (h & 0x8000u) ? (~h & 0xffffu) : (h | 0x8000u);
+}
+__device__ __forceinline__ float key_val(unsigned key) {
+  const unsigned h = (key & 0x8000u) ? (key & 0x7fffu) : (~key & 0xffffu);
+  return __uint_as_float(h << 16);
+}
+__device__ __forceinline__ unsigned hist_at(const unsigned* hist, unsigned key) {
+  const unsigned d = key >> 1;
+  return (hist[(d & 31u) * 1024u + (d >> 5)] >> ((key & 1u) * 16u)) & 0xffffu;
+}
+template <class V>
+__device__ __forceinline__ V wave_scan(V v, int lane) {   // inclusive, lane order
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const V u = __shfl_up(v, o, 64);
+    if (lane >= o) v += u;
   }
+  return v;
+}
+
+__global__ __launch_bounds__(SMP_THREADS) void k_decode_sample(
+    const bf16_t* __restrict__ logits, int ldl, int classes, int sample, const float* __restrict__ fpar,
+    const int* __restrict__ ipar, float* __restrict__ info, int* __restrict__ ctl, long long* __restrict__ next_ids,
+    long long* __restrict__ tokens, int* __restrict__ lens, int* __restrict__ finished, int Lcap,
+    unsigned* __restrict__ ticket) {
+  __shared__ __attribute__((aligned(16))) unsigned hist[32768];
+  __shared__ __attribute__((aligned(16))) unsigned bm[2048];
+  __shared__ unsigned long long wmass[16], s_zall, s_pexm, s_keptm;
+  __shared__ unsigned wcnt[16];
+  __shared__ int s_kmax, s_keyk, s_nk, s_psel, s_pexc, s_thr, s_keptc;
+  __shared__ float sv[16];
+  __shared__ int si[16];
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const unsigned seed = (unsigned)ctl[0], step = (unsigned)ctl[1];
+  const int eos = ctl[2];
+  const float T = fpar[0], topp = fpar[1], pen = fpar[2], ipen = fpar[3];
+  const int topk = ipar[0];
+  const bool penon = pen != 1.f;
+  const bf16_t* row = logits + (long long)b * ldl;
+
+  for (int i = tid; i < 8192; i += SMP_THREADS) reinterpret_cast<uint4*>(hist)[i] = make_uint4(0, 0, 0, 0);
+  if (tid < 512) reinterpret_cast<uint4*>(bm)[tid] = make_uint4(0, 0, 0, 0);
+  if (tid == 0) {
+    s_zall = s_pexm = s_keptm = 0ull;
+    s_kmax = -1; s_keyk = 0; s_nk = -1; s_psel = 0; s_pexc = 0; s_thr = 0; s_keptc = 0;
+  }
+  __syncthreads();
+  if (penon) {   // block-uniform
+    int n = lens[b];
+    n = n > Lcap - 1 ? Lcap - 1 : n;
+    for (int i = tid; i <= n; i += SMP_THREADS) {
+      const long long id = tokens[(long long)b * Lcap + i];
+      if (id >= 0 && id < classes) atomicOr(&bm[id >> 5], 1u << (id & 31));   // classes <= 65535
+    }
+    __syncthreads();
+  }
+  // the penalised bf16 of column c (raw bits h)
+  auto penalised = [&](unsigned h, int c) -> unsigned {
+    if (penon && ((bm[c >> 5] >> (c & 31)) & 1u)) {
+      const float f = bf2f((bf16_t)h);
+      h = f2bf(f > 0.f ? f * ipen : f * pen);
+    }
+    return h;
+  };
+  for (int c0 = tid * 8; c0 < classes; c0 += SMP_THREADS * 8) {
+    const uint4 q = *reinterpret_cast<const uint4*>(row + c0);   // ldl % 8 == 0: the row covers c0 .. c0 + 7
+    const unsigned w4[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const int c = c0 + k;
+      if (c >= classes) continue;
+      const unsigned h = penalised((w4[k >> 1] >> ((k & 1) * 16)) & 0xffffu, c);
+      if (bf_is_nan(h)) continue;
+      const unsigned key = bf_key(h), d = key >> 1;
+      atomicAdd(&hist[(d & 31u) * 1024u + (d >> 5)], 1u << ((key & 1u) * 16u));
+    }
+  }
+  __syncthreads();
+
+  // ---- counts: the maximum and the k-th largest value
+  const int ch = SMP_THREADS - 1 - tid;   // chunk: keys 64 ch .. 64 ch + 63
+  unsigned cnt = 0;
+  for (int j = 0; j < 32; ++j) {
+    const unsigned hw = hist[j * 1024 + ch];
+    cnt += (hw & 0xffffu) + (hw >> 16);
+  }
+  const unsigned cincl = wave_scan(cnt, lane);
+  if (lane == 63) wcnt[wv] = cincl;
+  __syncthreads();
+  unsigned coff = 0, total = 0;
+  for (int k = 0; k < 16; ++k) {
+    const unsigned w = wcnt[k];
+    coff += k < wv ? w : 0u;
+    total += w;
+  }
+  const unsigned cexcl = coff + cincl - cnt;
+  if (total == 0u) {   // no comparable value in the row: token 0
+    if (tid == 0) {
+      const float qnan = __uint_as_float(0x7fc00000u);
+      info[b * 4 + 0] = qnan; info[b * 4 + 1] = 0.f; info[b * 4 + 2] = 0.f; info[b * 4 + 3] = qnan;
+      advance_tail(b, 0x7fffffff, classes, eos, step, ctl, next_ids, tokens, lens, finished, Lcap, ticket);
+    }
+    return;
+  }
+  const bool kon = topk > 0 && topk < classes && (unsigned)topk <= total;
+  const bool first = cnt > 0u && cexcl == 0u;
+  const bool kth = kon && cexcl < (unsigned)topk && (unsigned)topk <= cexcl + cnt;
+  if (first || kth) {
+    unsigned run = cexcl;
+    bool fdone = !first, kdone = !kth;
+    for (int q = 63; q >= 0 && !(fdone && kdone); --q) {
+      const unsigned key = (unsigned)(ch * 64 + q), c = hist_at(hist, key);
+      if (!c) continue;
+      run += c;
+      if (!fdone) { s_kmax = (int)key; fdone = true; }
+      if (!kdone && run >= (unsigned)topk) { s_keyk = (int)key; s_nk = (int)run; kdone = true; }
+    }
+  }
+  if (!kon && cnt > 0u && cexcl + cnt == total) {   // top-k off: the threshold is the smallest value
+    for (int q = 0; q < 64; ++q) {
+      const unsigned key = (unsigned)(ch * 64 + q);
+      if (hist_at(hist, key)) { s_keyk = (int)key; break; }
+    }
+  }
+  __syncthreads();
+
+  // ---- masses: Z over the top-k survivors, the total over every non-NaN column
+  const int kmax = s_kmax, keyk = s_keyk;
+  const double vmax = (double)key_val((unsigned)kmax);
+  const double sc = 1.4426950408889634 / (double)T;
+  // the class weight of a value as a 2^-46 fixed-point number; the maximum's is exactly 1
+  auto weight = [&](unsigned key) -> unsigned long long {
+    if ((int)key == kmax) return 1ull << SMP_FX;
+    return (unsigned long long)__double2ll_rn(exp2(((double)key_val(key) - vmax) * sc) * (double)(1ull << SMP_FX));
+  };
+  unsigned long long mk = 0ull, mall = 0ull;
+  if (cnt) {
+    for (int q = 63; q >= 0; --q) {
+      const unsigned key = (unsigned)(ch * 64 + q), c = hist_at(hist, key);
+      if (!c) continue;
+      const unsigned long long wi = weight(key);
+      mall += c * wi;
+      if ((int)key >= keyk) mk += c * wi;
+    }
+  }
+  if (mall) atomicAdd(&s_zall, mall);
+  const unsigned long long mincl = wave_scan(mk, lane);
+  if (lane == 63) wmass[wv] = mincl;
+  __syncthreads();
+  unsigned long long moff = 0ull, Z = 0ull;
+  for (int k = 0; k < 16; ++k) {
+    const unsigned long long w = wmass[k];
+    moff += k < wv ? w : 0ull;
+    Z += w;
+  }
+  const unsigned long long mexcl = moff + mincl - mk;
+  const bool pon = topp < 1.f;
+  unsigned long long tgt = 0ull;
+  if (pon) {   // the smallest prefix of whole classes with mass >= p Z; Z >= 2^46: the maximum's class
+    tgt = (unsigned long long)ceil((double)topp * (double)Z);
+    tgt = tgt < 1ull ? 1ull : (tgt > Z ? Z : tgt);
+    if (mk && mexcl < tgt && tgt <= mexcl + mk) { s_psel = ch; s_pexm = mexcl; s_pexc = (int)cexcl; }
+  } else if (tid == 0) {
+    s_thr = keyk; s_keptc = s_nk < 0 ? (int)total : s_nk; s_keptm = Z;
+  }
+  __syncthreads();
+  if (pon && wv == 0) {   // the crossing inside the selected chunk: one key per lane, descending
+    const unsigned key = (unsigned)(s_psel * 64 + 63 - lane), c = hist_at(hist, key);
+    unsigned long long m = 0ull;
+    if (c && (int)key >= keyk) {
+      const unsigned long long wi = weight(key);
+      m = c * wi;
+    }
+    const unsigned long long mi = s_pexm + wave_scan(m, lane);
+    const unsigned ci = (unsigned)s_pexc + wave_scan(c, lane);
+    const unsigned long long hit = __ballot(m != 0ull && mi >= tgt);
+    if (hit && lane == __ffsll((long long)hit) - 1) { s_thr = (int)key; s_keptc = (int)ci; s_keptm = mi; }
+  }
+  if (pon) __syncthreads();
+  const unsigned thr = (unsigned)s_thr;
+
+  // ---- the pick among the kept columns
+  const float invT = sample ? 1.f / T : 1.f;
+  const unsigned sb = seed ^ ((unsigned)b * 0x9E3779B9u + 0x67756D62u);
+  float best = -INFINITY;
+  int bi = 0x7fffffff;
+  for (int c0 = tid * 8; c0 < classes; c0 += SMP_THREADS * 8) {
+    const uint4 q = *reinterpret_cast<const uint4*>(row + c0);
+    const unsigned w4[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const int c = c0 + k;
+      if (c >= classes) continue;
+      const unsigned h = penalised((w4[k >> 1] >> ((k & 1) * 16)) & 0xffffu, c);
+      if (bf_is_nan(h) || bf_key(h) < thr) continue;
+      float v = bf2f((bf16_t)h);
+      if (sample) v = gumbel_key(v, invT, sb, step, (unsigned)c);
+      if (v > best || (v == best && c < bi)) { best = v; bi = c; }
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(best, o, 64);
+    const int oi = __shfl_xor(bi, o, 64);
+    if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
+  }
+  if (lane == 0) { sv[wv] = best; si[wv] = bi; }
+  __syncthreads();
+  if (tid != 0) return;
+  for (int k = 1; k < 16; ++k)
+    if (sv[k] > best || (sv[k] == best && si[k] < bi)) { best = sv[k]; bi = si[k]; }
+  info[b * 4 + 0] = key_val(thr);
+  info[b * 4 + 1] = (float)s_keptc;
+  info[b * 4 + 2] = (float)((double)s_keptm / (double)s_zall);
+  info[b * 4 + 3] = (float)vmax;
+  advance_tail(b, bi, classes, eos, step, ctl, next_ids, tokens, lens, finished, Lcap, ticket);
 }
 
 }  // namespace
@@ -473,5 +731,21 @@ KML_API int kml_decode_advance(const bf16_t* logits, int ldl, int classes, int s
     return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(k_decode_advance, dim3((unsigned)B), dim3(256), 0, s, logits, ldl, classes, sample, temp, ctl,
                      next_ids, tokens, lens, finished, Lcap, ticket);
+  KML_LAUNCH_CHECK();
+}
+
+// the largest `classes` kml_decode_sample takes (16-bit counts per value, 65536-bit id bitmap)
+KML_API int kml_decode_sample_max_classes(void) { return SMP_MAX_CLASSES; }
+
+// kml_decode_advance behind a repetition penalty, top-k and top-p: fpar fp32 [temperature, top_p,
+// penalty, 1 / penalty], ipar int32 [top_k], info fp32 [B, 4] (written every call)
+KML_API int kml_decode_sample(const bf16_t* logits, int ldl, int classes, int sample, const float* fpar,
+                              const int* ipar, float* info, int* ctl, long long* next_ids, long long* tokens,
+                              int* lens, int* finished, int B, int Lcap, unsigned* ticket, hipStream_t s) {
+  if (!logits || !fpar || !ipar || !info || !ctl || !next_ids || !tokens || !lens || !finished || !ticket || B < 1 ||
+      classes < 1 || classes > SMP_MAX_CLASSES || ldl % 8 || ldl < classes || Lcap < 1)
+    return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_decode_sample, dim3((unsigned)B), dim3(SMP_THREADS), 0, s, logits, ldl, classes, sample, fpar,
+                     ipar, info, ctl, next_ids, tokens, lens, finished, Lcap, ticket);
   KML_LAUNCH_CHECK();
 }

@@ -26,7 +26,7 @@ import torch
 import torch.nn as tnn
 from torch.autograd import Function
 
-from ..nn.decode import KVCache
+from ..nn.decode import KVCache, filter_logits
 from ..nn.flat import grad_storage_of, shadow_of
 from ..nn.modules import Linear, cross_entropy
 from ..nn.transformer import Dropout, LayerNorm, RNGState, SelfAttention, _bf, gather_rows
@@ -321,14 +321,25 @@ class GPT2LMHeadModel(tnn.Module):
             x, s = ln.add_norm(m, residual=s)
         logits = self.lm_head.forward_small(x, keep_pad=True)
         if advance:
-            D.decode_advance(logits, self.vocab, cache.ctl, cache.temp, cache.next_ids, cache.tokens, cache.lens,
-                             cache.finished, sample=cache.sample)
+            self._pick(cache, logits)
         return logits
 
+    def _pick(self, cache, logits):
+        """The GPU step's last launch: the plain sampler, or the filtered one when the cache has
+        a repetition penalty, top-k or top-p on."""
+        from ..ops import decode as D
+        if cache.filtered:
+            D.decode_sample(logits, self.vocab, cache.ctl, cache.fpar, cache.ipar, cache.next_ids, cache.tokens,
+                            cache.lens, cache.finished, sample=cache.sample, info=cache.info)
+        else:
+            D.decode_advance(logits, self.vocab, cache.ctl, cache.temp, cache.next_ids, cache.tokens, cache.lens,
+                             cache.finished, sample=cache.sample)
+
     def _replay(self, cache, advance):
-        """The GPU step as one captured graph per (cache, advance, sampling); captured on first
-        use after an eager warm-up whose effect on the decode state is rolled back."""
-        key = (bool(advance), bool(cache.sample))
+        """The GPU step as one captured graph per (cache, advance, sampling, filtered); captured
+        on first use after an eager warm-up whose effect on the decode state is rolled back.  The
+        filter parameters live in device memory: other values replay the same graph."""
+        key = (bool(advance), bool(cache.sample), bool(cache.filtered))
         ent = cache._graphs.get(key)
         if ent is None:
             from ..engine.step import capture_graph
@@ -352,7 +363,8 @@ class GPT2LMHeadModel(tnn.Module):
 
     def decode_step(self, cache):
         """Feed ``cache.next_ids``, append its keys / values, pick the next token (greedy or
-        Gumbel-max, per the cache's sampling state) and advance ``lens``.  Returns the logits."""
+        Gumbel-max, behind the cache's repetition penalty / top-k / top-p if any is on) and
+        advance ``lens``.  Returns the logits."""
         if cache.lens.is_cuda:
             return self._replay(cache, True)
         return self._step(cache, True)
@@ -362,9 +374,7 @@ class GPT2LMHeadModel(tnn.Module):
         (``cache.next_ids``, ``cache.tokens[b, prompt_len[b]]``).  Returns the prompt's last logits."""
         logits = self._prefill(ids, attention_mask, cache)
         if ids.is_cuda:
-            from ..ops import decode as D
-            D.decode_advance(logits, self.vocab, cache.ctl, cache.temp, cache.next_ids, cache.tokens, cache.lens,
-                             cache.finished, sample=cache.sample)
+            self._pick(cache, logits)
         else:
             _advance_cpu(cache, logits, cache.gen)
         return logits
@@ -383,9 +393,13 @@ class GPT2LMHeadModel(tnn.Module):
         return logits[:, :self.vocab].clone()
 
     @torch.no_grad()
-    def generate(self, ids, attention_mask=None, max_new_tokens=32, temperature=0.0, eos_token_id=None, seed=0):
+    def generate(self, ids, attention_mask=None, max_new_tokens=32, temperature=0.0, eos_token_id=None, seed=0,
+                 top_k=0, top_p=1.0, repetition_penalty=1.0):
         """Continue each right-padded prompt by ``max_new_tokens`` tokens: greedy at
-        ``temperature == 0``, else Gumbel-max sampling reproducible from ``seed``.  A sequence that
+        ``temperature == 0``, else Gumbel-max sampling reproducible from ``seed``.  HF's processor
+        chain runs on the device ahead of the pick: ``repetition_penalty`` (1: off) over the prompt
+        and everything generated, ``top_k`` (0: off; ties at the k-th value stay) and ``top_p`` (1:
+        off; whole classes of equal value).  A sequence that
         draws ``eos_token_id`` keeps emitting it.  Returns int64 ``[B, Lprompt_max +
         max_new_tokens]``: row b is its prompt, its new tokens, then ``eos_token_id`` (0 without
         one) up to the common width."""
@@ -409,7 +423,8 @@ class GPT2LMHeadModel(tnn.Module):
         cache = caches.get(key)
         if cache is None:
             cache = caches[key] = self.new_cache(B, Lcap, ids.device)
-        cache.reset(seed=seed, temperature=temperature, eos_token_id=eos_token_id)
+        cache.reset(seed=seed, temperature=temperature, eos_token_id=eos_token_id, top_k=top_k, top_p=top_p,
+                    repetition_penalty=repetition_penalty)
         if ids.is_cuda:
             for p in self.parameters():   # bf16 shadows current before the captured step reads them
                 shadow_of(p)
@@ -425,11 +440,20 @@ class GPT2LMHeadModel(tnn.Module):
 
 
 def _advance_cpu(cache, logits, gen):
-    """Stock-torch twin of ``kml_decode_advance`` on a CPU cache."""
+    """Stock-torch twin of ``kml_decode_advance`` / ``kml_decode_sample`` on a CPU cache."""
     eos = int(cache.ctl[2])
+    keep = None
+    if cache.filtered:
+        T, k, p, pen = cache.filters
+        logits, keep = filter_logits(logits, cache.tokens, cache.lens, T, k, p, pen)
     if cache.sample:
         u = torch.rand(logits.shape, generator=gen, dtype=torch.float64).clamp_(1e-300, 1.0 - 1e-16)
-        tok = (logits.double() / float(cache.temp[0]) - torch.log(-torch.log(u))).argmax(-1)
+        key = logits.double() / float(cache.temp[0]) - torch.log(-torch.log(u))
+        if keep is not None:
+            key = key.masked_fill(~keep, float("-inf"))
+        tok = key.argmax(-1)
+    elif keep is not None:   # the argmax of the penalised row; NaN never wins, an all-NaN row gives 0
+        tok = logits.masked_fill(torch.isnan(logits), float("-inf")).argmax(-1)
     else:
         tok = logits.argmax(-1)
     if eos >= 0:

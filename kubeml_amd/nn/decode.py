@@ -5,6 +5,60 @@ from __future__ import annotations
 import torch
 
 
+def filter_logits(logits, tokens, lens, temperature=1.0, top_k=0, top_p=1.0, penalty=1.0):
+    """Stock-torch twin of the filters of ``kml_decode_sample``, in HF's processor order.
+
+    ``logits [B, classes]``; ``tokens [B, L]`` int64 and ``lens [B]``: row b's history is
+    ``tokens[b, 0 .. lens[b]]``.  Returns ``(penalised logits, keep mask)``.
+
+    1. Repetition penalty, once per distinct id of the history inside ``[0, classes)``: a logit v
+       becomes ``v / penalty`` if positive, else ``v * penalty``.  bf16 input takes the kernel's
+       arithmetic: ``bf16(fp32(v) * fp32(1 / penalty))`` and ``bf16(fp32(v) * fp32(penalty))``.
+    2. Columns are compared as values: ``-0.0 == +0.0``, NaN is never kept.
+    3. ``0 < top_k < classes``: keep what is ``>=`` the k-th largest value (its ties included).
+    4. ``top_p < 1``: with ``w = exp((v - vmax) / T)`` over the survivors (fp64) and Z their sum,
+       walk the classes of equal value downwards and keep the smallest prefix of whole classes
+       whose mass is ``>= fp32(top_p) * Z``; the class of the maximum always stays.
+    The temperature is taken as the fp32 number the kernel reads."""
+    B, C = logits.shape
+    z = logits.clone()
+    if penalty != 1.0:
+        pen = torch.tensor(float(penalty), dtype=torch.float32)
+        inv = torch.tensor(1.0 / float(penalty), dtype=torch.float32)
+        for b in range(B):
+            ids = tokens[b, :max(int(lens[b]) + 1, 0)].cpu()
+            ids = torch.unique(ids[(ids >= 0) & (ids < C)]).to(z.device)
+            v = z[b, ids]
+            if z.dtype == torch.bfloat16:
+                f = v.float()
+                z[b, ids] = torch.where(f > 0, f * inv.to(f.device), f * pen.to(f.device)).to(torch.bfloat16)
+            else:
+                z[b, ids] = torch.where(v > 0, v / float(penalty), v * float(penalty))
+    x = z.double().cpu() + 0.0   # -0.0 + 0.0 = +0.0
+    T = float(torch.tensor(float(temperature), dtype=torch.float32))
+    p = float(torch.tensor(float(top_p), dtype=torch.float32))
+    valid = ~torch.isnan(x)
+    xs = torch.where(valid, x, torch.full_like(x, float("-inf")))
+    keep = valid.clone()
+    if 0 < top_k < C:
+        kth = xs.topk(int(top_k), dim=-1).values[:, -1:]
+        keep &= xs >= kth
+    if p < 1.0:
+        for b in range(B):
+            if not bool(keep[b].any()):
+                continue
+            v = xs[b][keep[b]]
+            vals, inverse = torch.unique(v, return_inverse=True)   # ascending classes
+            vmax = vals[-1]
+            w = torch.where(vals == vmax, torch.ones_like(vals), torch.exp((vals - vmax) / T))
+            mass = torch.zeros_like(vals).index_add_(0, inverse, w[inverse]).flip(0)   # descending
+            cum = mass.cumsum(0)
+            reach = (cum >= p * cum[-1]).nonzero()
+            idx = int(reach[0]) if reach.numel() else vals.numel() - 1
+            keep[b] &= xs[b] >= vals.flip(0)[idx]
+    return z, keep.to(z.device)
+
+
 class KVCache:
     """Keys and values of ``layers`` attention layers for ``B`` sequences of up to ``Lcap``
     tokens (rounded up to a multiple of 64), head dim 64.
@@ -18,6 +72,9 @@ class KVCache:
       token the next step feeds; ``finished`` int32 ``[B]``: eos seen.
     * ``ctl`` int32 ``[seed, step, eos (-1: none), 0]`` and ``temp`` fp32 ``[temperature]``: what
       the sampler reads; ``ws``: the chunk partials of the decode attention (GPU only).
+    * ``fpar`` fp32 ``[temperature, top_p, penalty, 1 / penalty]`` and ``ipar`` int32 ``[top_k]``:
+      what the filtered sampler (``kml_decode_sample``) reads; ``info`` fp32 ``[B, 4]``: what it
+      reports per row (threshold value, kept columns, kept mass share, row maximum).
     """
 
     def __init__(self, layers, B, H, Lcap, device, dtype=None):
@@ -37,16 +94,24 @@ class KVCache:
         self.finished = torch.zeros(self.B, dtype=torch.int32, device=device)
         self.ctl = torch.tensor([0, 0, -1, 0], dtype=torch.int32, device=device)
         self.temp = torch.ones(1, dtype=torch.float32, device=device)
+        self.fpar = torch.tensor([1.0, 1.0, 1.0, 1.0], dtype=torch.float32, device=device)
+        self.ipar = torch.zeros(1, dtype=torch.int32, device=device)
+        self.info = torch.zeros((self.B, 4), dtype=torch.float32, device=device)
         self.ws = None
         if gpu:
             from ..ops import decode as D
             self.ws = D.attn_decode_workspace(self.B, self.H, self.Lcap, device)
         self.sample = False   # Gumbel-max sampling at temp[0] instead of the argmax
+        self.filtered = False   # a repetition penalty, top-k or top-p is on: the filtered sampler picks
+        self.filters = (1.0, 0, 1.0, 1.0)   # host copy: temperature, top_k, top_p, penalty
         self.gen = None       # CPU sampling: the torch.Generator the draws come from
-        self._graphs = {}     # (advance, sample) -> (captured step, its logits)
+        self._graphs = {}     # (advance, sample, filtered) -> (captured step, its logits)
 
-    def reset(self, seed=0, temperature=0.0, eos_token_id=None):
-        """Empty the cache for a new batch (the K / V rows are simply no longer covered by lens)."""
+    def reset(self, seed=0, temperature=0.0, eos_token_id=None, top_k=0, top_p=1.0, repetition_penalty=1.0):
+        """Empty the cache for a new batch (the K / V rows are simply no longer covered by lens)
+        and set the sampling state; ``top_k`` 0, ``top_p`` 1 and ``repetition_penalty`` 1 are off."""
+        from ..ops.decode import sampling_params
+        fpar, ipar = sampling_params(temperature, top_k, top_p, repetition_penalty, sample=temperature > 0)
         self.lens.zero_()
         self.tokens.zero_()
         self.next_ids.zero_()
@@ -55,6 +120,10 @@ class KVCache:
         self.ctl.copy_(torch.tensor([int(seed) & 0x7FFFFFFF, 0, eos, 0], dtype=torch.int32))
         self.temp.fill_(float(temperature) if temperature > 0 else 1.0)
         self.sample = temperature > 0
+        self.fpar.copy_(torch.tensor(fpar, dtype=torch.float32))
+        self.ipar.copy_(torch.tensor(ipar, dtype=torch.int32))
+        self.filters = (fpar[0], ipar[0], fpar[1], fpar[2])
+        self.filtered = ipar[0] != 0 or fpar[1] != 1.0 or fpar[2] != 1.0
         if self.device.type != "cuda":
             self.gen = torch.Generator().manual_seed(int(seed))
 

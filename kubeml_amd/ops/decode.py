@@ -1,9 +1,9 @@
 """Launchers for the decode kernels (csrc/kernels/decode.hip): KV-cache append, one-query
 attention over the cache, the skinny (M <= 16) GEMM, the embedding at the device lengths and
-the next-token choice.
+the next-token choice (plain, or behind a repetition penalty, top-k and top-p).
 
 Everything a step needs that changes per token — sequence lengths, seed / step, temperature,
-eos — is read from device memory, so one captured step replays for every token.  All launches
+eos, the sampling filters — is read from device memory, so one captured step replays for every token.  All launches
 go on the current HIP stream and are hipGraph-capturable (no host sync, no memset nodes).
 """
 from __future__ import annotations
@@ -180,3 +180,67 @@ def decode_advance(logits, classes, ctl, temp, next_ids, tokens, lens, finished,
     HIP.call("kml_decode_advance", "p i i i p p p p p p i i p s", _p(logits), logits.stride(0), int(classes),
              int(bool(sample)), _p(temp), _p(ctl), _p(next_ids), _p(tokens), _p(lens), _p(finished), B,
              tokens.shape[1], _p(ticket), _s())
+
+
+def sample_max_classes() -> int:
+    """The widest row :func:`decode_sample` takes: it counts every bf16 value of the row in 16 bits
+    and keeps the penalised ids in a 65536-bit bitmap (both constants of the kernel)."""
+    return int(HIP.raw("kml_decode_sample_max_classes"))
+
+
+def sampling_params(temperature=1.0, top_k=0, top_p=1.0, penalty=1.0, sample=True):
+    """Check the sampling parameters and return what the kernel reads: ``(fpar, ipar)`` =
+    ``([temperature, top_p, penalty, 1 / penalty], [top_k])``.  Limits: ``penalty > 0``,
+    ``0 < top_p <= 1``, ``top_k >= 0`` (0: off), ``temperature > 0`` when sampling (greedy: the
+    nucleus is measured at temperature 1).  ``1 / penalty`` is stored, in fp32, because the kernel
+    multiplies and never divides."""
+    if not penalty > 0:
+        raise ValueError(f"repetition_penalty must be > 0, got {penalty}")
+    if not 0 < top_p <= 1:
+        raise ValueError(f"top_p must be in (0, 1], got {top_p}")
+    if int(top_k) != top_k or top_k < 0:
+        raise ValueError(f"top_k must be an integer >= 0, got {top_k}")
+    if sample and not temperature > 0:
+        raise ValueError(f"temperature must be > 0 when sampling, got {temperature}")
+    T = float(temperature) if sample else 1.0
+    return [T, float(top_p), float(penalty), 1.0 / float(penalty)], [min(int(top_k), 0x7FFFFFFF)]
+
+
+def decode_sample(logits, classes, ctl, fpar, ipar, next_ids, tokens, lens, finished, sample, info=None):
+    """:func:`decode_advance` behind HF's processor chain, in the same single launch: the
+    repetition penalty over the distinct ids of ``tokens[b, 0 .. lens[b]]`` (each logit rounded to
+    bf16 again), top-k with ties at the k-th value kept, top-p over whole classes of equal value at
+    temperature ``fpar[0]``, then the argmax (``sample`` False) or the Gumbel-max draw among the
+    kept columns.  ``fpar`` fp32 ``[temperature, top_p, penalty, 1 / penalty]`` and ``ipar`` int32
+    ``[top_k]`` as :func:`sampling_params` gives them, on the device.  At most
+    :func:`sample_max_classes` classes.  Returns ``info`` fp32 ``[B, 4]``: the smallest kept value,
+    the kept column count, kept mass / mass of all non-NaN columns, the row maximum after the
+    penalty."""
+    _chk_view(logits, "logits")
+    B, ldw = logits.shape
+    if not 1 <= classes <= ldw:
+        raise ValueError(f"decode_sample: {classes} classes in rows of {ldw}")
+    if classes > sample_max_classes():
+        raise ValueError(f"decode_sample: {classes} classes; the kernel counts at most {sample_max_classes()}")
+    _chk(ctl, I32, "ctl", ndim=1)
+    _chk(fpar, F32, "fpar", ndim=1)
+    _chk(ipar, I32, "ipar", ndim=1)
+    _chk(next_ids, I64, "next_ids", ndim=1)
+    _chk(tokens, I64, "tokens", ndim=2)
+    _chk(finished, I32, "finished", ndim=1)
+    _chk_lens(lens, B)
+    if (ctl.numel() < 4 or fpar.numel() < 4 or ipar.numel() < 1 or next_ids.numel() != B or finished.numel() != B or
+            tokens.shape[0] != B):
+        raise ValueError("decode_sample: state tensors do not match the batch")
+    if logits.stride(0) < -(-classes // 8) * 8:
+        raise ValueError("decode_sample: logits rows shorter than the classes padded to 8")
+    if info is None:
+        info = torch.empty((B, 4), dtype=F32, device=logits.device)
+    _chk(info, F32, "info", ndim=2)
+    if info.shape != (B, 4):
+        raise ValueError(f"info: expected [{B}, 4]")
+    ticket = _COUNTERS.take(logits.device, 1)
+    HIP.call("kml_decode_sample", "p i i i p p p p p p p p i i p s", _p(logits), logits.stride(0), int(classes),
+             int(bool(sample)), _p(fpar), _p(ipar), _p(info), _p(ctl), _p(next_ids), _p(tokens), _p(lens),
+             _p(finished), B, tokens.shape[1], _p(ticket), _s())
+    return info

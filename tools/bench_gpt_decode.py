@@ -3,12 +3,17 @@ same step on the existing Linear route and against full recompute, the skinny GE
 existing small-M route per shape, and the decode attention over its keys-per-chunk choices.
 
     python tools/bench_gpt_decode.py [--rounds 5] [--iters 20] [--new 256] [--out FILE.json]
+                                     [--top-k K] [--top-p P] [--repetition-penalty R] [--skip-kernels]
 
 * decode: B in {1, 4, 16}, prompt 128, ``--new`` tokens.  (a) the captured step of ``generate``
   (``decode_step`` replays, timed between device events after the prefill); (b) the same step
   with every ``forward_small`` sent to ``Linear.forward``; (c) ``model(ids)`` on the whole growing
   sequence per token, B = 1, 32 tokens, host clock ending in a synchronise.  (a) and (b) alternate
-  inside every round; the figure is the median over the rounds.
+  inside every round; the figure is the median over the rounds.  With ``--top-k`` / ``--top-p`` /
+  ``--repetition-penalty`` (default: off) a third variant, ``filtered``, is the captured step whose
+  last launch is ``kml_decode_sample`` with those filters, sampling at temperature 1.
+* sampler: ``kml_decode_advance`` against ``kml_decode_sample`` alone on ``[B, 50264]`` logits, a
+  history of 384 tokens, B in {1, 4, 16}; the filters of the flags, or 50 / 0.95 / 1.2 without any.
 * GEMM: the five GPT-2 small weight shapes at M in {1, 4, 8, 16}: ``gemm_skinny`` against what
   ``Linear.forward`` launches at that M (the 1x1 implicit-GEMM conv, plus the GELU launch).  Each
   variant walks a ring of weight copies of at least 64 MB, so no launch finds its weights in the
@@ -46,6 +51,10 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--new", type=int, default=256)
     ap.add_argument("--skip-model", action="store_true")
+    ap.add_argument("--skip-kernels", action="store_true", help="no GEMM / attention sweeps")
+    ap.add_argument("--top-k", type=int, default=0)
+    ap.add_argument("--top-p", type=float, default=1.0)
+    ap.add_argument("--repetition-penalty", type=float, default=1.0)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import torch
@@ -92,6 +101,9 @@ def main():
 
     res = {"device": torch.cuda.get_device_name(0), "chunk": D.attn_decode_chunk(), "rounds": a.rounds,
            "iters": a.iters}
+    filt = dict(top_k=a.top_k, top_p=a.top_p, repetition_penalty=a.repetition_penalty)
+    filtered = a.top_k != 0 or a.top_p != 1.0 or a.repetition_penalty != 1.0
+    res["filters"] = filt if filtered else None
 
     # ------------------------------------------------------------------ skinny GEMM vs existing
     def existing(x, w, bias, act):
@@ -100,58 +112,90 @@ def main():
         y = K.conv_fwd(x.view(M, 1, 1, Kd), w.view(N, 1, 1, Kd), 1, 1, (1, 1), (0, 0), bias=bias).view(M, N)
         return T.gelu_fwd(y) if act == "gelu" else y
 
-    gemm = []
-    for name, N, Kd, act, has_bias in SHAPES:
-        copies = max(2, min(48, -(-(64 << 20) // (N * Kd * 2))))
-        ws = [(torch.randn(N, Kd, device=dev, generator=gen) * 0.02).to(BF) for _ in range(copies)]
-        bias = torch.randn(N, device=dev, generator=gen) if has_bias else None
-        for M in (1, 4, 8, 16):
-            x = torch.randn(M, Kd, device=dev, generator=gen).to(BF)
-            out = torch.empty(M, N, dtype=BF, device=dev)
-            ring = [ws[i % copies] for i in range(a.iters)]
+    if not a.skip_kernels:
+        gemm = []
+        for name, N, Kd, act, has_bias in SHAPES:
+            copies = max(2, min(48, -(-(64 << 20) // (N * Kd * 2))))
+            ws = [(torch.randn(N, Kd, device=dev, generator=gen) * 0.02).to(BF) for _ in range(copies)]
+            bias = torch.randn(N, device=dev, generator=gen) if has_bias else None
+            for M in (1, 4, 8, 16):
+                x = torch.randn(M, Kd, device=dev, generator=gen).to(BF)
+                out = torch.empty(M, N, dtype=BF, device=dev)
+                ring = [ws[i % copies] for i in range(a.iters)]
 
-            def sk():
-                for w in ring:
-                    D.gemm_skinny(x, w, bias, act=act, out=out)
+                def sk():
+                    for w in ring:
+                        D.gemm_skinny(x, w, bias, act=act, out=out)
 
-            def ex():
-                for w in ring:
-                    existing(x, w, bias, act)
-            runs = {"skinny": graphed(sk), "existing": graphed(ex)}
-            if M == 4 and N == 768:       # the K-split sweep behind the plan of the two narrow shapes
-                for S in (1, 2, 4, 8):
-                    def sks(S=S):
-                        for w in ring:
-                            D.gemm_skinny(x, w, bias, act=act, out=out, splits=S)
-                    runs[f"skinny_splits_{S}"] = graphed(sks)
+                def ex():
+                    for w in ring:
+                        existing(x, w, bias, act)
+                runs = {"skinny": graphed(sk), "existing": graphed(ex)}
+                if M == 4 and N == 768:       # the K-split sweep behind the plan of the two narrow shapes
+                    for S in (1, 2, 4, 8):
+                        def sks(S=S):
+                            for w in ring:
+                                D.gemm_skinny(x, w, bias, act=act, out=out, splits=S)
+                        runs[f"skinny_splits_{S}"] = graphed(sks)
+                r = alternate(runs, a.iters)
+                floor = N * Kd * 2 / 6.3e12 * 1e6
+                gemm.append({"shape": name, "N": N, "K": Kd, "M": M, "splits": int(D.HIP.raw("kml_gemm_skinny_splits", N, Kd)),
+                             **r, "weight_floor_us_derived": round(floor, 3)})
+                print(json.dumps(gemm[-1]), file=sys.stderr, flush=True)
+            del ws
+        res["gemm"] = gemm
+
+        # ------------------------------------------------------------------ decode attention, chunk sweep
+        B, H, Lcap = 4, 12, 1024
+        kc = torch.randn(B, H, Lcap, 64, device=dev, generator=gen).to(BF)
+        vc = torch.randn(B, H, Lcap, 64, device=dev, generator=gen).to(BF)
+        q = torch.randn(B, 3 * H * 64, device=dev, generator=gen).to(BF)
+        wsb = D.attn_decode_workspace(B, H, Lcap, dev)
+        o = torch.empty(B, H * 64, dtype=BF, device=dev)
+        attn = []
+        for n in (128, 512, 1023):
+            lens = torch.full((B,), n - 1, dtype=torch.int32, device=dev)
+            runs = {}
+            for c in (64, 128, 256, 512):
+                def f(c=c):
+                    for _ in range(a.iters):
+                        D.attn_decode(q, kc, vc, lens, ws=wsb, out=o, chunk=c)
+                runs[str(c)] = graphed(f)
             r = alternate(runs, a.iters)
-            floor = N * Kd * 2 / 6.3e12 * 1e6
-            gemm.append({"shape": name, "N": N, "K": Kd, "M": M, "splits": int(D.HIP.raw("kml_gemm_skinny_splits", N, Kd)),
-                         **r, "weight_floor_us_derived": round(floor, 3)})
-            print(json.dumps(gemm[-1]), file=sys.stderr, flush=True)
-        del ws
-    res["gemm"] = gemm
+            attn.append({"keys": n, "B": B, "H": H, "Lcap": Lcap, "chunk_us": r})
+            print(json.dumps(attn[-1]), file=sys.stderr, flush=True)
+        res["attention"] = attn
 
-    # ------------------------------------------------------------------ decode attention, chunk sweep
-    B, H, Lcap = 4, 12, 1024
-    kc = torch.randn(B, H, Lcap, 64, device=dev, generator=gen).to(BF)
-    vc = torch.randn(B, H, Lcap, 64, device=dev, generator=gen).to(BF)
-    q = torch.randn(B, 3 * H * 64, device=dev, generator=gen).to(BF)
-    wsb = D.attn_decode_workspace(B, H, Lcap, dev)
-    o = torch.empty(B, H * 64, dtype=BF, device=dev)
-    attn = []
-    for n in (128, 512, 1023):
-        lens = torch.full((B,), n - 1, dtype=torch.int32, device=dev)
-        runs = {}
-        for c in (64, 128, 256, 512):
-            def f(c=c):
-                for _ in range(a.iters):
-                    D.attn_decode(q, kc, vc, lens, ws=wsb, out=o, chunk=c)
-            runs[str(c)] = graphed(f)
-        r = alternate(runs, a.iters)
-        attn.append({"keys": n, "B": B, "H": H, "Lcap": Lcap, "chunk_us": r})
-        print(json.dumps(attn[-1]), file=sys.stderr, flush=True)
-    res["attention"] = attn
+    # ------------------------------------------------------------------ the sampler alone
+    fk = filt if filtered else dict(top_k=50, top_p=0.95, repetition_penalty=1.2)
+    fpar, ipar = D.sampling_params(1.0, fk["top_k"], fk["top_p"], fk["repetition_penalty"])
+    sampler = []
+    for Bm in (1, 4, 16):
+        logits = (torch.randn(Bm, 50264, device=dev, generator=gen) * 3.0).to(BF)
+
+        def state():
+            st = dict(ctl=torch.tensor([1, 0, -1, 0], dtype=torch.int32, device=dev),
+                      next_ids=torch.zeros(Bm, dtype=torch.int64, device=dev),
+                      tokens=torch.randint(0, 50257, (Bm, 1024), device=dev, generator=gen),
+                      lens=torch.full((Bm,), 383, dtype=torch.int32, device=dev),
+                      finished=torch.zeros(Bm, dtype=torch.int32, device=dev))
+            return st
+        sa, ss = state(), state()
+        temp = torch.ones(1, device=dev)
+        fp, ip = torch.tensor(fpar, device=dev), torch.tensor(ipar, dtype=torch.int32, device=dev)
+        info = torch.empty(Bm, 4, device=dev)
+
+        def adv():
+            for _ in range(a.iters):
+                D.decode_advance(logits, 50257, temp=temp, sample=True, **sa)
+
+        def smp():
+            for _ in range(a.iters):
+                D.decode_sample(logits, 50257, fpar=fp, ipar=ip, sample=True, info=info, **ss)
+        r = alternate({"kml_decode_advance": graphed(adv), "kml_decode_sample": graphed(smp)}, a.iters)
+        sampler.append({"B": Bm, "classes": 50257, "history": 384, **fk, **r})
+        print(json.dumps(sampler[-1]), file=sys.stderr, flush=True)
+    res["sampler"] = sampler
 
     # ------------------------------------------------------------------ the model
     if not a.skip_model:
@@ -174,17 +218,20 @@ def main():
             ids = torch.randint(0, 50257, (Bm, prompt), device=dev, generator=gen)
             per = {}
             caches = {}
-            for variant in ("generate", "existing_linears"):
+            kws = {"generate": {}, "existing_linears": {}}
+            if filtered:
+                kws["filtered"] = dict(temperature=1.0, seed=1, **filt)
+            for variant in kws:
                 NM._SMALL_EXISTING = _Everything() if variant == "existing_linears" else routes
                 caches[variant] = model.new_cache(Bm, prompt + new, dev)
-                caches[variant].reset()
+                caches[variant].reset(**kws[variant])
                 model.prefill(ids, None, caches[variant])
                 model.decode_step(caches[variant])       # capture under this variant's routing
             NM._SMALL_EXISTING = routes
             times = {v: [] for v in caches}
             for _ in range(a.rounds):
                 for variant, cache in caches.items():
-                    cache.reset()
+                    cache.reset(**kws[variant])
                     model.prefill(ids, None, cache)
                     torch.cuda.synchronize()
                     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
