@@ -9,6 +9,11 @@
 //   kml_decode_advance  greedy / Gumbel-max token choice, eos bookkeeping, lens and step advance
 //   kml_decode_sample   the same choice after a repetition penalty, top-k and top-p (nucleus)
 //                       filtering of the row, every parameter read from device memory
+//   speculative decoding, k draft tokens verified per round (Q = k + 1 rows a sequence):
+//   kml_embed2_multi / kml_attn_decode_multi   the rows at positions lens[b] .. lens[b] + k, each
+//                       bit-identical to the one-row kernels at that length
+//   kml_draft_lookup    n-gram (prompt lookup) drafter over a sequence's own history
+//   kml_verify_pick     the pick of every row, then accept / commit on the device
 // Sequence lengths, the sampling temperature, seed, step and eos live in device memory, so one
 // captured step replays for every token.  No float atomics anywhere: every reduction has a fixed
 // order (lane butterflies, wave order in LDS, chunk / split order in the fold).
@@ -57,7 +62,8 @@ __device__ __forceinline__ void unpack8(const uint4 v, float* f) {
 
 // ------------------------------------------------------------------------------------ KV append
 // One thread per 16 bytes: (token row, head, K | V, 8 columns).  Prefill: row t of sequence b goes
-// to cache row t; decode (Lq = 1): to cache row lens[b].  Rows outside [0, Lcap) are dropped.
+// to cache row t; decode: to cache row lens[b] + t (Lq = 1 in a plain step, the rows of a verify
+// round otherwise).  Rows outside [0, Lcap) are dropped.
 __global__ __launch_bounds__(256) void k_kv_append(const bf16_t* __restrict__ qkv, int ldq, bf16_t* __restrict__ kc,
                                                    bf16_t* __restrict__ vc, const int* __restrict__ lens, int B, int H,
                                                    int Lq, int Lcap, int decode) {
@@ -69,7 +75,7 @@ __global__ __launch_bounds__(256) void k_kv_append(const bf16_t* __restrict__ qk
   const int h = (int)(rh % H);
   const long long tr = rh / H;           // token row b * Lq + t
   const int b = (int)(tr / Lq), t = (int)(tr % Lq);
-  const int row = decode ? lens[b] : t;
+  const int row = decode ? lens[b] + t : t;
   if (row < 0 || row >= Lcap) return;
   const uint4 v = *reinterpret_cast<const uint4*>(qkv + tr * ldq + (long long)(1 + isv) * H * 64 + h * 64 + c8 * 8);
   bf16_t* dst = (isv ? vc : kc) + (((long long)b * H + h) * Lcap + row) * 64 + c8 * 8;
@@ -630,6 +636,294 @@ __global__ __launch_bounds__(SMP_THREADS) void k_decode_sample(
   advance_tail(b, bi, classes, eos, step, ctl, next_ids, tokens, lens, finished, Lcap, ticket);
 }
 
+// ============================================================ speculative decoding (verify rounds)
+// A round feeds Q = k + 1 rows per sequence — next_ids[b] and k draft tokens at positions
+// lens[b] .. lens[b] + k — through the decode step and keeps the longest prefix of the drafts that
+// the model itself would have picked.  Row j of a sequence is computed exactly as a plain step at
+// length lens[b] + j computes it (same order of every sum), so the committed tokens are the ones
+// plain decoding gives.
+
+// ------------------------------------------------------------------- embedding of a round's rows
+// out[b Q + j] = word[x_j] + pos[clamp(lens[b] + j)], x_0 = next_ids[b], x_j = draft[b, j - 1]
+__global__ __launch_bounds__(64) void k_embed2_multi(const long long* __restrict__ next_ids,
+                                                     const long long* __restrict__ draft,
+                                                     const int* __restrict__ lens, const bf16_t* __restrict__ word,
+                                                     const bf16_t* __restrict__ pos, bf16_t* __restrict__ out, int Q,
+                                                     int N, long long vocab, int max_pos) {
+  const int r = blockIdx.x, b = r / Q, j = r % Q, lane = threadIdx.x;
+  long long id = j == 0 ? next_ids[b] : draft[(long long)b * (Q - 1) + j - 1];
+  id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
+  int p = lens[b] + j;
+  p = p < 0 ? 0 : (p >= max_pos ? max_pos - 1 : p);
+  for (int c = lane * 4; c < N; c += 256) {
+    const uint2 a = *reinterpret_cast<const uint2*>(word + id * N + c);
+    const uint2 e = *reinterpret_cast<const uint2*>(pos + (long long)p * N + c);
+    uint2 o;
+    o.x = pack_bf2(lo_bf(a.x) + lo_bf(e.x), hi_bf(a.x) + hi_bf(e.x));
+    o.y = pack_bf2(lo_bf(a.y) + lo_bf(e.y), hi_bf(a.y) + hi_bf(e.y));
+    *reinterpret_cast<uint2*>(out + (long long)r * N + c) = o;
+  }
+}
+
+// ------------------------------------------------------------- decode attention, Q queries a head
+// k_attn_decode for Q <= 16 queries per (sequence, head): query j sees keys 0 .. lens[b] + j.
+// Same chunks and lane -> key map; grid (ceil(Lcap / C), B * H, ceil(Q / ATTN_QG)): a block serves a
+// group of up to ATTN_QG consecutive queries.  It loads its chunk's K and V rows ONCE (up to its last
+// query's length) and keeps them in registers; its queries then take turns.  For query j every
+// sum is k_attn_decode's at length lens[b] + j: a key past that length scores -inf, has
+// probability 0 and a zero V row by selection, a chunk wholly past it writes no partial, and the
+// fold runs over chunks 0 .. (lens[b] + j) / C.  Partials: ws[((bh Q + j) nch + ch) * ATTN_WS];
+// one ticket per (b, h, group).  The queries of a block are serial (a block-wide maximum each),
+// which is why 16 of them are spread over four blocks and not given to one
+// (profiles/r14/prompt_lookup.md).
+constexpr int ATTN_QG = 4;   // queries per block: one per wave in the partial store and the fold
+template <int C>
+__global__ __launch_bounds__(256) void k_attn_decode_multi(const bf16_t* __restrict__ q, int ldq,
+                                                           const bf16_t* __restrict__ kc,
+                                                           const bf16_t* __restrict__ vc, const int* __restrict__ lens,
+                                                           float* __restrict__ ws, unsigned* __restrict__ cnt,
+                                                           bf16_t* __restrict__ out, int ldo, int H, int Lcap, int Q,
+                                                           float scale) {
+  constexpr int R = C / 32;
+  static_assert(ATTN_QG == 4, "one query per wave of the 256-thread block");
+  __shared__ float sm[ATTN_QG][4], ss[ATTN_QG][4], so[ATTN_QG][4][64];
+  __shared__ unsigned sh_last;
+  const int ch = blockIdx.x, bh = blockIdx.y, nch = gridDim.x;
+  const int b = bh / H, h = bh % H;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int l0 = lens[b];
+  auto qlen = [&](int qi) {
+    const int l = l0 + qi;
+    return l < 0 ? 0 : (l > Lcap - 1 ? Lcap - 1 : l);
+  };
+  const int q0 = blockIdx.z * ATTN_QG, q1 = q0 + ATTN_QG < Q ? q0 + ATTN_QG : Q;   // this block's queries
+  const int nmax = qlen(q1 - 1) + 1, j0 = ch * C;
+  if (j0 < nmax) {   // block-uniform
+    const int c8 = lane & 7, kr = lane >> 3;
+    const float sc = scale * LOG2E;
+    const long long base = (long long)bh * Lcap * 64 + c8 * 8;
+    uint4 kk[R], vv[R];
+#pragma unroll
+    for (int i = 0; i < R; ++i) {
+      const int j = j0 + i * 32 + wv * 8 + kr;
+      kk[i] = j < nmax ? *reinterpret_cast<const uint4*>(kc + base + (long long)j * 64) : make_uint4(0, 0, 0, 0);
+    }
+#pragma unroll
+    for (int i = 0; i < R; ++i) {
+      const int j = j0 + i * 32 + wv * 8 + kr;
+      vv[i] = j < nmax ? *reinterpret_cast<const uint4*>(vc + base + (long long)j * 64) : make_uint4(0, 0, 0, 0);
+    }
+#pragma unroll 1
+    for (int qi = q0; qi < q1; ++qi) {
+      const int n = qlen(qi) + 1, g = qi - q0;
+      if (j0 >= n) continue;   // block-uniform: this query ends before the chunk
+      float qf[8];
+      unpack8(*reinterpret_cast<const uint4*>(q + ((long long)b * Q + qi) * ldq + h * 64 + c8 * 8), qf);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) qf[k] *= sc;
+      float s[R];
+      float mx = -INFINITY;
+#pragma unroll
+      for (int i = 0; i < R; ++i) {
+        const int j = j0 + i * 32 + wv * 8 + kr;
+        float kf[8], d = 0.f;
+        unpack8(kk[i], kf);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) d = fmaf(qf[k], kf[k], d);
+        d += __shfl_xor(d, 1, 64);
+        d += __shfl_xor(d, 2, 64);
+        d += __shfl_xor(d, 4, 64);
+        s[i] = j < n ? d : -INFINITY;
+        mx = fmaxf(mx, s[i]);
+      }
+      mx = wave_max(mx);
+      if (lane == 0) sm[g][wv] = mx;
+      __syncthreads();
+      mx = fmaxf(fmaxf(sm[g][0], sm[g][1]), fmaxf(sm[g][2], sm[g][3]));   // finite: key j0 is valid
+      float o[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, ls = 0.f;
+#pragma unroll
+      for (int i = 0; i < R; ++i) {
+        const int j = j0 + i * 32 + wv * 8 + kr;
+        const bool ok = j < n;
+        const float p = ok ? __builtin_amdgcn_exp2f(s[i] - mx) : 0.f;
+        float vf[8];
+        unpack8(vv[i], vf);
+        ls += p;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) o[k] = fmaf(p, ok ? vf[k] : 0.f, o[k]);   // a later query's row: 0, as unloaded
+      }
+#pragma unroll
+      for (int sh = 8; sh < 64; sh <<= 1) {
+        ls += __shfl_xor(ls, sh, 64);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) o[k] += __shfl_xor(o[k], sh, 64);
+      }
+      if (lane < 8) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) so[g][wv][c8 * 8 + k] = o[k];
+      }
+      if (lane == 0) ss[g][wv] = ls;
+    }
+    __syncthreads();
+    const int qi = q0 + wv, g = wv;   // wave w stores query q0 + w (ATTN_QG == waves of a block)
+    if (qi < q1 && j0 < qlen(qi) + 1) {   // wave-uniform
+      float* part = ws + (((long long)bh * Q + qi) * nch + ch) * ATTN_WS;
+      st_part(part + 2 + lane, ((so[g][0][lane] + so[g][1][lane]) + so[g][2][lane]) + so[g][3][lane]);
+      if (lane == 0) {
+        st_part(part, fmaxf(fmaxf(sm[g][0], sm[g][1]), fmaxf(sm[g][2], sm[g][3])));
+        st_part(part + 1, ((ss[g][0] + ss[g][1]) + ss[g][2]) + ss[g][3]);
+      }
+    }
+  }
+  if (!last_block(cnt + (long long)bh * gridDim.z + blockIdx.z, (unsigned)nch, &sh_last)) return;
+  const int qi = q0 + wv;
+  if (qi < q1) {
+    const float* p0 = ws + ((long long)bh * Q + qi) * nch * ATTN_WS;
+    const int nv = qlen(qi) / C + 1;   // <= nch
+    float M = -INFINITY;
+    for (int c = 0; c < nv; ++c) M = fmaxf(M, ld_part(p0 + c * ATTN_WS));
+    float S = 0.f, O = 0.f;
+    for (int c = 0; c < nv; ++c) {
+      const float w = __builtin_amdgcn_exp2f(ld_part(p0 + c * ATTN_WS) - M);
+      S = fmaf(w, ld_part(p0 + c * ATTN_WS + 1), S);
+      O = fmaf(w, ld_part(p0 + c * ATTN_WS + 2 + lane), O);
+    }
+    out[((long long)b * Q + qi) * ldo + h * 64 + lane] = f2bf(O / S);
+  }
+}
+
+// --------------------------------------------------------------------------- n-gram drafter
+// Prompt lookup: one block per sequence over its history tokens[b, 0 .. L], L = lens[b].  For
+// g = min(G, L) .. 1: the suffix of g tokens ending at L is searched at the starts s <= L - g (an
+// earlier occurrence with at least one token after it); the LARGEST such s wins — each thread keeps
+// its largest, the block takes the maximum, so the result does not depend on any arrival order.
+// The draft is the K tokens after the occurrence, the index clamped to L (the tail repeats the
+// last copied token); with no match at any g every slot is tokens[b, L].
+__global__ __launch_bounds__(256) void k_draft_lookup(const long long* __restrict__ tokens,
+                                                      const int* __restrict__ lens, long long* __restrict__ draft,
+                                                      int Lcap, int K, int G) {
+  __shared__ int sw[4];
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const long long* row = tokens + (long long)b * Lcap;
+  int L = lens[b];
+  L = L < 0 ? 0 : (L > Lcap - 1 ? Lcap - 1 : L);
+  int from = L;   // first token to copy
+  for (int g = G < L ? G : L; g >= 1; --g) {   // block-uniform
+    int best = -1;
+    for (int s = tid; s <= L - g; s += 256) {
+      bool ok = true;
+      for (int i = 0; i < g && ok; ++i) ok = row[s + i] == row[L - g + 1 + i];
+      if (ok) best = s;   // s grows: the last hit is this thread's largest
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const int ov = __shfl_xor(best, o, 64);
+      best = ov > best ? ov : best;
+    }
+    if (lane == 0) sw[wv] = best;
+    __syncthreads();
+    const int a0 = sw[0] > sw[1] ? sw[0] : sw[1], a1 = sw[2] > sw[3] ? sw[2] : sw[3];
+    best = a0 > a1 ? a0 : a1;
+    __syncthreads();   // sw is written again at the next g
+    if (best >= 0) { from = best + g; break; }
+  }
+  for (int j = tid; j < K; j += 256) {
+    const int src = from + j < L ? from + j : L;
+    draft[(long long)b * K + j] = row[src];
+  }
+}
+
+// ----------------------------------------------------------------------- verify: pick and commit
+// grid B * Q, one block per row r = b Q + j: k_decode_advance's scan (argmax, or the Gumbel key
+// with lowest column on ties) with the noise step lens[b] + j - start[b] — the step plain decoding
+// has when it reaches that position.  The picks go to pick[r] write-through; the last block of the
+// grid (ticket, as in last_block) then commits every sequence in one thread:
+//   p = lens[b]; frozen when p >= limit[b].  Otherwise pick j lands at tokens[b, p + j + 1] while
+//   that is <= limit[b]; after pick j the walk goes on only if draft[b, j] == pick j and it was
+//   not eos.  A sequence finished before the round commits eos in every slot.  next_ids[b] = the
+//   last committed token, lens[b] = p + committed.
+// stats int32 = [accepted drafts (sum), committed tokens (sum), max over b of limit - lens, 0].
+__global__ __launch_bounds__(256) void k_verify_pick(const bf16_t* __restrict__ logits, int ldl, int classes, int sample,
+                                                     const float* __restrict__ temp, const int* __restrict__ ctl,
+                                                     const int* __restrict__ start, const int* __restrict__ limit,
+                                                     const long long* __restrict__ draft, int* __restrict__ pick,
+                                                     long long* __restrict__ next_ids, long long* __restrict__ tokens,
+                                                     int* __restrict__ lens, int* __restrict__ finished,
+                                                     int* __restrict__ stats, int B, int Q, int Lcap,
+                                                     unsigned* __restrict__ ticket) {
+  __shared__ float sv[4];
+  __shared__ int si[4];
+  const int r = blockIdx.x, b = r / Q, jr = r % Q;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const unsigned seed = (unsigned)ctl[0];
+  const unsigned step = (unsigned)(lens[b] + jr - start[b]);   // read before the ticket: the commit moves lens
+  const int eos = ctl[2];
+  const float invT = sample ? 1.f / temp[0] : 1.f;
+  const unsigned sb = seed ^ ((unsigned)b * 0x9E3779B9u + 0x67756D62u);
+  const bf16_t* row = logits + (long long)r * ldl;
+  float best = -INFINITY;
+  int bi = 0x7fffffff;
+  for (int c0 = tid * 8; c0 < classes; c0 += 2048) {
+    float f[8];
+    unpack8(*reinterpret_cast<const uint4*>(row + c0), f);   // ldl % 8 == 0: the row covers c0 .. c0 + 7
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const int c = c0 + k;
+      float v = f[k];
+      if (sample) v = gumbel_key(v, invT, sb, step, (unsigned)c);
+      if (c < classes && (v > best || (v == best && c < bi))) { best = v; bi = c; }
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(best, o, 64);
+    const int oi = __shfl_xor(bi, o, 64);
+    if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
+  }
+  if (lane == 0) { sv[wv] = best; si[wv] = bi; }
+  __syncthreads();
+  if (tid != 0) return;
+  for (int k = 1; k < 4; ++k)
+    if (sv[k] > best || (sv[k] == best && si[k] < bi)) { best = sv[k]; bi = si[k]; }
+  if (bi >= classes) bi = 0;   // a row without one comparable value (all NaN)
+  __hip_atomic_store(pick + r, bi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  const unsigned tk = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (tk != gridDim.x - 1) return;
+  __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  int acc = 0, com = 0, rem = 0;
+  for (int s = 0; s < B; ++s) {
+    const int p = lens[s], lim = limit[s];
+    int m = 0;
+    if (p < lim) {
+      int fin = finished[s];
+      const bool was = eos >= 0 && fin;
+      long long last = 0;
+      for (int j = 0; j < Q; ++j) {
+        const int at = p + j + 1;
+        if (at > lim) break;
+        const int pk = __hip_atomic_load(pick + s * Q + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const long long tok = was ? (long long)eos : (long long)pk;
+        if (at >= 0 && at < Lcap) tokens[(long long)s * Lcap + at] = tok;
+        last = tok;
+        m = j + 1;
+        if (was) continue;
+        if (eos >= 0 && tok == eos) { fin = 1; break; }
+        if (j == Q - 1 || draft[(long long)s * (Q - 1) + j] != tok) break;
+      }
+      finished[s] = fin;
+      next_ids[s] = last;
+      lens[s] = p + m;
+      com += m;
+      if (!was) acc += m - 1;
+    }
+    rem = lim - (p + m) > rem ? lim - (p + m) : rem;
+  }
+  stats[0] += acc;
+  stats[1] += com;
+  stats[2] = rem;
+}
+
 }  // namespace
 
 // ========================================================================================= C ABI
@@ -637,7 +931,7 @@ KML_API int kml_kv_append(const bf16_t* qkv, int ldq, bf16_t* kc, bf16_t* vc, co
                           int Lcap, int decode, hipStream_t s) {
   if (!qkv || !kc || !vc || B < 1 || H < 1 || Lq < 1 || Lcap < 64 || Lcap % 64 || ldq % 8 || ldq < 3 * H * 64)
     return (int)hipErrorInvalidValue;
-  if (decode && (Lq != 1 || !lens)) return (int)hipErrorInvalidValue;
+  if (decode && (Lq > 16 || !lens)) return (int)hipErrorInvalidValue;
   if (!decode && Lq > Lcap) return (int)hipErrorInvalidValue;
   const long long total = (long long)B * Lq * H * 16;
   hipLaunchKernelGGL(k_kv_append, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, qkv, ldq, kc, vc, lens, B, H,
@@ -747,5 +1041,63 @@ KML_API int kml_decode_sample(const bf16_t* logits, int ldl, int classes, int sa
     return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(k_decode_sample, dim3((unsigned)B), dim3(SMP_THREADS), 0, s, logits, ldl, classes, sample, fpar,
                      ipar, info, ctl, next_ids, tokens, lens, finished, Lcap, ticket);
+  KML_LAUNCH_CHECK();
+}
+
+// ------------------------------------------------------------------- verify rounds (Q rows a sequence)
+// floats of workspace kml_attn_decode_multi needs: kml_attn_decode_ws_floats for each of Q queries
+KML_API long long kml_attn_decode_multi_ws_floats(int B, int H, int Lcap, int Q) {
+  return (long long)B * H * Q * ((Lcap + 63) / 64) * ATTN_WS;
+}
+
+// q: row b * Q + j of a [B * Q, ldq] buffer is query j of sequence b and sees keys 0 .. lens[b] + j;
+// out [B * Q, ldo] likewise.  Row j is bit-identical to kml_attn_decode at lens[b] + j.  ws from
+// kml_attn_decode_multi_ws_floats; cnt: B*H*Q zeroed tickets (one per (b, h) and group of queries is used).
+KML_API int kml_attn_decode_multi(const bf16_t* q, int ldq, const bf16_t* kc, const bf16_t* vc, const int* lens,
+                                  float* ws, unsigned* cnt, bf16_t* out, int ldo, int B, int H, int Lcap, int Q,
+                                  float scale, hipStream_t s) {
+  if (!q || !kc || !vc || !lens || !ws || !cnt || !out || B < 1 || H < 1 || Q < 1 || Q > 16 || Lcap < 64 ||
+      Lcap % 64 || ldq % 8 || ldq < H * 64 || ldo < H * 64 || (long long)B * H > 65535)
+    return (int)hipErrorInvalidValue;
+  const dim3 grid((unsigned)((Lcap + KML_DECODE_CHUNK - 1) / KML_DECODE_CHUNK), (unsigned)(B * H),
+                  (unsigned)((Q + ATTN_QG - 1) / ATTN_QG));
+  hipLaunchKernelGGL(k_attn_decode_multi<KML_DECODE_CHUNK>, grid, dim3(256), 0, s, q, ldq, kc, vc, lens, ws, cnt, out,
+                     ldo, H, Lcap, Q, scale);
+  KML_LAUNCH_CHECK();
+}
+
+// out [B * Q, N]: row b * Q + j = word[x_j] + pos[lens[b] + j], x_0 = next_ids[b], x_j = draft[b, j - 1]
+// (draft int64 [B, Q - 1]; may be null when Q == 1)
+KML_API int kml_embed2_multi(const long long* next_ids, const long long* draft, const int* lens, const bf16_t* word,
+                             const bf16_t* pos, bf16_t* out, int B, int Q, int N, long long vocab, int max_pos,
+                             hipStream_t s) {
+  if (!next_ids || !lens || !word || !pos || !out || B < 1 || Q < 1 || Q > 16 || (Q > 1 && !draft) || N < 4 || N % 4 ||
+      vocab < 1 || max_pos < 1)
+    return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_embed2_multi, dim3((unsigned)(B * Q)), dim3(64), 0, s, next_ids, draft, lens, word, pos, out, Q,
+                     N, vocab, max_pos);
+  KML_LAUNCH_CHECK();
+}
+
+// draft int64 [B, K] from the history tokens[b, 0 .. lens[b]] (tokens int64 [B, Lcap]); G: longest n-gram tried
+KML_API int kml_draft_lookup(const long long* tokens, const int* lens, long long* draft, int B, int Lcap, int K, int G,
+                             hipStream_t s) {
+  if (!tokens || !lens || !draft || B < 1 || Lcap < 1 || K < 1 || G < 1) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_draft_lookup, dim3((unsigned)B), dim3(256), 0, s, tokens, lens, draft, Lcap, K, G);
+  KML_LAUNCH_CHECK();
+}
+
+// logits [B * Q, ldl]; start / limit int32 [B]; draft int64 [B, Q - 1] (may be null when Q == 1); pick int32
+// [B * Q] (written); stats int32 [4] (accumulated); ticket: one zeroed counter
+KML_API int kml_verify_pick(const bf16_t* logits, int ldl, int classes, int sample, const float* temp, const int* ctl,
+                            const int* start, const int* limit, const long long* draft, int* pick,
+                            long long* next_ids, long long* tokens, int* lens, int* finished, int* stats, int B, int Q,
+                            int Lcap, unsigned* ticket, hipStream_t s) {
+  if (!logits || !ctl || !start || !limit || !pick || !next_ids || !tokens || !lens || !finished || !stats ||
+      !ticket || B < 1 || Q < 1 || Q > 16 || (Q > 1 && !draft) || classes < 1 || ldl % 8 || ldl < classes || Lcap < 1 ||
+      (sample && !temp))
+    return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_verify_pick, dim3((unsigned)(B * Q)), dim3(256), 0, s, logits, ldl, classes, sample, temp, ctl,
+                     start, limit, draft, pick, next_ids, tokens, lens, finished, stats, B, Q, Lcap, ticket);
   KML_LAUNCH_CHECK();
 }

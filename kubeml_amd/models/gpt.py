@@ -15,7 +15,9 @@
   cross-entropy kernels in place;
 * inference: ``generate`` / ``prefill`` / ``decode_step`` on a :class:`~kubeml_amd.nn.KVCache` —
   the prompt through the kernels above, then one captured step per token on the decode kernels
-  (csrc/kernels/decode.hip: cache append, one-query attention, skinny GEMMs, sampling).
+  (csrc/kernels/decode.hip: cache append, one-query attention, skinny GEMMs, sampling);
+  ``generate(prompt_lookup_num_tokens=k)`` / ``draft_lookup`` / ``verify_step``: speculative
+  decoding, k n-gram drafts verified per captured round of k + 1 rows, same tokens as without.
 
 FFN activation: the erf GELU of the GEMM epilogue (HF ``activation_function="gelu"``); GPT-2's
 tanh approximation (``gelu_new``) has no epilogue yet.
@@ -26,7 +28,7 @@ import torch
 import torch.nn as tnn
 from torch.autograd import Function
 
-from ..nn.decode import KVCache, filter_logits
+from ..nn.decode import KVCache, filter_logits, lookup_draft_reference
 from ..nn.flat import grad_storage_of, shadow_of
 from ..nn.modules import Linear, cross_entropy
 from ..nn.transformer import Dropout, LayerNorm, RNGState, SelfAttention, _bf, gather_rows
@@ -394,7 +396,7 @@ class GPT2LMHeadModel(tnn.Module):
 
     @torch.no_grad()
     def generate(self, ids, attention_mask=None, max_new_tokens=32, temperature=0.0, eos_token_id=None, seed=0,
-                 top_k=0, top_p=1.0, repetition_penalty=1.0):
+                 top_k=0, top_p=1.0, repetition_penalty=1.0, prompt_lookup_num_tokens=0, max_matching_ngram_size=2):
         """Continue each right-padded prompt by ``max_new_tokens`` tokens: greedy at
         ``temperature == 0``, else Gumbel-max sampling reproducible from ``seed``.  HF's processor
         chain runs on the device ahead of the pick: ``repetition_penalty`` (1: off) over the prompt
@@ -402,7 +404,17 @@ class GPT2LMHeadModel(tnn.Module):
         off; whole classes of equal value).  A sequence that
         draws ``eos_token_id`` keeps emitting it.  Returns int64 ``[B, Lprompt_max +
         max_new_tokens]``: row b is its prompt, its new tokens, then ``eos_token_id`` (0 without
-        one) up to the common width."""
+        one) up to the common width.
+
+        ``prompt_lookup_num_tokens = k >= 1`` turns on prompt-lookup speculative decoding (HF's
+        option of that name): an n-gram lookup in each sequence's own history (n-grams of up to
+        ``max_matching_ngram_size`` tokens) drafts ``k`` tokens and one round of ``k + 1`` rows per
+        sequence verifies them (:meth:`draft_lookup`, :meth:`verify_step`), so a round emits 1 to
+        ``k + 1`` tokens per sequence.  The result is, element for element, what the same call
+        returns with ``k = 0``, greedy or sampled; ``last_generate_stats`` then holds ``rounds``,
+        ``accepted`` (draft tokens accepted) and ``tokens`` (tokens the rounds committed), both
+        summed over the sequences.  Limits: ``B <= 4``, ``B * (k + 1) <= 16``, no ``top_k`` /
+        ``top_p`` / ``repetition_penalty``."""
         tr = self.transformer
         B, L = ids.shape
         if max_new_tokens < 1:
@@ -413,6 +425,10 @@ class GPT2LMHeadModel(tnn.Module):
         if int(plen.max()) + max_new_tokens > tr.max_pos:
             raise ValueError(f"generate: prompt {int(plen.max())} + {max_new_tokens} new tokens exceeds max_pos "
                              f"{tr.max_pos}")
+        k = _draft_count(prompt_lookup_num_tokens, max_matching_ngram_size)
+        if k:
+            return self._generate_lookup(ids, attention_mask, plen, max_new_tokens, temperature, eos_token_id, seed,
+                                         top_k, top_p, repetition_penalty, k, int(max_matching_ngram_size))
         Lcap = -(-(L + max_new_tokens) // 64) * 64
         sample = temperature > 0
         caches = self.__dict__.setdefault("_kml_decode_caches", {})
@@ -437,6 +453,223 @@ class GPT2LMHeadModel(tnn.Module):
         end = (plen + max_new_tokens).to(out.device)
         out.masked_fill_(torch.arange(W, device=out.device)[None] >= end[:, None], fill)
         return out
+
+    # ------------------------------------------------------------------ speculative decoding
+    # A verify round feeds q = k + 1 rows per sequence — next_ids[b] and k draft tokens at positions
+    # lens[b] .. lens[b] + k — and commits the longest prefix the model itself would have picked.
+    # Row j is computed exactly as the plain step at length lens[b] + j computes it (skinny GEMMs
+    # whose rows do not depend on the row count, attention with k_attn_decode's order of sums, the
+    # noise step of that position), so the tokens are plain decoding's, bit for bit.  K / V rows of
+    # rejected drafts stay in the cache: the next round overwrites them before a query reads them.
+
+    def draft_lookup(self, cache, k, max_ngram=2):
+        """Prompt-lookup drafts for the next verify round: int64 ``[B, k]`` on the cache's device,
+        an n-gram lookup in ``cache.tokens[b, 0 .. lens[b]]`` (``nn.lookup_draft_reference`` is the
+        rule).  With ``k == cache.draft_tokens`` the result is the cache's own draft buffer."""
+        own = cache.draft if cache.draft is not None and k == cache.draft_tokens else None
+        if cache.lens.is_cuda:
+            from ..ops import decode as D
+            return D.draft_lookup(cache.tokens, cache.lens, k, max_ngram, out=own)
+        d = lookup_draft_reference(cache.tokens, cache.lens, k, max_ngram)
+        return d if own is None else own.copy_(d)
+
+    @torch.no_grad()
+    def verify_step(self, cache, draft_ids):
+        """One verify round on a cache prepared with ``reset(draft_tokens=k)`` and prefilled:
+        feeds ``next_ids[b], draft_ids[b, 0], ..., draft_ids[b, k-1]`` at positions ``lens[b] ..
+        lens[b] + k``, then accepts and commits on the device (``ops.decode.verify_pick`` has the
+        rule): ``tokens``, ``next_ids``, ``lens``, ``finished`` and ``cache.stats`` advance.  Any
+        drafter may supply ``draft_ids`` (int64 ``[B, k]``).  Returns the logits ``[B * (k + 1),
+        vocab (padded to 8 on the GPU)]``, row ``b * (k + 1) + j`` for position ``lens[b] + j``."""
+        k = cache.draft_tokens
+        if k < 1:
+            raise ValueError("verify_step: the cache was not reset with draft_tokens >= 1")
+        if draft_ids.dtype != torch.int64 or tuple(draft_ids.shape) != (cache.B, k):
+            raise ValueError(f"verify_step: draft_ids must be int64 [{cache.B}, {k}], got {draft_ids.dtype} "
+                             f"{tuple(draft_ids.shape)}")
+        if draft_ids.data_ptr() != cache.draft.data_ptr():
+            cache.draft.copy_(draft_ids)
+        if cache.lens.is_cuda:
+            return self._replay_round(cache)
+        return self._round_cpu(cache)
+
+    def _round(self, cache):
+        """The launches of a GPU verify round, :meth:`_step` on ``B * q`` rows."""
+        from ..ops import decode as D
+        tr = self.transformer
+        q = cache.draft_tokens + 1
+        e = D.embed2_multi(cache.next_ids, cache.draft, cache.lens, shadow_of(tr.wte.weight), shadow_of(tr.wpe.weight))
+        x, s = tr.h[0].ln_1.add_norm(e)
+        for i, (blk, ln) in enumerate(self._closers()):
+            qkv = blk.attn.qkv.forward_small(x, skinny=True)
+            # append BEFORE attention: query j reads the rows lens[b] .. lens[b] + j this round wrote
+            # (and nothing past them: what a rejected draft of an earlier round left there is dead)
+            D.kv_append(qkv, cache.k[i], cache.v[i], q, lens=cache.lens)
+            ctx = D.attn_decode_multi(qkv, cache.k[i], cache.v[i], cache.lens, q, ws=cache.ws_multi)
+            x2, s = blk.ln_2.add_norm(blk.attn.out.forward_small(ctx, skinny=True), residual=s)
+            m = blk.mlp.c_proj.forward_small(blk.mlp.c_fc.forward_small(x2, act="gelu", skinny=True), skinny=True)
+            x, s = ln.add_norm(m, residual=s)
+        # skinny at every row count: above 4 rows forward_small would send the tied decoder elsewhere
+        logits = self.lm_head.forward_small(x, keep_pad=True, skinny=True)
+        D.verify_pick(logits, self.vocab, cache.ctl, cache.temp, cache.start, cache.limit, cache.draft, cache.pick,
+                      cache.next_ids, cache.tokens, cache.lens, cache.finished, cache.stats, sample=cache.sample)
+        return logits
+
+    def _replay_round(self, cache):
+        """The GPU verify round as one captured graph per (cache, sampling, q), as :meth:`_replay`
+        keeps the plain step: drafts, start, limit, seed, temperature and eos are device memory."""
+        key = ("verify", bool(cache.sample), cache.draft_tokens + 1)
+        ent = cache._graphs.get(key)
+        if ent is None:
+            from ..engine.step import capture_graph
+            state = [cache.lens, cache.tokens, cache.next_ids, cache.finished, cache.stats]
+            keep = [t.clone() for t in state]
+            cur = torch.cuda.current_stream()
+            side = torch.cuda.Stream()
+            side.wait_stream(cur)
+            with torch.cuda.stream(side):
+                self._round(cache)   # the replay re-appends the same K / V rows: idempotent
+            cur.wait_stream(side)
+            for t, kept in zip(state, keep):
+                t.copy_(kept)
+            torch.cuda.synchronize()
+            g = torch.cuda.CUDAGraph()
+            with capture_graph(g, capture_error_mode="thread_local"):
+                logits = self._round(cache)
+            ent = cache._graphs[key] = (g, logits)
+        ent[0].replay()
+        return ent[1]
+
+    def _round_cpu(self, cache):
+        """The CPU twin of a verify round.  The rows of a sequence go through :meth:`_step` one
+        position at a time, with the shapes of plain decoding, so that row j has the bits of the
+        plain step at that position whatever the BLAS does with another row count."""
+        B, q = cache.B, cache.draft_tokens + 1
+        feed = torch.cat([cache.next_ids[:, None], cache.draft], 1)
+        base, nxt = cache.lens.clone(), cache.next_ids.clone()
+        rows = []
+        for j in range(q):
+            cache.lens.copy_(base + j)
+            cache.next_ids.copy_(feed[:, j])
+            rows.append(self._step(cache, False))   # appends at lens[b] + j, then attends up to it
+        cache.lens.copy_(base)
+        cache.next_ids.copy_(nxt)
+        logits = torch.stack(rows, 1)   # [B, q, vocab]
+        if cache.sample:
+            T = float(cache.temp[0])
+            pick = torch.empty((B, q), dtype=torch.int64)
+            for b in range(B):
+                for j in range(q):
+                    # the draw plain decoding consumes for this sequence's new token of that index
+                    u = cache.uniforms_cpu(int(base[b]) + j - int(cache.start[b]), logits[:, 0].shape)[b]
+                    pick[b, j] = (logits[b, j].double() / T - torch.log(-torch.log(u))).argmax(-1)
+        else:
+            pick = logits.argmax(-1)
+        cache.pick.copy_(pick.reshape(-1).to(torch.int32))
+        _verify_commit_cpu(cache)
+        cache.forget_uniforms_cpu(int((cache.lens - cache.start).min()))
+        return logits.reshape(B * q, -1)
+
+    def _generate_lookup(self, ids, attention_mask, plen, max_new_tokens, temperature, eos_token_id, seed, top_k,
+                         top_p, repetition_penalty, k, max_ngram):
+        tr = self.transformer
+        B, L = ids.shape
+        q = k + 1
+        if B > 4:
+            raise ValueError(f"generate: prompt lookup takes batches up to 4, got {B} (above that plain decoding "
+                             "sends the tied decoder to another GEMM and identity with it cannot be promised)")
+        if B * q > 16:
+            raise ValueError(f"generate: {B} sequences x ({k} draft tokens + 1) = {B * q} rows; a verify round "
+                             "takes at most 16")
+        if top_k != 0 or top_p != 1.0 or repetition_penalty != 1.0:
+            raise ValueError("generate: prompt lookup does not run behind top_k, top_p or repetition_penalty "
+                             "(the filtered sampler takes one row per sequence)")
+        Lcap = -(-(L + max_new_tokens + q) // 64) * 64
+        sample = temperature > 0
+        caches = self.__dict__.setdefault("_kml_decode_caches", {})
+        stamp = shadow_of(tr.wte.weight).data_ptr() if ids.is_cuda else 0
+        key = (B, Lcap, sample, ids.device, tr.wte.weight.dtype, stamp, q)
+        cache = caches.get(key)
+        if cache is None:
+            cache = caches[key] = self.new_cache(B, Lcap, ids.device)
+        cache.reset(seed=seed, temperature=temperature, eos_token_id=eos_token_id, start=plen - 1,
+                    limit=plen - 1 + max_new_tokens, draft_tokens=k)
+        if ids.is_cuda:
+            for p in self.parameters():
+                shadow_of(p)
+        self.prefill(ids, attention_mask, cache)
+        # How the host learns that every sequence is at its limit: the commit leaves max over b of
+        # limit[b] - lens[b] in cache.stats[2].  A round moves a sequence by at most q, so
+        # ceil(remaining / q) rounds are needed whatever is accepted; only then is stats read
+        # again (16 bytes) — at most one read per round, far fewer when little is accepted.
+        rounds, remaining, st = 0, max_new_tokens - 1, [0, 0, 0, 0]
+        while remaining > 0:
+            n = -(-remaining // q)
+            for _ in range(n):
+                self.verify_step(cache, self.draft_lookup(cache, k, max_ngram))
+            rounds += n
+            st = cache.stats.tolist()
+            remaining = st[2]
+        self.last_generate_stats = {"rounds": rounds, "accepted": st[0], "tokens": st[1]}
+        W = L + max_new_tokens
+        out = cache.tokens[:, :W].clone()
+        fill = 0 if eos_token_id is None else int(eos_token_id)
+        end = (plen + max_new_tokens).to(out.device)
+        out.masked_fill_(torch.arange(W, device=out.device)[None] >= end[:, None], fill)
+        return out
+
+
+def _draft_count(k, max_ngram):
+    """``prompt_lookup_num_tokens`` as an int (None: 0), both options checked."""
+    k = 0 if k is None else k
+    if isinstance(k, bool) or not isinstance(k, (int, float)) or int(k) != k or k < 0:
+        raise ValueError(f"prompt_lookup_num_tokens must be an integer >= 0, got {k!r}")
+    if isinstance(max_ngram, bool) or not isinstance(max_ngram, (int, float)) or int(max_ngram) != max_ngram \
+            or max_ngram < 1:
+        raise ValueError(f"max_matching_ngram_size must be an integer >= 1, got {max_ngram!r}")
+    return int(k)
+
+
+def _verify_commit_cpu(cache):
+    """Stock-torch twin of the commit of ``kml_verify_pick`` on a CPU cache whose ``pick`` holds
+    the rows' choices: per sequence, pick j lands at ``tokens[b, lens[b] + j + 1]`` while that index
+    is ``<= limit[b]`` and every earlier draft equalled its pick without being eos; a sequence
+    finished before the round commits eos in every slot; one at its limit is frozen."""
+    eos = int(cache.ctl[2])
+    B, q, Lcap = cache.B, cache.draft_tokens + 1, cache.Lcap
+    pick, draft = cache.pick.reshape(B, q).tolist(), cache.draft.tolist()
+    acc = com = rem = 0
+    for b in range(B):
+        p, lim = int(cache.lens[b]), int(cache.limit[b])
+        m = 0
+        if p < lim:
+            fin = int(cache.finished[b])
+            was = eos >= 0 and fin != 0
+            last = 0
+            for j in range(q):
+                at = p + j + 1
+                if at > lim:
+                    break
+                tok = eos if was else pick[b][j]
+                if 0 <= at < Lcap:
+                    cache.tokens[b, at] = tok
+                last, m = tok, j + 1
+                if was:
+                    continue
+                if eos >= 0 and tok == eos:
+                    fin = 1
+                    break
+                if j == q - 1 or draft[b][j] != tok:
+                    break
+            cache.finished[b] = fin
+            cache.next_ids[b] = last
+            cache.lens[b] = p + m
+            com += m
+            acc += 0 if was else m - 1
+        rem = max(rem, lim - (p + m))
+    cache.stats[0] += acc
+    cache.stats[1] += com
+    cache.stats[2] = rem
 
 
 def _advance_cpu(cache, logits, gen):

@@ -349,15 +349,18 @@ class Linear(tnn.Module):
             y._kml_linear = self   # raw linear output: a consuming cross_entropy may sum our bias grad
         return y
 
-    def forward_small(self, x, act: Optional[str] = None, keep_pad: bool = False):
+    def forward_small(self, x, act: Optional[str] = None, keep_pad: bool = False, skinny: bool = False):
         """Inference-only forward for M <= 16 rows (a decode step: M = batch): no autograd, the
         bf16 shadow weights, the skinny GEMM of ops/decode.py with bias and erf-GELU in its
         epilogue.  Shapes listed in ``_SMALL_EXISTING`` (from the row count at which the skinny
-        kernel measured slower) and fused-ReLU layers take :meth:`forward` instead."""
+        kernel measured slower) and fused-ReLU layers take :meth:`forward` instead.  ``skinny``:
+        ignore ``_SMALL_EXISTING`` and take the skinny GEMM at every row count up to 16 — a row of
+        its result does not depend on the row count, which a verify round of the speculative
+        ``generate`` relies on."""
         with torch.no_grad():
             rows = x.shape[0] if x.dim() == 2 else 0
             if (not _on_gpu(x) or self.fused_relu or
-                    rows >= _SMALL_EXISTING.get((self.out_pad, self.in_pad), 17)):
+                    (not skinny and rows >= _SMALL_EXISTING.get((self.out_pad, self.in_pad), 17))):
                 return self.forward(x, act=act, keep_pad=keep_pad)
             if act not in (None, "gelu"):
                 raise ValueError(f"forward_small: act {act!r}")

@@ -1,6 +1,8 @@
 """Launchers for the decode kernels (csrc/kernels/decode.hip): KV-cache append, one-query
 attention over the cache, the skinny (M <= 16) GEMM, the embedding at the device lengths and
-the next-token choice (plain, or behind a repetition penalty, top-k and top-p).
+the next-token choice (plain, or behind a repetition penalty, top-k and top-p); and the verify
+round of speculative decoding: multi-row embedding and append, multi-query attention, the n-gram
+drafter, pick and commit.
 
 Everything a step needs that changes per token — sequence lengths, seed / step, temperature,
 eos, the sampling filters — is read from device memory, so one captured step replays for every token.  All launches
@@ -48,15 +50,15 @@ def _chk_lens(lens, B):
 def kv_append(qkv, kc, vc, Lq, lens=None):
     """Copy the K and V columns of a fused ``[B*Lq, 3*H*64]`` QKV buffer into the cache
     ``kc, vc [B, H, Lcap, 64]``.  ``lens`` None: prefill, row t of sequence b goes to cache row
-    t.  ``lens`` given (``Lq == 1``): the row of sequence b goes to cache row ``lens[b]``.  Rows
-    at or past Lcap are dropped."""
+    t.  ``lens`` given (``Lq <= 16``: 1 in a plain step, the rows of a verify round otherwise):
+    row t of sequence b goes to cache row ``lens[b] + t``.  Rows at or past Lcap are dropped."""
     B, H, Lcap = _chk_cache(kc, vc)
     _chk_view(qkv, "qkv")
     if qkv.shape[0] != B * Lq or qkv.shape[1] != 3 * H * 64:
         raise ValueError(f"qkv: expected [{B * Lq}, {3 * H * 64}], got {tuple(qkv.shape)}")
     if lens is not None:
-        if Lq != 1:
-            raise ValueError("kv_append: decode mode appends one row per sequence (Lq == 1)")
+        if not 1 <= Lq <= 16:
+            raise ValueError("kv_append: decode mode appends 1..16 rows per sequence")
         _chk_lens(lens, B)
     elif Lq > Lcap:
         raise ValueError(f"kv_append: {Lq} prompt rows do not fit a cache of {Lcap}")
@@ -244,3 +246,131 @@ def decode_sample(logits, classes, ctl, fpar, ipar, next_ids, tokens, lens, fini
              int(bool(sample)), _p(fpar), _p(ipar), _p(info), _p(ctl), _p(next_ids), _p(tokens), _p(lens),
              _p(finished), B, tokens.shape[1], _p(ticket), _s())
     return info
+
+
+# ------------------------------------------------------------------ verify rounds (speculative decoding)
+def attn_decode_multi_workspace(B, H, Lcap, Q, device):
+    """fp32 workspace for the chunk partials of ``Q`` queries per (sequence, head)."""
+    return torch.empty(int(HIP.raw("kml_attn_decode_multi_ws_floats", B, H, Lcap, Q)), dtype=F32, device=device)
+
+
+def _chk_draft(draft, B, K, name="draft"):
+    _chk(draft, I64, name, ndim=2)
+    if draft.shape != (B, K) or not draft.is_contiguous():
+        raise ValueError(f"{name}: expected a contiguous [{B}, {K}] int64 tensor, got {tuple(draft.shape)}")
+
+
+def attn_decode_multi(q, kc, vc, lens, Q, ws=None, out=None, scale=None):
+    """:func:`attn_decode` for ``Q <= 16`` queries per (b, h) in one pass over the cache: row
+    ``b * Q + j`` of ``q [B*Q, >= H*64]`` sees cache rows ``0 .. lens[b] + j`` and its output row is
+    bit-identical to :func:`attn_decode` called with ``lens[b] + j``.  Returns ``[B*Q, H*64]`` bf16."""
+    B, H, Lcap = _chk_cache(kc, vc)
+    _chk_view(q, "q")
+    if not 1 <= Q <= 16:
+        raise ValueError(f"attn_decode_multi: Q = {Q} queries; the kernel takes 1..16")
+    if q.shape[0] != B * Q or q.shape[1] < H * 64:
+        raise ValueError(f"q: expected a [{B * Q}, >= {H * 64}] view, got {tuple(q.shape)}")
+    _chk_lens(lens, B)
+    need = int(HIP.raw("kml_attn_decode_multi_ws_floats", B, H, Lcap, Q))
+    if ws is None:
+        ws = torch.empty(need, dtype=F32, device=q.device)
+    _chk(ws, F32, "ws")
+    if ws.numel() < need:
+        raise ValueError(f"ws: {ws.numel()} floats, {Q} queries on this cache need {need}")
+    if out is None:
+        out = torch.empty((B * Q, H * 64), dtype=BF16, device=q.device)
+    _chk_view(out, "out")
+    if out.shape != (B * Q, H * 64):
+        raise ValueError(f"out: expected [{B * Q}, {H * 64}], got {tuple(out.shape)}")
+    scale = 1.0 / math.sqrt(64) if scale is None else scale
+    cnt = _COUNTERS.take(q.device, B * H * Q)
+    HIP.call("kml_attn_decode_multi", "p i p p p p p p i i i i i f s", _p(q), q.stride(0), _p(kc), _p(vc), _p(lens),
+             _p(ws), _p(cnt), _p(out), out.stride(0), B, H, Lcap, int(Q), float(scale), _s())
+    return out
+
+
+def embed2_multi(next_ids, draft, lens, word, pos, out=None):
+    """The embedding of a verify round: ``out[b*Q + j] = word[x_j] + pos[lens[b] + j]`` with
+    ``x_0 = next_ids[b]`` and ``x_j = draft[b, j - 1]`` (``draft`` int64 ``[B, Q - 1]``); the
+    position is clamped to the table as :func:`embed2_at` clamps it."""
+    _chk(next_ids, I64, "next_ids", ndim=1)
+    B = next_ids.numel()
+    _chk(draft, I64, "draft", ndim=2)
+    K = draft.shape[1]
+    _chk_draft(draft, B, K)
+    if not 1 <= K <= 15:
+        raise ValueError(f"embed2_multi: {K} draft tokens; a round takes 1..15")
+    _chk_lens(lens, B)
+    _chk(word, BF16, "word", ndim=2)
+    _chk(pos, BF16, "pos", ndim=2)
+    N = word.shape[1]
+    if pos.shape[1] != N or N % 4:
+        raise ValueError(f"embed2_multi: tables {tuple(word.shape)} / {tuple(pos.shape)}")
+    Q = K + 1
+    if out is None:
+        out = torch.empty((B * Q, N), dtype=BF16, device=next_ids.device)
+    _chk(out, BF16, "out", ndim=2)
+    if out.shape != (B * Q, N):
+        raise ValueError(f"out: expected [{B * Q}, {N}]")
+    HIP.call("kml_embed2_multi", "p p p p p p i i i l i s", _p(next_ids), _p(draft), _p(lens), _p(word), _p(pos),
+             _p(out), B, Q, N, word.shape[0], pos.shape[0], _s())
+    return out
+
+
+def draft_lookup(tokens, lens, k, max_ngram=2, out=None):
+    """Prompt-lookup drafter: ``k`` draft tokens per sequence from its own history ``tokens[b, 0 ..
+    lens[b]]`` (:func:`kubeml_amd.nn.lookup_draft_reference` is the rule, in stock torch).
+    Returns int64 ``[B, k]``."""
+    _chk(tokens, I64, "tokens", ndim=2)
+    B, Lcap = tokens.shape
+    _chk_lens(lens, B)
+    if int(k) != k or k < 1 or int(max_ngram) != max_ngram or max_ngram < 1:
+        raise ValueError(f"draft_lookup: k = {k}, max_ngram = {max_ngram} (integers >= 1)")
+    if not tokens.is_contiguous():
+        raise ValueError("draft_lookup: tokens must be contiguous")
+    if out is None:
+        out = torch.empty((B, int(k)), dtype=I64, device=tokens.device)
+    _chk_draft(out, B, int(k), "out")
+    HIP.call("kml_draft_lookup", "p p p i i i i s", _p(tokens), _p(lens), _p(out), B, Lcap, int(k), int(max_ngram),
+             _s())
+    return out
+
+
+def verify_pick(logits, classes, ctl, temp, start, limit, draft, pick, next_ids, tokens, lens, finished, stats,
+                sample):
+    """The last launch of a verify round.  ``logits [B*Q, >= classes]`` bf16: row ``b*Q + j`` is
+    the model's output for position ``lens[b] + j``.  Every row is picked as
+    :func:`decode_advance` picks (argmax, or Gumbel-max at ``temp[0]``) with the noise step
+    ``lens[b] + j - start[b]``; then, per sequence, pick j is committed to ``tokens[b, lens[b] + j
+    + 1]`` while that index is ``<= limit[b]`` and every earlier draft matched its pick
+    (``draft[b, j-1] == pick[b, j-1]``) without being eos; ``next_ids``, ``lens`` and ``finished``
+    advance accordingly.  ``pick`` int32 ``[B*Q]`` receives every row's choice; ``stats`` int32
+    ``[4]`` accumulates ``[accepted drafts, committed tokens]`` and holds ``max(limit - lens)``."""
+    _chk_view(logits, "logits")
+    R, ldw = logits.shape
+    B = lens.numel()
+    if B < 1 or R % B or not 2 <= R // B <= 16:
+        raise ValueError(f"verify_pick: {R} rows for {B} sequences (2..16 rows each)")
+    Q = R // B
+    if not 1 <= classes <= ldw:
+        raise ValueError(f"verify_pick: {classes} classes in rows of {ldw}")
+    _chk(ctl, I32, "ctl", ndim=1)
+    _chk(temp, F32, "temp", ndim=1)
+    _chk(next_ids, I64, "next_ids", ndim=1)
+    _chk(tokens, I64, "tokens", ndim=2)
+    _chk(finished, I32, "finished", ndim=1)
+    _chk(pick, I32, "pick", ndim=1)
+    _chk(stats, I32, "stats", ndim=1)
+    _chk_lens(lens, B)
+    _chk_lens(start, B)
+    _chk_lens(limit, B)
+    _chk_draft(draft, B, Q - 1)
+    if (ctl.numel() < 4 or temp.numel() < 1 or next_ids.numel() != B or finished.numel() != B or
+            tokens.shape[0] != B or not tokens.is_contiguous() or pick.numel() < R or stats.numel() < 4):
+        raise ValueError("verify_pick: state tensors do not match the batch")
+    if logits.stride(0) < -(-classes // 8) * 8:
+        raise ValueError("verify_pick: logits rows shorter than the classes padded to 8")
+    ticket = _COUNTERS.take(logits.device, 1)
+    HIP.call("kml_verify_pick", "p i i i p p p p p p p p p p p i i i p s", _p(logits), logits.stride(0), int(classes),
+             int(bool(sample)), _p(temp), _p(ctl), _p(start), _p(limit), _p(draft), _p(pick), _p(next_ids),
+             _p(tokens), _p(lens), _p(finished), _p(stats), B, Q, tokens.shape[1], _p(ticket), _s())

@@ -4,6 +4,7 @@ existing small-M route per shape, and the decode attention over its keys-per-chu
 
     python tools/bench_gpt_decode.py [--rounds 5] [--iters 20] [--new 256] [--out FILE.json]
                                      [--top-k K] [--top-p P] [--repetition-penalty R] [--skip-kernels]
+                                     [--prompt-lookup K[,K...]]
 
 * decode: B in {1, 4, 16}, prompt 128, ``--new`` tokens.  (a) the captured step of ``generate``
   (``decode_step`` replays, timed between device events after the prefill); (b) the same step
@@ -21,6 +22,9 @@ existing small-M route per shape, and the decode attention over its keys-per-chu
 * attention: B = 4, H = 12, Lcap = 1024, n in {128, 512, 1023} keys, chunk in {64, 128, 256, 512}.
 * floor: the bf16 weight bytes one token reads, over the 6.3 TB/s the microarchitecture notes give
   as the achievable HBM rate — derived, not measured.
+* ``--prompt-lookup K[,K...]``: only the speculative-decoding measurements (:func:`prompt_lookup`):
+  the verify round of K + 1 rows beside the plain step (``K = 0``: the plain step alone), oracle and
+  n-gram drafts, and the multi-query decode attention beside separate one-query launches.
 
 Prints one JSON line.
 """
@@ -45,6 +49,171 @@ class _Everything:
         return 0
 
 
+def prompt_lookup(a, ks, graphed, alternate):
+    """``--prompt-lookup K[,K...]``: speculative decoding with k draft tokens per verify round.
+
+    * attention: B = 1, H = 12, ``kml_attn_decode_multi`` at q in {4, 8, 16} queries against q
+      separate ``kml_attn_decode`` launches, lens in {256, 1024}; captured, alternating.
+    * model (GPT-2 small, random weights, prompt 128, ``--new`` tokens), for B in {1, 4} and every K
+      with B (K + 1) <= 16, all variants alternating inside every round of one process:
+      ``step`` — the plain captured decode step (what K = 0 runs; the baseline); ``round`` — one
+      verify round (replays of the captured round on constant drafts: the launches do not depend
+      on what is accepted); ``oracle`` — a whole decode with teacher-forced drafts (the plain run's
+      own continuation, gathered by three stock-torch launches per round, which are inside the
+      time): every draft accepted, the ceiling; ``break_even`` = round / step, the tokens per
+      round and sequence above which speculation wins.
+    * realised: ``generate`` with the n-gram drafter against plain ``generate`` (host clock,
+      prefill included) on a prompt that repeats a block of 16 tokens and on random token ids.
+      K = 0 reports the plain step only."""
+    import torch
+    from kubeml_amd.ops import decode as D
+    dev = torch.device("cuda", 0)
+    BF = torch.bfloat16
+    gen = torch.Generator(device=dev).manual_seed(0)
+    out = {"ks": ks}
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) * 1e3
+
+    def stat(v, nd=2):
+        return {"us": round(statistics.median(v), nd), "min": round(min(v), nd), "max": round(max(v), nd)}
+
+    if not a.skip_kernels:
+        B, H, Lcap = 1, 12, 1152
+        kc = torch.randn(B, H, Lcap, 64, device=dev, generator=gen).to(BF)
+        vc = torch.randn(B, H, Lcap, 64, device=dev, generator=gen).to(BF)
+        ws1 = D.attn_decode_workspace(B, H, Lcap, dev)
+        o1 = torch.empty(B, H * 64, dtype=BF, device=dev)
+        attn = []
+        for n in (256, 1024):
+            lens = torch.full((B,), n, dtype=torch.int32, device=dev)
+            for q in (4, 8, 16):
+                rows = torch.randn(B * q, 3 * H * 64, device=dev, generator=gen).to(BF)
+                wsm = D.attn_decode_multi_workspace(B, H, Lcap, q, dev)
+                om = torch.empty(B * q, H * 64, dtype=BF, device=dev)
+                each = [lens + j for j in range(q)]
+
+                def multi():
+                    for _ in range(a.iters):
+                        D.attn_decode_multi(rows, kc, vc, lens, q, ws=wsm, out=om)
+
+                def separate():
+                    for _ in range(a.iters):
+                        for j in range(q):
+                            D.attn_decode(rows[j:j + 1], kc, vc, each[j], ws=ws1, out=o1)
+                r = alternate({"multi": graphed(multi), "separate": graphed(separate)}, a.iters)
+                attn.append({"lens": n, "q": q, "B": B, "H": H, **r})
+                print(json.dumps(attn[-1]), file=sys.stderr, flush=True)
+        out["attention"] = attn
+    if a.skip_model:
+        return out
+
+    from kubeml_amd.models.gpt import gpt2_small
+    from kubeml_amd.nn import flatten_module
+    torch.manual_seed(0)
+    model = gpt2_small(dropout=0.0).to(dev).eval()
+    flatten_module(model)
+    prompt, new = 128, a.new
+    W = prompt + new
+    cases = []
+    for Bm in (1, 4):
+        for K in ks:
+            if Bm * (K + 1) > 16:
+                continue
+            q = K + 1
+            ids = torch.randint(0, 50257, (Bm, prompt), device=dev, generator=gen)
+            plain = model.new_cache(Bm, W + q, dev)
+
+            def arm_plain():
+                plain.reset()
+                model.prefill(ids, None, plain)
+            arm_plain()
+            model.decode_step(plain)   # capture
+
+            def steps():
+                for _ in range(new - 1):
+                    model.decode_step(plain)
+            case = {"B": Bm, "K": K, "prompt": prompt, "new": new}
+            if K == 0:
+                v = []
+                for _ in range(a.rounds):
+                    arm_plain()
+                    v.append(timed(steps) / (new - 1))
+                case["step"] = stat(v)
+                cases.append(case)
+                print(json.dumps(case), file=sys.stderr, flush=True)
+                continue
+            ref = model.generate(ids, max_new_tokens=new)
+            spec = model.new_cache(Bm, W + q, dev)
+            start = torch.full((Bm,), prompt - 1)
+            ar = torch.arange(1, q, device=dev)[None]
+
+            def arm():
+                spec.reset(start=start, limit=start + new, draft_tokens=K)
+                model.prefill(ids, None, spec)
+            arm()
+            model.verify_step(spec, spec.draft)   # capture
+            nr = max(1, (new - 1) // q)           # constant (zero) drafts: a sequence moves 1 .. q per round
+
+            def rounds():
+                for _ in range(nr):
+                    model.verify_step(spec, spec.draft)
+            no = -(-(new - 1) // q)
+
+            def oracle():
+                for _ in range(no):
+                    draft = ref.gather(1, (spec.lens[:, None].long() + ar).clamp(max=W - 1))
+                    model.verify_step(spec, draft)
+            t = {"step": [], "round": [], "oracle": []}
+            for _ in range(a.rounds):
+                arm_plain()
+                t["step"].append(timed(steps) / (new - 1))
+                arm()
+                t["round"].append(timed(rounds) / nr)
+                arm()
+                t["oracle"].append(timed(oracle))
+            st = spec.stats.tolist()
+            case["step"], case["round"] = stat(t["step"]), stat(t["round"])
+            case["break_even_tokens_per_round"] = round(case["round"]["us"] / case["step"]["us"], 3)
+            us = statistics.median(t["oracle"])
+            case["oracle"] = {"rounds": no, "accepted": st[0], "tokens": st[1],
+                              "exact": bool(torch.equal(spec.tokens[:, :W], ref)), "decode_us": round(us, 1),
+                              "tokens_per_s": round(Bm * (new - 1) / us * 1e6, 1),
+                              "plain_tokens_per_s": round(Bm / case["step"]["us"] * 1e6, 1)}
+            block = torch.randint(0, 50257, (Bm, 16), device=dev, generator=gen).repeat(1, prompt // 16)
+            for name, p in (("repeated_block", block), ("random_ids", ids)):
+                want = model.generate(p, max_new_tokens=new)
+                got = model.generate(p, max_new_tokens=new, prompt_lookup_num_tokens=K)
+                tp, tl = [], []
+                for _ in range(a.rounds):
+                    for v, kw in ((tp, {}), (tl, {"prompt_lookup_num_tokens": K})):
+                        torch.cuda.synchronize()
+                        t0 = time.perf_counter()
+                        model.generate(p, max_new_tokens=new, **kw)
+                        torch.cuda.synchronize()
+                        v.append(time.perf_counter() - t0)
+                s = model.last_generate_stats
+                case[name] = {"exact": bool(torch.equal(want, got)), **s,
+                              "accepted_per_round": round(s["accepted"] / s["rounds"], 3),
+                              "tokens_per_round_and_sequence": round(s["tokens"] / s["rounds"] / Bm, 3),
+                              "plain_call_s": round(statistics.median(tp), 4),
+                              "lookup_call_s": round(statistics.median(tl), 4),
+                              "plain_tokens_per_s": round(Bm * new / statistics.median(tp), 1),
+                              "lookup_tokens_per_s": round(Bm * new / statistics.median(tl), 1)}
+            cases.append(case)
+            print(json.dumps(case), file=sys.stderr, flush=True)
+            del plain, spec
+            model.__dict__.pop("_kml_decode_caches", None)
+    out["model"] = cases
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=5)
@@ -55,6 +224,8 @@ def main():
     ap.add_argument("--top-k", type=int, default=0)
     ap.add_argument("--top-p", type=float, default=1.0)
     ap.add_argument("--repetition-penalty", type=float, default=1.0)
+    ap.add_argument("--prompt-lookup", default=None, metavar="K[,K...]",
+                    help="only the prompt-lookup (speculative decoding) measurements, for these draft counts")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import torch
@@ -101,6 +272,15 @@ def main():
 
     res = {"device": torch.cuda.get_device_name(0), "chunk": D.attn_decode_chunk(), "rounds": a.rounds,
            "iters": a.iters}
+    if a.prompt_lookup is not None:
+        res["prompt_lookup"] = prompt_lookup(a, [int(k) for k in a.prompt_lookup.split(",")], graphed, alternate)
+        line = json.dumps(res)
+        print(line)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                f.write(line + "\n")
+        return
     filt = dict(top_k=a.top_k, top_p=a.top_p, repetition_penalty=a.repetition_penalty)
     filtered = a.top_k != 0 or a.top_p != 1.0 or a.repetition_penalty != 1.0
     res["filters"] = filt if filtered else None
