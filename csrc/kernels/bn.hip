@@ -596,6 +596,10 @@ __global__ __launch_bounds__(NT) void k_bn_bwd_apply_fin(
 // bank conflicts (k_bn_bwd_apply_v 44 %, k_bn_apply_v 38 %; profiles/r6/bn_lds.md).
 __host__ __device__ constexpr int bn_tstride(int ch8) { return ch8 + (((4 - ch8) % 32) + 32) % 32; }
 __host__ __device__ constexpr int bn_tslots(int C) { return 8 * bn_tstride(C >> 3); }
+// partial rows go through EarlyRows (one pass over the float4 columns of a [2C] row) when they fit
+// the block, through sum_partial_rows otherwise; kml_bn_plan reports the same choice (a macro: the
+// register-resident kernels compile to the same code as with the expression written out)
+#define BN_EARLY_ROWS(C, nt) ((C) / 2 <= (nt))
 
 // ---------------------------------------------------------------------------------------
 // Register-resident apply kernels (the default).  Each thread owns V 16-byte chunks
@@ -649,7 +653,7 @@ __device__ __forceinline__ void bn_apply_body(const BnApArgs& p, int bid, int nb
   const int T = nblk * NT;
   const int i0 = bid * NT + (int)threadIdx.x;
   const bool parts = mode == 0 && stats_rows > 0;
-  const bool early = parts && C / 2 <= NT;
+  const bool early = parts && BN_EARLY_ROWS(C, NT);
   EarlyRows er;
   if (early) er.issue(stats, stats_rows, 2 * C, NT);
   uint4 xv[V], rv[V];
@@ -815,7 +819,7 @@ __device__ __forceinline__ void bn_bwd_apply_body(const BnbArgs& p, int bid, int
   const int n8 = (int)(M * C / 8);
   const int T = nblk * NT;
   const int i0 = bid * NT + (int)threadIdx.x;
-  const bool early = C / 2 <= NT;
+  const bool early = BN_EARLY_ROWS(C, NT);
   EarlyRows er;
   if (early) er.issue(part, G, 2 * C, NT);
   uint4 dv[V], xv[V], yv[V];
@@ -1356,8 +1360,9 @@ static int launch_bwd_apply_fin(const bf16_t* dy, const bf16_t* y, const bf16_t*
 
 // stats_rows > 0: stats is [stats_rows][2C] partial sums (conv epilogue), summed here
 // fold rows [G][W] -> ws [ceil(G / FOLD_R)][W] when they are large; returns the rows to use
+static bool fold_needed(int G, int W, bool has_ws) { return has_ws && (long long)G * W * 4 > FOLD_BYTES; }
 static const float* maybe_fold(const float* part, int& G, int W, float* ws, hipStream_t s) {
-  if (!ws || (long long)G * W * 4 <= FOLD_BYTES) return part;
+  if (!fold_needed(G, W, ws != nullptr)) return part;
   const int NG = (G + FOLD_R - 1) / FOLD_R;
   hipLaunchKernelGGL(k_rows_fold, dim3((unsigned)((W / 4 + 63) / 64), (unsigned)NG), dim3(256), 0, s, part, ws, G, W,
                      FOLD_R);
@@ -1386,7 +1391,7 @@ KML_API int kml_bn_apply(const bf16_t* x, const float* stats, int stats_rows, co
   if (C % 8) return (int)hipErrorInvalidValue;
   if (g_bn_rec) {   // recording: only the single-launch register path pairs
     g_bn_rec->ok = false;
-    if (!reg_ok(M, C) || (mode == 0 && stats_rows > 0 && fold_ws && (long long)stats_rows * 2 * C * 4 > FOLD_BYTES))
+    if (!reg_ok(M, C) || (mode == 0 && stats_rows > 0 && fold_needed(stats_rows, 2 * C, fold_ws != nullptr)))
       return 0;
   }
   if (mode == 0 && stats_rows > 0) stats = maybe_fold(stats, stats_rows, 2 * C, fold_ws, s);
@@ -1494,7 +1499,9 @@ KML_API int kml_bn_bwd(const bf16_t* dy, const bf16_t* y, const bf16_t* x, const
     return launch_bwd_apply_fin(dy, y, x, mean, rstd, gamma, part, gf, dgamma, dbeta, dx, dres, M, C, accumulate, s);
   }
   const int g = bwd_blocks(M, C, &rpb);
-  // these two variants reduce INTO dgamma / dbeta (the apply kernel reads them back)
+  // these two variants reduce INTO dgamma / dbeta (the apply kernel reads them back): with
+  // accumulate they need dgamma / dbeta zero on entry, or dx is computed from the earlier gradient
+  // too (ops/kernels.py bn_bwd reduces into a zeroed scratch pair and adds it afterwards)
   if (!accumulate) {  // zeroing kernels, not memset nodes (util.hip kml_zero)
     int e = kml_zero(dgamma, C * (long long)sizeof(float), s);
     if (!e) e = kml_zero(dbeta, C * (long long)sizeof(float), s);
@@ -1575,6 +1582,38 @@ KML_API int kml_bn_bwd_pair(const long long* q1, const long long* q2, hipStream_
     if (rc) return rc;
   }
   return 0;
+}
+
+// Host-only: which kernel variant the launchers above choose, from the same predicates (reg_ok,
+// pick_v, v_grid, fold_needed, wide_sum, BN_EARLY_ROWS); launches nothing.  kind 0: kml_bn_apply
+// in training mode with G = stats_rows (0: final sums; eval mode plans as G = 0); 1: kml_bn_bwd
+// with the fused reduce (G is ignored: the rows are its own reduction blocks); 2:
+// kml_bn_bwd_apply_partial over G rows.  Returns -1 for arguments the launcher rejects, else
+//   bit 0 register-resident kernel (else the LDS-coefficient fallback), bits 1..4 its V (V << 1),
+//   bit 5 pipelined (more than one batch per thread), bit 6 EarlyRows row sum,
+//   bit 7 1024-thread wide-sum fallback, bit 8 k_rows_fold runs first.
+KML_API int kml_bn_plan(int kind, long long M, int C, int G, int has_fold_ws) {
+  if (C <= 0 || C % 8 || M <= 0 || kind < 0 || kind > 2) return -1;
+  if (kind != 0 && C / 8 > TPB) return -1;
+  if (kind == 2 && G <= 0) return -1;
+  int rpb;
+  if (kind == 1) { G = bwd_blocks(M, C, &rpb); has_fold_ws = 1; }
+  if (G < 0) G = 0;
+  int plan = 0;
+  if (G > 0 && fold_needed(G, 2 * C, has_fold_ws != 0)) {
+    plan |= 256;
+    G = (G + FOLD_R - 1) / FOLD_R;
+  }
+  if (reg_ok(M, C)) {
+    const long long n8 = M * C / 8;
+    const int V = pick_v(n8, kind == 0 ? 8 : 4);
+    plan |= 1 | (V << 1);
+    if (n8 > (long long)v_grid(n8, V) * TPB * V) plan |= 32;
+    if (G > 0 && BN_EARLY_ROWS(C, TPB)) plan |= 64;
+  } else if (G > 0 && wide_sum(G, C)) {
+    plan |= 128;
+  }
+  return plan;
 }
 
 KML_API int kml_relu_fwd(const bf16_t* x, bf16_t* y, long long n, hipStream_t s) {

@@ -1271,6 +1271,23 @@ def _fold_ws(G, C, dev):
     return torch.empty(n * 2 * C, dtype=F32, device=dev) if n > 0 else None
 
 
+# kml_bn_plan bits: which kernel variant the BN launchers choose for a shape
+BN_PLAN_REG, BN_PLAN_PIPE, BN_PLAN_EARLY, BN_PLAN_WIDE, BN_PLAN_FOLD = 1, 32, 64, 128, 256
+BN_PLAN_APPLY, BN_PLAN_BWD, BN_PLAN_BWD_PARTIAL = 0, 1, 2
+
+
+def bn_plan(kind, M, C, G=0, fold_ws=True):
+    """Host-only query (launches nothing): the variant bn_apply (kind BN_PLAN_APPLY, G = stats_rows;
+    eval mode plans as G = 0), bn_bwd with the fused reduce (BN_PLAN_BWD) or bn_bwd(partial=(.., G))
+    (BN_PLAN_BWD_PARTIAL) runs at [M][C] -> dict(reg, v, pipe, early, wide, fold).  ``v`` is 0 on
+    the fallback path."""
+    m = HIP.fn("kml_bn_plan", "i l i i i")(int(kind), int(M), int(C), int(G), int(bool(fold_ws)))
+    if m < 0:
+        raise ValueError(f"kml_bn_plan: invalid arguments kind={kind} M={M} C={C} G={G}")
+    return dict(reg=bool(m & BN_PLAN_REG), v=(m >> 1) & 15, pipe=bool(m & BN_PLAN_PIPE),
+                early=bool(m & BN_PLAN_EARLY), wide=bool(m & BN_PLAN_WIDE), fold=bool(m & BN_PLAN_FOLD))
+
+
 def bn_apply(x, stats, gamma, beta, y=None, res=None, save_mean=None, save_rstd=None, run_mean=None,
              run_var=None, eps=1e-5, momentum=0.1, relu=False, training=True, stats_rows=0):
     _chk(x, BF16, "x")
@@ -1362,6 +1379,19 @@ def bn_bwd(dy, y, x, mean, rstd, gamma, dgamma, dbeta, dx=None, dres=None, parti
         ws = torch.empty(nws, dtype=F32, device=x.device)
         if _BN_REDUCE == "ticket":
             cnt = _COUNTERS.take(x.device, 1)
+    if _BN_REDUCE != "fused" and accumulate:
+        # The ticket / atomic variants reduce INTO dgamma / dbeta and their apply kernel reads the
+        # totals back as this pass's sums: onto a non-zero gradient, dx would carry the earlier
+        # gradient.  Reduce into a scratch pair instead and add it afterwards (launched at once,
+        # also inside a bn_bwd_pair block: these variants never pair).
+        sums = torch.empty(2 * C, dtype=F32, device=x.device)
+        args = (_p(dy), _p(y), _p(x), _p(mean), _p(rstd), _p(gamma), _p(sums[C:]), _p(sums[:C]), _p(dx), _p(dres),
+                _p(ws), _p(cnt), M, C, 0)
+        with _Riding(rider):
+            HIP.call("kml_bn_bwd", "p p p p p p p p p p p p l i i s", *args, _s())
+        dgamma.add_(sums[C:])
+        dbeta.add_(sums[:C])
+        return dx
     args = (_p(dy), _p(y), _p(x), _p(mean), _p(rstd), _p(gamma), _p(dgamma), _p(dbeta), _p(dx), _p(dres), _p(ws),
             _p(cnt), M, C, int(bool(accumulate)))
     if record:   # the record holds every operand (the reduction workspace included) until the launch
