@@ -52,6 +52,27 @@ __device__ __forceinline__ float kml_gelu_grad(float x) {
          x * 0.3989422804014327f * __builtin_amdgcn_exp2f(-0.5f * 1.4426950408889634f * x * x);
 }
 
+// tanh-approximated GELU (HF "gelu_new" / torch approximate="tanh") in its sigmoid form:
+// 0.5 x (1 + tanh u) = x s, s = sigmoid(2u), u = sqrt(2/pi) (x + 0.044715 x^3) — one v_exp_f32
+// and one rcp, no tanhf, no branch.  The argument is built from x clamped to +-12, where
+// exp2 has already left the fp32 range: s is exactly 1 (x >= 12) or exactly 0 (x <= -12,
+// rcp(inf)), so x^3 never overflows and every finite x gives a finite value; the factor x
+// itself is not clamped, so NaN propagates.
+__device__ __forceinline__ float kml_gelu_tanh_sig(float xc) {
+  constexpr float k2 = (float)(2.0 * 0.7978845608028654 * 1.4426950408889634);   // 2 sqrt(2/pi) log2(e)
+  const float z = xc * fmaf(xc * xc, -0.044715f * k2, -k2);                       // -2 u log2(e)
+  return __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(z));
+}
+__device__ __forceinline__ float kml_gelu_tanh(float x) {
+  return x * kml_gelu_tanh_sig(fminf(fmaxf(x, -12.f), 12.f));
+}
+// s + x s (1 - s) 2 sqrt(2/pi) (1 + 0.134145 x^2); past the clamp s (1 - s) is exactly 0
+__device__ __forceinline__ float kml_gelu_tanh_grad(float x) {
+  const float xc = fminf(fmaxf(x, -12.f), 12.f);
+  const float s = kml_gelu_tanh_sig(xc);
+  return fmaf(x * s * (1.f - s), 1.5957691216057308f * fmaf(0.134145f, xc * xc, 1.f), s);
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

@@ -203,7 +203,7 @@ __global__ __launch_bounds__(256) void k_attn_decode(const bf16_t* __restrict__ 
 // the other rows.  Two shapes of block: 16 waves (the layer weights: K of 768 .. 3072 spread over
 // the waves of one block, so N >= 1536 needs no block split) and 4 waves (vocabulary-sized N:
 // thousands of blocks, 12 or 13 per CU, where a 16-wave block's tail would leave CUs idle).
-constexpr int SK_NONE = 0, SK_GELU = 1;
+constexpr int SK_NONE = 0, SK_GELU = 1, SK_GELU_TANH = 2;   // SK_GELU: erf form; SK_GELU_TANH: kml_gelu_tanh
 
 template <int NW, int U>
 __global__ __launch_bounds__(NW * 64) void k_gemm_skinny(const bf16_t* __restrict__ x, int ldx,
@@ -252,6 +252,7 @@ __global__ __launch_bounds__(NW * 64) void k_gemm_skinny(const bf16_t* __restric
     if (m >= M || n >= N) return;
     if (bias) v += bias[n];
     if (act == SK_GELU) v = kml_gelu(v);
+    else if (act == SK_GELU_TANH) v = kml_gelu_tanh(v);
     y[(long long)m * ldy + n] = f2bf(v);
   };
   float* mine = ws + ((long long)nb * S + sp) * E;
@@ -994,7 +995,7 @@ KML_API int kml_gemm_skinny_splits(int N, int K) {
 KML_API int kml_gemm_skinny(const bf16_t* x, int ldx, const bf16_t* w, int ldw, const float* bias, bf16_t* y, int ldy,
                             int M, int N, int K, int act, int splits, float* ws, unsigned* cnt, hipStream_t s) {
   if (!x || !w || !y || M < 1 || M > 16 || N < 1 || K < 8 || K % 8 || ldx % 8 || ldw % 8 || ldx < K || ldw < K ||
-      ldy < N || (act != SK_NONE && act != SK_GELU) || splits < 0)
+      ldy < N || (act != SK_NONE && act != SK_GELU && act != SK_GELU_TANH) || splits < 0)
     return (int)hipErrorInvalidValue;
   const SkinnyPlan p = skinny_plan(N, K, splits);
   if (p.S > 1 && (!ws || !cnt)) return (int)hipErrorInvalidValue;

@@ -21,7 +21,7 @@
 //   chunk ^= row & 7 (ds_read_b128), KS tiles [64][R] a row-bit permutation read with the
 //   transposing ds_read_b64_tr_b16 — both conflict-free (tools/lds_banks.py).
 // * The MFMA is issued with the B fragment as its first operand, so a lane's accumulator
-//   holds 4 consecutive OUTPUT COLUMNS of one output row: the epilogue (bias, erf-GELU,
+//   holds 4 consecutive OUTPUT COLUMNS of one output row: the epilogue (bias, erf/tanh GELU,
 //   bf16 pack, or fp32 beta / atomic accumulate) stores 8 or 16 contiguous bytes per lane
 //   straight from registers — no LDS staging pass.
 // * Out-of-range rows / K columns read a zero page instead of branching (counted vmcnt
@@ -42,6 +42,8 @@ constexpr int GEMM_ADD_C2 = 3;  // act code: C = bf16(bf16(A B) + c2)
 // the epilogue of the dgrad that produced d(activation), c2 = the saved pre-activation; the
 // column sums of C (the FFN1 bias gradient) go to colpart[M / 256][N] (one row per M-tile)
 constexpr int GEMM_GELU_BWD = 4;
+constexpr int GEMM_GELU_TANH = 2;      // forward act code: tanh-approximated GELU (kml_gelu_tanh)
+constexpr int GEMM_GELU_TANH_BWD = 7;  // GEMM_GELU_BWD with gelu_tanh'(c2)
 // act code (layout 0, bf16 out): BatchNorm statistics of the output in the epilogue — a 1x1
 // stride-1 convolution run as this GEMM (ops.kernels.conv_fwd's GEMM route) writes one partial
 // row [sum(N) | sumsq(N)] per M-tile to colpart[M / BM][2 N], the layout of the implicit-GEMM
@@ -65,7 +67,7 @@ struct GemmArgs {
   const bf16_t* zp;    // >= 16 zero bytes
   long long lda, ldb, ldc;
   int M, N, K;
-  int act;             // 0 none, 1 erf-GELU
+  int act;             // 0 none, 1 erf-GELU, 2 tanh-GELU, or one of the GEMM_* codes above
   float beta;
   int kchunk;          // split-K slice length (multiple of 64)
   float* colpart;      // GEMM_GELU_BWD: per-M-tile column sums of the output; GEMM_STATS / BNF: [M/BM][2N]
@@ -350,6 +352,9 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, f32x4_t (&acc)[
         if (g.act == 1) {
 #pragma unroll
           for (int r = 0; r < 4; ++r) v[r] = gelu_erf(v[r]);
+        } else if (g.act == GEMM_GELU_TANH) {   // act is uniform over the grid
+#pragma unroll
+          for (int r = 0; r < 4; ++r) v[r] = kml_gelu_tanh(v[r]);
         }
         uint2 p;
         p.x = pack_bf2(v[0], v[1]);
@@ -406,6 +411,9 @@ __device__ __forceinline__ void gemm_store4(const GemmArgs& g, int m, int n, flo
     if (g.act == 1) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) v[r] = gelu_erf(v[r]);
+    } else if (g.act == GEMM_GELU_TANH) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) v[r] = kml_gelu_tanh(v[r]);
     }
     *reinterpret_cast<uint2*>(static_cast<bf16_t*>(g.c) + off) = make_uint2(pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3]));
   } else {
@@ -1142,11 +1150,13 @@ __global__ __launch_bounds__(NT) void k_gemm4(GemmArgs g) {
 // lands every half-tile before the barrier that precedes its first read by either group
 // (derivation in the comment of k_gemm8 below).
 //
-// Epilogue (bf16 out): bias / erf-GELU in registers, the tile staged through the (now
+// Epilogue (bf16 out): bias / erf or tanh GELU in registers, the tile staged through the (now
 // idle) LDS with a row-XOR swizzle, then 16-byte row-contiguous global stores (512 B per
 // half-wave): full cache lines instead of 16 rows x 32 B per store instruction.
 // ---------------------------------------------------------------------------------------
-template <bool A_KC, bool B_KC, int OUT, int BN = 256>
+// TANH (OUT 0): the instantiation launch8 picks for act GEMM_GELU_TANH / GEMM_GELU_TANH_BWD — the
+// tanh GELU where the other applies the erf GELU, so neither carries a branch on the other's form.
+template <bool A_KC, bool B_KC, int OUT, int BN = 256, bool TANH = false>
 __global__ __launch_bounds__(NT) void k_gemm8(GemmArgs g) {
   static_assert(BN == 256 || BN == 192, "k_gemm8: BN is 256 or 192");
   constexpr int HT = 256 * 32 * 2;  // half-tile slot bytes (a 192-row B half-tile uses 12 of 16 KB)
@@ -1298,7 +1308,13 @@ __global__ __launch_bounds__(NT) void k_gemm8(GemmArgs g) {
           const int col = wn * WN + j * 16 + 4 * (lane >> 4);
           float v0 = acc[i][j][0] + bias4[j].x, v1 = acc[i][j][1] + bias4[j].y;
           float v2 = acc[i][j][2] + bias4[j].z, v3 = acc[i][j][3] + bias4[j].w;
-          if (act) { v0 = gelu_erf(v0); v1 = gelu_erf(v1); v2 = gelu_erf(v2); v3 = gelu_erf(v3); }
+          if constexpr (TANH) {
+            if (act) {
+              v0 = kml_gelu_tanh(v0); v1 = kml_gelu_tanh(v1); v2 = kml_gelu_tanh(v2); v3 = kml_gelu_tanh(v3);
+            }
+          } else {
+            if (act) { v0 = gelu_erf(v0); v1 = gelu_erf(v1); v2 = gelu_erf(v2); v3 = gelu_erf(v3); }
+          }
           uint2 p;
           p.x = pack_bf2(v0, v1);
           p.y = pack_bf2(v2, v3);
@@ -1310,7 +1326,8 @@ __global__ __launch_bounds__(NT) void k_gemm8(GemmArgs g) {
       __syncthreads();
     };
     // LDS tile -> 16-byte row-contiguous global stores (512 B per half-wave)
-    const bool gbwd = g.act == GEMM_GELU_BWD, gst = BN == 256 && g.act == GEMM_STATS;
+    const bool gbwd = g.act == (TANH ? GEMM_GELU_TANH_BWD : GEMM_GELU_BWD);
+    const bool gst = BN == 256 && g.act == GEMM_STATS;
     float csum[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};  // GELU_BWD / STATS: this thread's 8 columns
     float csq[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};   // STATS: sums of squares
     auto store = [&](bf16_t* dst) {
@@ -1327,7 +1344,11 @@ __global__ __launch_bounds__(NT) void k_gemm8(GemmArgs g) {
             unsigned ow[4];
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-              ow[k] = pack_bf2(lo_bf(dw[k]) * kml_gelu_grad(lo_bf(pw[k])), hi_bf(dw[k]) * kml_gelu_grad(hi_bf(pw[k])));
+              if constexpr (TANH)
+                ow[k] = pack_bf2(lo_bf(dw[k]) * kml_gelu_tanh_grad(lo_bf(pw[k])),
+                                 hi_bf(dw[k]) * kml_gelu_tanh_grad(hi_bf(pw[k])));
+              else
+                ow[k] = pack_bf2(lo_bf(dw[k]) * kml_gelu_grad(lo_bf(pw[k])), hi_bf(dw[k]) * kml_gelu_grad(hi_bf(pw[k])));
               csum[2 * k] += lo_bf(ow[k]);
               csum[2 * k + 1] += hi_bf(ow[k]);
             }
@@ -1358,7 +1379,7 @@ __global__ __launch_bounds__(NT) void k_gemm8(GemmArgs g) {
       stage(false);
       store(g.c2);
     }
-    stage(g.act == 1);
+    stage(g.act == (TANH ? GEMM_GELU_TANH : 1));
     store(static_cast<bf16_t*>(g.c));
     if (BN == 256 && gbwd) {  // column sums: 16 threads (tid >> 5) share each 8-column chunk; fixed order
       float* red = reinterpret_cast<float*>(smem);
@@ -1398,13 +1419,19 @@ __global__ __launch_bounds__(NT) void k_gemm8(GemmArgs g) {
 
 template <bool A_KC, bool B_KC, int OUT, int BN = 256>
 int launch8(GemmArgs g, int splits, hipStream_t s) {
-  if (BN != 256 && g.act == GEMM_GELU_BWD) return (int)hipErrorInvalidValue;
+  if (BN != 256 && (g.act == GEMM_GELU_BWD || g.act == GEMM_GELU_TANH_BWD)) return (int)hipErrorInvalidValue;
   splits = splits < 1 ? 1 : splits;
   int chunk = (g.K + splits - 1) / splits;
   chunk = ((chunk + 63) / 64) * 64;
   g.kchunk = chunk > 0 ? chunk : 64;
   const int z = g.K > 0 ? (g.K + g.kchunk - 1) / g.kchunk : 1;
   dim3 grid((g.N + BN - 1) / BN, (g.M + 255) / 256, z);
+  if constexpr (OUT == 0) {
+    if (g.act == GEMM_GELU_TANH || g.act == GEMM_GELU_TANH_BWD) {
+      hipLaunchKernelGGL((k_gemm8<A_KC, B_KC, OUT, BN, true>), grid, dim3(NT), 0, s, g);
+      KML_LAUNCH_CHECK();
+    }
+  }
   hipLaunchKernelGGL((k_gemm8<A_KC, B_KC, OUT, BN>), grid, dim3(NT), 0, s, g);
   KML_LAUNCH_CHECK();
 }
@@ -1503,7 +1530,7 @@ KML_API int kml_gemm(const bf16_t* a, long long lda, const bf16_t* b, long long 
   // tile beat hipBLASLt alone (71 vs 88 us) but not inside the step (profiles/r5/bert_qkv_rowpass.md)
   g.rowpass = 0; g.grp_out = nullptr; g.grp_cnt = nullptr; g.grp_tiles = 0;
   if (M <= 0 || N <= 0) return 0;
-  if (act == GEMM_GELU_BWD) return (int)hipErrorInvalidValue;  // kml_gemm_dgrad_gelu
+  if (act == GEMM_GELU_BWD || act == GEMM_GELU_TANH_BWD) return (int)hipErrorInvalidValue;  // kml_gemm_dgrad_gelu*
   if (layout == 0 && out == 0) return by_tile<true, true, 0>(g, tile, 1, s);
   if (layout == 0 && out == 1) return by_tile<true, true, 1>(g, tile, 1, s);
   if (layout == 0 && out == 2) return by_tile<true, true, 2>(g, tile, splits, s);
@@ -1662,17 +1689,28 @@ KML_API int kml_gemm_dgrad_bnf(const bf16_t* a, long long lda, const bf16_t* b, 
 // dgrad (layout 1, 256x256 phase tile) with the GELU backward of the layer that produced its
 // operand's forward input in the epilogue: c = bf16(bf16(dy W) * gelu'(pre)), colpart[M/256][N]
 // = per-M-tile column sums of c (summed in order by the caller: the FFN1 bias gradient).
-KML_API int kml_gemm_dgrad_gelu(const bf16_t* a, long long lda, const bf16_t* b, long long ldb, bf16_t* c,
-                                long long ldc, const bf16_t* pre, float* colpart, const bf16_t* zp, int M, int N,
-                                int K, hipStream_t s) {
+static int dgrad_gelu_launch(int act, const bf16_t* a, long long lda, const bf16_t* b, long long ldb, bf16_t* c,
+                             long long ldc, const bf16_t* pre, float* colpart, const bf16_t* zp, int M, int N, int K,
+                             hipStream_t s) {
   if (M <= 0 || N <= 0) return 0;
   if (N % 8 || ldc % 8 || !pre || !colpart) return (int)hipErrorInvalidValue;
   GemmArgs g;
   g.a = a; g.b = b; g.c = c; g.c2 = const_cast<bf16_t*>(pre); g.bias = nullptr; g.zp = zp;
   g.lda = lda; g.ldb = ldb; g.ldc = ldc;
-  g.M = M; g.N = N; g.K = K; g.act = GEMM_GELU_BWD; g.beta = 0.f; g.kchunk = K; g.colpart = colpart;
+  g.M = M; g.N = N; g.K = K; g.act = act; g.beta = 0.f; g.kchunk = K; g.colpart = colpart;
   g.by = nullptr; g.bc = nullptr; g.bmean = nullptr; g.brstd = nullptr; g.mask_out = 0; g.rowpass = 0; g.grp_out = nullptr; g.grp_cnt = nullptr; g.grp_tiles = 0;
   return launch8<true, false, 0>(g, 1, s);
+}
+KML_API int kml_gemm_dgrad_gelu(const bf16_t* a, long long lda, const bf16_t* b, long long ldb, bf16_t* c,
+                                long long ldc, const bf16_t* pre, float* colpart, const bf16_t* zp, int M, int N,
+                                int K, hipStream_t s) {
+  return dgrad_gelu_launch(GEMM_GELU_BWD, a, lda, b, ldb, c, ldc, pre, colpart, zp, M, N, K, s);
+}
+// the same with the tanh-approximated GELU's derivative: c = bf16(bf16(dy W) * gelu_tanh'(pre))
+KML_API int kml_gemm_dgrad_gelu_tanh(const bf16_t* a, long long lda, const bf16_t* b, long long ldb, bf16_t* c,
+                                     long long ldc, const bf16_t* pre, float* colpart, const bf16_t* zp, int M,
+                                     int N, int K, hipStream_t s) {
+  return dgrad_gelu_launch(GEMM_GELU_TANH_BWD, a, lda, b, ldb, c, ldc, pre, colpart, zp, M, N, K, s);
 }
 
 // Deterministic split-K weight gradient: dw[M][N] = beta * dw + sum_k A^T B (layout 2), each

@@ -1,6 +1,6 @@
 // transformer.hip — the non-GEMM ops of a BERT-style encoder for gfx950:
 //   LayerNorm fwd (+ fused residual add) / bwd (dgamma, dbeta two-level deterministic),
-//   GELU (erf) fwd/bwd, counter-based dropout fwd/bwd (mask regenerated, never stored),
+//   GELU (erf or tanh form) fwd/bwd, counter-based dropout fwd/bwd (mask regenerated, never stored),
 //   fused embedding (word + position + token type) gather fwd / scatter-add bwd,
 //   row gather / scatter (masked-LM positions).
 // Rows are bf16 vectors of length N (N % 4 == 0); one wave per row, 8-byte lane loads;
@@ -264,22 +264,34 @@ __global__ __launch_bounds__(256) void k_colreduce(const float* __restrict__ par
   }
 }
 
-// ------------------------------------------------------------------------------ GELU (erf form)
-__device__ __forceinline__ float gelu(float x) { return kml_gelu(x); }
-__device__ __forceinline__ float gelu_grad(float x) { return kml_gelu_grad(x); }
+// ------------------------------------------------------------------------------ GELU
+// TANH: the tanh approximation (kml_gelu_tanh) instead of the erf form — a compile-time variant
+// of every kernel below, chosen by the export that launches it
+template <bool TANH>
+__device__ __forceinline__ float gelu(float x) {
+  if constexpr (TANH) return kml_gelu_tanh(x);
+  else return kml_gelu(x);
+}
+template <bool TANH>
+__device__ __forceinline__ float gelu_grad(float x) {
+  if constexpr (TANH) return kml_gelu_tanh_grad(x);
+  else return kml_gelu_grad(x);
+}
 
+template <bool TANH>
 __global__ void k_gelu_fwd(const bf16_t* __restrict__ x, bf16_t* __restrict__ y, long long n4) {
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
     float f[4];
     ld4(x + i * 4, f);
 #pragma unroll
-    for (int k = 0; k < 4; ++k) f[k] = gelu(f[k]);
+    for (int k = 0; k < 4; ++k) f[k] = gelu<TANH>(f[k]);
     st4(y + i * 4, f);
   }
 }
 
 // 16-byte rows of 8 elements, two independent loads in flight per thread (the GELU pass
 // after a library GEMM writes the pre-activation: 2 x 100 MB for BERT-base's FFN1)
+template <bool TANH>
 __global__ void k_gelu_fwd8(const uint4* __restrict__ x, uint4* __restrict__ y, long long n8) {
   const long long stride = (long long)gridDim.x * blockDim.x;
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n8; i += 2 * stride) {
@@ -290,7 +302,7 @@ __global__ void k_gelu_fwd8(const uint4* __restrict__ x, uint4* __restrict__ y, 
       const unsigned w[4] = {v.x, v.y, v.z, v.w};
       unsigned o[4];
 #pragma unroll
-      for (int k = 0; k < 4; ++k) o[k] = pack_bf2(gelu(lo_bf(w[k])), gelu(hi_bf(w[k])));
+      for (int k = 0; k < 4; ++k) o[k] = pack_bf2(gelu<TANH>(lo_bf(w[k])), gelu<TANH>(hi_bf(w[k])));
       return make_uint4(o[0], o[1], o[2], o[3]);
     };
     y[i] = g(a);
@@ -298,6 +310,7 @@ __global__ void k_gelu_fwd8(const uint4* __restrict__ x, uint4* __restrict__ y, 
   }
 }
 
+template <bool TANH>
 __global__ void k_gelu_bwd(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ x, bf16_t* __restrict__ dx,
                            long long n4) {
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
@@ -305,7 +318,7 @@ __global__ void k_gelu_bwd(const bf16_t* __restrict__ dy, const bf16_t* __restri
     ld4(dy + i * 4, d);
     ld4(x + i * 4, f);
 #pragma unroll
-    for (int k = 0; k < 4; ++k) d[k] *= gelu_grad(f[k]);
+    for (int k = 0; k < 4; ++k) d[k] *= gelu_grad<TANH>(f[k]);
     st4(dx + i * 4, d);
   }
 }
@@ -315,6 +328,7 @@ __global__ void k_gelu_bwd(const bf16_t* __restrict__ dy, const bf16_t* __restri
 // pre-activation x is): the FFN1 bias gradient without a second pass over dx.  A block covers
 // rows [y * rpb, +rpb) x 1024 columns; each thread owns 4 columns (8-byte accesses, a block
 // row is 2 KB contiguous) and sums the bf16-rounded dx it stores.
+template <bool TANH>
 __global__ __launch_bounds__(256) void k_gelu_bwd_colsum(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ x,
                                                         bf16_t* __restrict__ dx, float* __restrict__ part,
                                                         long long M, int N, int rpb) {
@@ -335,7 +349,7 @@ __global__ __launch_bounds__(256) void k_gelu_bwd_colsum(const bf16_t* __restric
 #pragma unroll
     for (int u = 0; u < U; ++u) {
 #pragma unroll
-      for (int k = 0; k < 4; ++k) d[u][k] = bf2f(f2bf(d[u][k] * gelu_grad(f[u][k])));
+      for (int k = 0; k < 4; ++k) d[u][k] = bf2f(f2bf(d[u][k] * gelu_grad<TANH>(f[u][k])));
       st4(dx + (r + u) * N + c, d[u]);
 #pragma unroll
       for (int k = 0; k < 4; ++k) acc[k] += d[u][k];
@@ -346,7 +360,7 @@ __global__ __launch_bounds__(256) void k_gelu_bwd_colsum(const bf16_t* __restric
     ld4(dy + r * N + c, d);
     ld4(x + r * N + c, f);
 #pragma unroll
-    for (int k = 0; k < 4; ++k) d[k] = bf2f(f2bf(d[k] * gelu_grad(f[k])));
+    for (int k = 0; k < 4; ++k) d[k] = bf2f(f2bf(d[k] * gelu_grad<TANH>(f[k])));
     st4(dx + r * N + c, d);
 #pragma unroll
     for (int k = 0; k < 4; ++k) acc[k] += d[k];
@@ -587,20 +601,34 @@ KML_API int kml_ln_bwd(const bf16_t* dy, const bf16_t* xin, const float* mean, c
   KML_LAUNCH_CHECK();
 }
 
-KML_API int kml_gelu_fwd(const bf16_t* x, bf16_t* y, long long n, hipStream_t s) {
+template <bool TANH>
+static int gelu_fwd_launch(const bf16_t* x, bf16_t* y, long long n, hipStream_t s) {
   if (n % 4) return (int)hipErrorInvalidValue;
   if (n % 8 == 0 && (reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) % 16 == 0)
-    hipLaunchKernelGGL(k_gelu_fwd8, dim3(kml_stream_grid(n / 16, 256)), dim3(256), 0, s,
+    hipLaunchKernelGGL(k_gelu_fwd8<TANH>, dim3(kml_stream_grid(n / 16, 256)), dim3(256), 0, s,
                        reinterpret_cast<const uint4*>(x), reinterpret_cast<uint4*>(y), n / 8);
   else
-    hipLaunchKernelGGL(k_gelu_fwd, dim3(kml_stream_grid(n / 4, 256)), dim3(256), 0, s, x, y, n / 4);
+    hipLaunchKernelGGL(k_gelu_fwd<TANH>, dim3(kml_stream_grid(n / 4, 256)), dim3(256), 0, s, x, y, n / 4);
   KML_LAUNCH_CHECK();
 }
+KML_API int kml_gelu_fwd(const bf16_t* x, bf16_t* y, long long n, hipStream_t s) {
+  return gelu_fwd_launch<false>(x, y, n, s);
+}
+KML_API int kml_gelu_tanh_fwd(const bf16_t* x, bf16_t* y, long long n, hipStream_t s) {
+  return gelu_fwd_launch<true>(x, y, n, s);
+}
 
-KML_API int kml_gelu_bwd(const bf16_t* dy, const bf16_t* x, bf16_t* dx, long long n, hipStream_t s) {
+template <bool TANH>
+static int gelu_bwd_launch(const bf16_t* dy, const bf16_t* x, bf16_t* dx, long long n, hipStream_t s) {
   if (n % 4) return (int)hipErrorInvalidValue;
-  hipLaunchKernelGGL(k_gelu_bwd, dim3(kml_stream_grid(n / 4, 256)), dim3(256), 0, s, dy, x, dx, n / 4);
+  hipLaunchKernelGGL(k_gelu_bwd<TANH>, dim3(kml_stream_grid(n / 4, 256)), dim3(256), 0, s, dy, x, dx, n / 4);
   KML_LAUNCH_CHECK();
+}
+KML_API int kml_gelu_bwd(const bf16_t* dy, const bf16_t* x, bf16_t* dx, long long n, hipStream_t s) {
+  return gelu_bwd_launch<false>(dy, x, dx, n, s);
+}
+KML_API int kml_gelu_tanh_bwd(const bf16_t* dy, const bf16_t* x, bf16_t* dx, long long n, hipStream_t s) {
+  return gelu_bwd_launch<true>(dy, x, dx, n, s);
 }
 
 // rows per block / row blocks of kml_gelu_bwd_colsum (its workspace is G x N floats)
@@ -617,17 +645,27 @@ KML_API long long kml_gelu_bwd_colsum_ws_floats(long long M, int N) {
   return (long long)gelu_cs_blocks(M, &rpb) * N;
 }
 
-// dx = dy * gelu'(x) over [M][N] and dbias[c] += sum_r dx[r][c] (deterministic row-block order)
-KML_API int kml_gelu_bwd_colsum(const bf16_t* dy, const bf16_t* x, bf16_t* dx, float* dbias, float* ws, long long M,
-                                int N, hipStream_t s) {
+template <bool TANH>
+static int gelu_bwd_colsum_launch(const bf16_t* dy, const bf16_t* x, bf16_t* dx, float* dbias, float* ws,
+                                  long long M, int N, hipStream_t s) {
   if (N % 4 || M <= 0) return (int)hipErrorInvalidValue;
   int rpb;
   const int g = gelu_cs_blocks(M, &rpb);
-  hipLaunchKernelGGL(k_gelu_bwd_colsum, dim3((unsigned)((N / 4 + 255) / 256), (unsigned)g), dim3(256), 0, s, dy, x,
-                     dx, ws, M, N, rpb);
+  hipLaunchKernelGGL(k_gelu_bwd_colsum<TANH>, dim3((unsigned)((N / 4 + 255) / 256), (unsigned)g), dim3(256), 0, s,
+                     dy, x, dx, ws, M, N, rpb);
   hipLaunchKernelGGL(k_colreduce, dim3((N + 63) / 64), dim3(256), 0, s, ws, g, N, N, dbias, (float*)nullptr, 0,
                      (float*)nullptr);
   KML_LAUNCH_CHECK();
+}
+// dx = dy * gelu'(x) over [M][N] and dbias[c] += sum_r dx[r][c] (deterministic row-block order)
+KML_API int kml_gelu_bwd_colsum(const bf16_t* dy, const bf16_t* x, bf16_t* dx, float* dbias, float* ws, long long M,
+                                int N, hipStream_t s) {
+  return gelu_bwd_colsum_launch<false>(dy, x, dx, dbias, ws, M, N, s);
+}
+// the tanh twin (same workspace: kml_gelu_bwd_colsum_ws_floats)
+KML_API int kml_gelu_tanh_bwd_colsum(const bf16_t* dy, const bf16_t* x, bf16_t* dx, float* dbias, float* ws,
+                                     long long M, int N, hipStream_t s) {
+  return gelu_bwd_colsum_launch<true>(dy, x, dx, dbias, ws, M, N, s);
 }
 
 // out[c] += sum_g part[g][c] for part [G][N] fp32 (fixed row order; k_colreduce: 64 columns x

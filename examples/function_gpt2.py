@@ -18,6 +18,8 @@ Train with ``kubeml train -f gpt2 --K 1 --grad-sync`` for synchronous data paral
 persistent Adam moments.  CPU workers run the same recipe with stock torch ops.
 
 ``KUBEML_GPT2_PRESET=tiny`` builds the 2-layer test model (vocab 1000) instead of GPT-2 small.
+``KUBEML_GPT2_ACT=gelu_tanh`` selects the tanh-approximated GELU of the released GPT-2 checkpoints
+(HF ``gelu_new``) instead of the erf GELU — set it when fine-tuning from released weights.
 """
 import os
 from typing import Tuple
@@ -86,5 +88,7 @@ class KubeGPT2(KubeModel):
 
 
 def main():
-    net = gpt2_tiny() if os.environ.get("KUBEML_GPT2_PRESET", "") == "tiny" else gpt2_small()
+    act = os.environ.get("KUBEML_GPT2_ACT", "") or "gelu"
+    build = gpt2_tiny if os.environ.get("KUBEML_GPT2_PRESET", "") == "tiny" else gpt2_small
+    net = build(activation=act)
     return KubeGPT2(net, TokenDataset()).start()

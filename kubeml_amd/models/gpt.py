@@ -19,10 +19,17 @@
   ``generate(prompt_lookup_num_tokens=k)`` / ``draft_lookup`` / ``verify_step``: speculative
   decoding, k n-gram drafts verified per captured round of k + 1 rows, same tokens as without.
 
-FFN activation: the erf GELU of the GEMM epilogue (HF ``activation_function="gelu"``); GPT-2's
-tanh approximation (``gelu_new``) has no epilogue yet.
+FFN activation: ``activation="gelu"`` (the erf GELU, HF ``activation_function="gelu"``; the
+default) or ``activation="gelu_tanh"`` (the tanh approximation, HF ``gelu_new`` /
+``gelu_pytorch_tanh`` — what every released GPT-2 checkpoint was trained with).  Both run in the
+GEMM epilogues forward and backward and in the skinny decode GEMM.  For released weights build the
+model from the checkpoint's ``config.json`` with :meth:`GPT2LMHeadModel.from_hf_config`, which
+picks the activation, then ``load_state_dict``.
 """
 from __future__ import annotations
+
+import json
+import os
 
 import torch
 import torch.nn as tnn
@@ -83,9 +90,15 @@ class GPT2Attention(SelfAttention):
                 sd[prefix + ours + ".bias"] = sd.pop(prefix + hf + ".bias")
 
 
+ACTIVATIONS = ("gelu", "gelu_tanh")   # Linear's act names: erf GELU, tanh-approximated GELU
+
+
 class GPT2MLP(tnn.Module):
-    def __init__(self, hidden, inter):
+    def __init__(self, hidden, inter, activation="gelu"):
         super().__init__()
+        if activation not in ACTIVATIONS:
+            raise ValueError(f"activation {activation!r}: one of {ACTIVATIONS}")
+        self.activation = activation
         self.c_fc = Linear(hidden, inter)
         self.c_proj = Linear(inter, hidden)
         # c_proj is the only consumer of c_fc's GELU output: its dgrad applies the GELU backward
@@ -107,7 +120,7 @@ class GPT2MLP(tnn.Module):
                 sd[prefix + n + ".weight"] = sd[prefix + n + ".weight"].t()
 
     def forward(self, x):
-        return self.c_proj(self.c_fc(x, act="gelu"))   # erf-GELU in the GEMM epilogue
+        return self.c_proj(self.c_fc(x, act=self.activation))   # the GELU in the GEMM epilogue
 
 
 class GPT2Block(tnn.Module):
@@ -115,12 +128,12 @@ class GPT2Block(tnn.Module):
     ``ln_1(h)`` already computed (by the previous block's closing add-and-normalise) and
     returns its MLP branch and the stream; the caller's next ``add_norm`` closes it."""
 
-    def __init__(self, hidden, heads, inter, eps, dropout, rng):
+    def __init__(self, hidden, heads, inter, eps, dropout, rng, activation="gelu"):
         super().__init__()
         self.ln_1 = LayerNorm(hidden, eps=eps)
         self.attn = GPT2Attention(hidden, heads, dropout, rng)
         self.ln_2 = LayerNorm(hidden, eps=eps)
-        self.mlp = GPT2MLP(hidden, inter)
+        self.mlp = GPT2MLP(hidden, inter, activation)
         self.drop1 = Dropout(dropout, rng)   # resid_pdrop after the attention projection
         self.drop2 = Dropout(dropout, rng)   # ... and after the MLP
         # ln_2's branch input is the attention projection's output alone: that Linear's bias
@@ -135,12 +148,13 @@ class GPT2Block(tnn.Module):
 
 
 class GPT2Model(tnn.Module):
-    def __init__(self, vocab, hidden, layers, heads, inter, max_pos, eps, dropout, rng):
+    def __init__(self, vocab, hidden, layers, heads, inter, max_pos, eps, dropout, rng, activation="gelu"):
         super().__init__()
         self.wte = tnn.Embedding(vocab, hidden)
         self.wpe = tnn.Embedding(max_pos, hidden)
         self.drop = Dropout(dropout, rng)   # embd_pdrop
-        self.h = tnn.ModuleList([GPT2Block(hidden, heads, inter, eps, dropout, rng) for _ in range(layers)])
+        self.h = tnn.ModuleList([GPT2Block(hidden, heads, inter, eps, dropout, rng, activation)
+                                 for _ in range(layers)])
         self.ln_f = LayerNorm(hidden, eps=eps)
         self.max_pos = max_pos
         # storage rows padded to 8 so the tied lm_head Linear can share the token table
@@ -179,17 +193,59 @@ class GPT2LMHeadModel(tnn.Module):
     def __init__(self, vocab=50257, hidden=768, layers=12, heads=12, inter=3072, max_pos=1024, eps=1e-5,
                  dropout=0.1, seed: int = 0, activation: str = "gelu"):
         super().__init__()
-        if activation != "gelu":
-            raise ValueError(f"activation {activation!r}: only the erf GELU (\"gelu\") has a GEMM epilogue; "
-                             "GPT-2's tanh approximation (gelu_new) is not implemented")
+        if activation not in ACTIVATIONS:
+            raise ValueError(f"activation {activation!r}: \"gelu\" (erf) or \"gelu_tanh\" (the tanh approximation "
+                             "that HF calls gelu_new; use activation=\"gelu_tanh\" for released GPT-2 weights, or "
+                             "GPT2LMHeadModel.from_hf_config, which maps HF's activation_function)")
+        self.activation = activation
         self.rng = RNGState(seed)
         self.vocab = vocab
-        self.transformer = GPT2Model(vocab, hidden, layers, heads, inter, max_pos, eps, dropout, self.rng)
+        self.transformer = GPT2Model(vocab, hidden, layers, heads, inter, max_pos, eps, dropout, self.rng,
+                                     activation)
         self.lm_head = Linear(hidden, vocab, bias=False)
         # weight tying (HF tie_word_embeddings): lm_head.weight IS the token table
         self.lm_head.weight = self.transformer.wte.weight
         self._init_weights(layers)
         self._register_load_state_dict_pre_hook(GPT2LMHeadModel._load_hook, with_module=True)
+
+    _HF_ACT = {"gelu_new": "gelu_tanh", "gelu_pytorch_tanh": "gelu_tanh", "gelu": "gelu"}
+
+    @classmethod
+    def from_hf_config(cls, config, **overrides):
+        """Build the model a HuggingFace GPT-2 ``config`` describes: a ``GPT2Config``, a dict, or the
+        path of a ``config.json``.  ``activation_function`` picks the FFN activation (``gelu_new``
+        and ``gelu_pytorch_tanh``: "gelu_tanh"; ``gelu``: "gelu"), ``n_inner`` defaults to
+        ``4 n_embd``.  Raises ``ValueError`` for what this model does not implement: another
+        activation, dropout rates that differ (there is one), ``scale_attn_by_inverse_layer_idx``,
+        ``reorder_and_upcast_attn``.  ``overrides`` replace constructor arguments (``seed=...``).
+        Follow with ``load_state_dict(hf_model.state_dict())`` for the weights."""
+        if isinstance(config, (str, os.PathLike)):
+            with open(config) as f:
+                config = json.load(f)
+        elif hasattr(config, "to_dict"):
+            config = config.to_dict()
+        if not isinstance(config, dict):
+            raise TypeError(f"from_hf_config: a GPT2Config, a dict or a path, got {type(config).__name__}")
+        c = config
+        act = c.get("activation_function", "gelu_new")
+        if act not in cls._HF_ACT:
+            raise ValueError(f"from_hf_config: activation_function {act!r} (supported: {sorted(cls._HF_ACT)})")
+        drop = c.get("resid_pdrop", 0.1)
+        for k in ("embd_pdrop", "attn_pdrop"):
+            if c.get(k, 0.1) != drop:
+                raise ValueError(f"from_hf_config: {k} = {c.get(k, 0.1)} differs from resid_pdrop = {drop}; "
+                                 "the model has one dropout rate")
+        for k in ("scale_attn_by_inverse_layer_idx", "reorder_and_upcast_attn"):
+            if c.get(k, False):
+                raise ValueError(f"from_hf_config: {k} is not implemented")
+        hidden = c.get("n_embd", 768)
+        inter = c.get("n_inner")
+        kw = dict(vocab=c.get("vocab_size", 50257), hidden=hidden, layers=c.get("n_layer", 12),
+                  heads=c.get("n_head", 12), inter=4 * hidden if inter is None else inter,
+                  max_pos=c.get("n_positions", 1024), eps=c.get("layer_norm_epsilon", 1e-5), dropout=drop,
+                  activation=cls._HF_ACT[act])
+        kw.update(overrides)
+        return cls(**kw)
 
     def _init_weights(self, layers):
         for m in self.modules():
@@ -319,7 +375,7 @@ class GPT2LMHeadModel(tnn.Module):
             D.kv_append(qkv, cache.k[i], cache.v[i], 1, lens=cache.lens)
             ctx = D.attn_decode(qkv, cache.k[i], cache.v[i], cache.lens, ws=cache.ws)
             x2, s = blk.ln_2.add_norm(blk.attn.out.forward_small(ctx), residual=s)
-            m = blk.mlp.c_proj.forward_small(blk.mlp.c_fc.forward_small(x2, act="gelu"))
+            m = blk.mlp.c_proj.forward_small(blk.mlp.c_fc.forward_small(x2, act=self.activation))
             x, s = ln.add_norm(m, residual=s)
         logits = self.lm_head.forward_small(x, keep_pad=True)
         if advance:
@@ -507,7 +563,7 @@ class GPT2LMHeadModel(tnn.Module):
             D.kv_append(qkv, cache.k[i], cache.v[i], q, lens=cache.lens)
             ctx = D.attn_decode_multi(qkv, cache.k[i], cache.v[i], cache.lens, q, ws=cache.ws_multi)
             x2, s = blk.ln_2.add_norm(blk.attn.out.forward_small(ctx, skinny=True), residual=s)
-            m = blk.mlp.c_proj.forward_small(blk.mlp.c_fc.forward_small(x2, act="gelu", skinny=True), skinny=True)
+            m = blk.mlp.c_proj.forward_small(blk.mlp.c_fc.forward_small(x2, act=self.activation, skinny=True), skinny=True)
             x, s = ln.add_norm(m, residual=s)
         # skinny at every row count: above 4 rows forward_small would send the tied decoder elsewhere
         logits = self.lm_head.forward_small(x, keep_pad=True, skinny=True)

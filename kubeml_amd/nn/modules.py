@@ -37,7 +37,7 @@ def _on_gpu(x):
 
 
 # Large linears (BERT: M = batch x seq tokens) run their three GEMMs on the hand-written
-# 256/128-tile LDS-DMA MFMA kernel of csrc/kernels/gemm.hip (ops/gemm.py): bias and erf-GELU
+# 256/128-tile LDS-DMA MFMA kernel of csrc/kernels/gemm.hip (ops/gemm.py): bias and erf / tanh GELU
 # in the forward epilogue, the weight gradient accumulated in fp32 straight into the flat
 # gradient storage (split-K with agent atomics).  Small-M layers and fused-ReLU heads stay on
 # the implicit-GEMM conv kernels.
@@ -155,8 +155,8 @@ class Conv2d(tnn.Module):
 # ======================================================================================
 
 class _LinearFn(Function):
-    """act: 0 none, 1 ReLU (implicit-GEMM path), 2 erf-GELU (gemm.hip epilogue; the
-    pre-activation is kept for backward)."""
+    """act: 0 none, 1 ReLU (implicit-GEMM path), 2 erf-GELU, 3 tanh-GELU (gemm.hip epilogue;
+    the pre-activation is kept for backward, and the function remembers which GELU it ran)."""
 
     @staticmethod
     def forward(ctx, x2, weight, bias, mod, act, keep_pad=False):
@@ -170,11 +170,12 @@ class _LinearFn(Function):
         if route == "gemm":
             from ..ops import gemm as G
             w2 = shadow_of(weight).view(op, ip)
-            pre = torch.empty((B, op), dtype=torch.bfloat16, device=x2.device) if act == 2 else None
-            y = G.linear_fwd(x2, w2, None if bias is None else master_of(bias), act=1 if act == 2 else 0, pre=pre,
+            pre = torch.empty((B, op), dtype=torch.bfloat16, device=x2.device) if act in (2, 3) else None
+            y = G.linear_fwd(x2, w2, None if bias is None else master_of(bias),
+                             act={2: G.GELU, 3: G.GELU_TANH}.get(act, 0), pre=pre,
                              bias16=None if bias is None else shadow_of(bias))
         else:
-            if act == 2:
+            if act in (2, 3):
                 raise ValueError("fused GELU needs the large-linear GEMM path")
             w = shadow_of(weight).view(op, 1, 1, ip)
             bias_st = None if bias is None else master_of(bias)
@@ -183,15 +184,17 @@ class _LinearFn(Function):
         ctx.y = y if act == 1 else None
         ctx.pre = pre
         # GELU hand-off (models/bert.py): a Linear declared as this one's sole consumer runs
-        # the GELU backward in its dgrad epilogue; it finds the pre-activation here
+        # the GELU backward in its dgrad epilogue; it finds the pre-activation, and which GELU
+        # produced its input, here
+        ctx.approx = "tanh" if act == 3 else "none"
         if pre is not None:
-            object.__setattr__(mod, "_kml_gelu_pre", (y.data_ptr(), pre))
+            object.__setattr__(mod, "_kml_gelu_pre", (y.data_ptr(), pre, ctx.approx))
         ctx.gelu = None
         prod = getattr(mod, "_kml_gelu_producer", None)
         if prod is not None and route == "gemm":
             hand = getattr(prod, "_kml_gelu_pre", None)
             if hand is not None and hand[0] == x2.data_ptr():
-                ctx.gelu = (prod, hand[1])
+                ctx.gelu = (prod, hand[1], hand[2])
                 object.__setattr__(prod, "_kml_gelu_pre", None)
         ctx.keep_pad = keep_pad
         if op != mod.out_features and not keep_pad:
@@ -212,14 +215,15 @@ class _LinearFn(Function):
         bias_done = False
         if ctx.act == 1:
             dy = K.relu_bwd(dy, ctx.y)
-        elif ctx.act == 2:
+        elif ctx.act in (2, 3):
             if getattr(mod, "_kml_gelu_done", False):
                 # the consumer's dgrad already applied the GELU backward and summed the bias
                 object.__setattr__(mod, "_kml_gelu_done", False)
             else:
                 from ..ops import transformer as T
                 # the bias gradient comes out of the GELU backward pass (no column-sum pass)
-                dy = T.gelu_bwd(dy, ctx.pre, dbias=grad_storage_of(mod.bias) if ctx.has_bias else None)
+                dy = T.gelu_bwd(dy, ctx.pre, dbias=grad_storage_of(mod.bias) if ctx.has_bias else None,
+                                approximate=ctx.approx)
             bias_done = ctx.has_bias
         dy4 = dy.view(B, 1, 1, op)
         x4 = ctx.x.view(B, 1, 1, ip)
@@ -254,9 +258,10 @@ class _LinearFn(Function):
             if ctx.needs_input_grad[0]:
                 dx = None
                 if ctx.gelu is not None and addend is None and _GELU_FUSE:
-                    prod, pre = ctx.gelu
+                    prod, pre, approx = ctx.gelu
                     dx = G.linear_dgrad_gelu(dy, w2, pre,
-                                             dbias=grad_storage_of(prod.bias) if prod.bias is not None else None)
+                                             dbias=grad_storage_of(prod.bias) if prod.bias is not None else None,
+                                             approximate=approx)
                     if dx is not None:
                         object.__setattr__(prod, "_kml_gelu_done", True)
                 if dx is None:
@@ -327,13 +332,16 @@ class Linear(tnn.Module):
         return f"in_features={self.in_features}, out_features={self.out_features}, bias={self.bias is not None}"
 
     def forward(self, x, act: Optional[str] = None, keep_pad: bool = False):
-        """act: None (module default: fused ReLU if constructed so), "gelu" (erf-GELU fused
-        into the GEMM epilogue on the GPU).  keep_pad: on the GPU return the [N, out_pad]
+        """act: None (module default: fused ReLU if constructed so), "gelu" (erf-GELU) or
+        "gelu_tanh" (the tanh approximation, HF ``gelu_new``), fused into the GEMM epilogue on
+        the GPU.  keep_pad: on the GPU return the [N, out_pad]
         output whose columns past out_features are zero (no slice copy; a consumer that
         knows the real width — ``cross_entropy(classes=...)`` — uses it in place)."""
-        a = 2 if act == "gelu" else (1 if self.fused_relu else 0)
+        a = 2 if act == "gelu" else (3 if act == "gelu_tanh" else (1 if self.fused_relu else 0))
         if not _on_gpu(x):
             y = F.linear(x, self.weight, self.bias)
+            if a == 3:
+                return F.gelu(y, approximate="tanh")
             return F.relu(y) if a == 1 else (F.gelu(y) if a == 2 else y)
         if x.dim() != 2:
             x = x.reshape(x.shape[0], -1)
@@ -341,9 +349,9 @@ class Linear(tnn.Module):
             x = x.to(torch.bfloat16)
         if x.shape[1] != self.in_pad:
             x = pad_channels(x, self.in_pad)
-        if a == 2 and _linear_route(x.shape[0], self.in_pad, self.out_pad, 2) != "gemm":
+        if a in (2, 3) and _linear_route(x.shape[0], self.in_pad, self.out_pad, a) != "gemm":
             from .transformer import GELU
-            return GELU()(_LinearFn.apply(x.contiguous(), self.weight, self.bias, self, 0))
+            return GELU("tanh" if a == 3 else "none")(_LinearFn.apply(x.contiguous(), self.weight, self.bias, self, 0))
         y = _LinearFn.apply(x.contiguous(), self.weight, self.bias, self, a, keep_pad)
         if a == 0:
             y._kml_linear = self   # raw linear output: a consuming cross_entropy may sum our bias grad
@@ -351,8 +359,8 @@ class Linear(tnn.Module):
 
     def forward_small(self, x, act: Optional[str] = None, keep_pad: bool = False, skinny: bool = False):
         """Inference-only forward for M <= 16 rows (a decode step: M = batch): no autograd, the
-        bf16 shadow weights, the skinny GEMM of ops/decode.py with bias and erf-GELU in its
-        epilogue.  Shapes listed in ``_SMALL_EXISTING`` (from the row count at which the skinny
+        bf16 shadow weights, the skinny GEMM of ops/decode.py with bias and the GELU (erf
+        or tanh form) in its epilogue.  Shapes listed in ``_SMALL_EXISTING`` (from the row count at which the skinny
         kernel measured slower) and fused-ReLU layers take :meth:`forward` instead.  ``skinny``:
         ignore ``_SMALL_EXISTING`` and take the skinny GEMM at every row count up to 16 — a row of
         its result does not depend on the row count, which a verify round of the speculative
@@ -362,7 +370,7 @@ class Linear(tnn.Module):
             if (not _on_gpu(x) or self.fused_relu or
                     (not skinny and rows >= _SMALL_EXISTING.get((self.out_pad, self.in_pad), 17))):
                 return self.forward(x, act=act, keep_pad=keep_pad)
-            if act not in (None, "gelu"):
+            if act not in (None, "gelu", "gelu_tanh"):
                 raise ValueError(f"forward_small: act {act!r}")
             if x.dim() != 2:
                 x = x.reshape(x.shape[0], -1)

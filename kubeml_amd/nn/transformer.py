@@ -2,7 +2,7 @@
 fp32 stock-torch path on CPU with identical parameters / ``state_dict`` names).
 
 * :class:`LayerNorm`     — torch.nn.LayerNorm semantics; fused residual add
-* :class:`GELU`, :class:`Dropout` — erf GELU; counter-based dropout (mask regenerated
+* :class:`GELU`, :class:`Dropout` — erf or tanh GELU; counter-based dropout (mask regenerated
   in backward from a device ``[seed, step]`` pair, so graph replays draw new masks)
 * :class:`SelfAttention` — fused QKV projection (one GEMM, ``[T, 3H]``) + flash
   attention kernel + output projection; ``state_dict`` exposes HuggingFace's
@@ -156,24 +156,35 @@ _LN_DROP_FUSE = True
 
 class _GELUFn(Function):
     @staticmethod
-    def forward(ctx, x):
+    def forward(ctx, x, approximate="none"):
         from ..ops import transformer as T
-        ctx.x = x
-        return T.gelu_fwd(x)
+        ctx.x, ctx.approx = x, approximate
+        return T.gelu_fwd(x, approximate=approximate)
 
     @staticmethod
     def backward(ctx, dy):
         from ..ops import transformer as T
-        dx = T.gelu_bwd(_bf(dy).contiguous(), ctx.x)
+        dx = T.gelu_bwd(_bf(dy).contiguous(), ctx.x, approximate=ctx.approx)
         ctx.x = None
-        return dx
+        return dx, None
 
 
 class GELU(tnn.Module):
+    """approximate: "none" (erf) or "tanh", as ``torch.nn.GELU``."""
+
+    def __init__(self, approximate: str = "none"):
+        super().__init__()
+        if approximate not in ("none", "tanh"):
+            raise ValueError(f"GELU: approximate {approximate!r} (\"none\" or \"tanh\")")
+        self.approximate = approximate
+
+    def extra_repr(self):
+        return f"approximate={self.approximate!r}"
+
     def forward(self, x):
         if not x.is_cuda:
-            return F.gelu(x)
-        return _GELUFn.apply(_bf(x).contiguous())
+            return F.gelu(x, approximate=self.approximate)
+        return _GELUFn.apply(_bf(x).contiguous(), self.approximate)
 
 
 class RNGState:

@@ -100,9 +100,12 @@ def attn_decode(q, kc, vc, lens, ws=None, out=None, scale=None, chunk=None):
     return out
 
 
+_SKINNY_ACT = {None: 0, "gelu": 1, "gelu_tanh": 2}   # kml_gemm_skinny's act codes
+
+
 def gemm_skinny(x, w, bias=None, act=None, out=None, splits=None):
     """y[M, N] = act(x[M, K] @ w[N, K]ᵀ + bias) for M <= 16: bf16 in / out, fp32 accumulate, fp32
-    bias, ``act`` None or "gelu" (erf).  x, w and out may be row-major views with a row stride
+    bias, ``act`` None, "gelu" (erf) or "gelu_tanh" (the tanh approximation).  x, w and out may be row-major views with a row stride
     that is a multiple of 8.  Row m of the result does not depend on M or on the other rows.
     ``splits``: another K split than the kernel's plan for (N, K) (the tuning sweep only)."""
     _chk_view(x, "x")
@@ -113,7 +116,7 @@ def gemm_skinny(x, w, bias=None, act=None, out=None, splits=None):
         raise ValueError(f"gemm_skinny: M = {M} rows; the skinny kernel takes 1..16")
     if w.shape[1] != K or K % 8 or K < 8:
         raise ValueError(f"gemm_skinny: x {tuple(x.shape)} vs w {tuple(w.shape)} (K a multiple of 8)")
-    if act not in (None, "gelu"):
+    if act not in _SKINNY_ACT:
         raise ValueError(f"gemm_skinny: act {act!r}")
     if bias is not None:
         _chk(bias, F32, "bias")
@@ -132,7 +135,7 @@ def gemm_skinny(x, w, bias=None, act=None, out=None, splits=None):
         ws = torch.empty(groups * S * 256, dtype=F32, device=x.device)
         cnt = _COUNTERS.take(x.device, groups)
     HIP.call("kml_gemm_skinny", "p i p i p p i i i i i i p p s", _p(x), x.stride(0), _p(w), w.stride(0), _p(bias),
-             _p(out), out.stride(0), M, N, K, 1 if act == "gelu" else 0, 0 if splits is None else S, _p(ws), _p(cnt),
+             _p(out), out.stride(0), M, N, K, _SKINNY_ACT[act], 0 if splits is None else S, _p(ws), _p(cnt),
              _s())
     return out
 

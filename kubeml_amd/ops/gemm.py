@@ -38,6 +38,8 @@ if os.path.exists(_TUNE_FILE):   # KUBEML_GEMM_TUNING_FILE=none: every GEMM on i
 _ZP = {}
 
 
+GELU = 1       # kml_gemm act code: erf GELU in the forward epilogue
+GELU_TANH = 2  # kml_gemm act code: tanh-approximated GELU (HF gelu_new) in the forward epilogue
 ADD_C2 = 3  # kml_gemm act code: bf16 output = bf16(bf16(A B) + c2)
 
 
@@ -87,7 +89,10 @@ def _check(t, dtype, name):
 
 def gemm(a, lda, b, ldb, c, ldc, M, N, K, layout, out, bias=None, act=0, c2=None, beta=0.0, tile=None,
          splits=None):
-    """Raw launcher; see gemm.hip for the layout / out codes."""
+    """Raw launcher; see gemm.hip for the layout / out codes.  act (bf16 output): 0 none,
+    GELU (1, erf), GELU_TANH (2), ADD_C2 (3)."""
+    if act not in (0, GELU, GELU_TANH, ADD_C2):
+        raise ValueError(f"gemm: act code {act!r}")
     _check(a, BF16, "a")
     _check(b, BF16, "b")
     _check(c, BF16 if out == 0 else F32, "c")
@@ -184,11 +189,14 @@ def linear_dgrad(dy, w, addend=None):
     return dx
 
 
-def linear_dgrad_gelu(dy, w, pre, dbias=None):
+def linear_dgrad_gelu(dy, w, pre, dbias=None, approximate="none"):
     """dx = bf16(bf16(dy @ w) * gelu'(pre)) in the dgrad epilogue — the GELU backward of the
     layer whose output this linear consumed (FFN1 -> FFN2), and ``dbias`` (fp32) += column
-    sums of dx (FFN1's bias gradient).  Only for shapes whose plan is the 256x256 phase tile
+    sums of dx (FFN1's bias gradient).  ``approximate``: "none" (erf) or "tanh", the GELU
+    that produced the forward.  Only for shapes whose plan is the 256x256 phase tile
     without split-K; returns None otherwise (the caller runs the separate GELU backward)."""
+    if approximate not in ("none", "tanh"):
+        raise ValueError(f"linear_dgrad_gelu: approximate {approximate!r}")
     T, op = dy.shape
     ip = w.shape[1]
     tile, splits = plan(1, T, ip, op)
@@ -199,9 +207,12 @@ def linear_dgrad_gelu(dy, w, pre, dbias=None):
     _check(pre, BF16, "pre")
     dx = torch.empty((T, ip), dtype=BF16, device=dy.device)
     colpart = torch.empty((_cdiv(T, 256), ip), dtype=F32, device=dy.device)
-    HIP.call("kml_gemm_dgrad_gelu", "p l p l p l p p p i i i s", dy.data_ptr(), int(op), w.data_ptr(), int(ip),
-             dx.data_ptr(), int(ip), pre.data_ptr(), colpart.data_ptr(), _zp(dy.device).data_ptr(), int(T), int(ip),
-             int(op), stream_ptr())
+    args = (dy.data_ptr(), int(op), w.data_ptr(), int(ip), dx.data_ptr(), int(ip), pre.data_ptr(), colpart.data_ptr(),
+            _zp(dy.device).data_ptr(), int(T), int(ip), int(op), stream_ptr())
+    if approximate == "tanh":
+        HIP.call("kml_gemm_dgrad_gelu_tanh", "p l p l p l p p p i i i s", *args)
+    else:
+        HIP.call("kml_gemm_dgrad_gelu", "p l p l p l p p p i i i s", *args)
     if dbias is not None:
         _check(dbias, F32, "dbias")
         HIP.call("kml_colreduce_add", "p i i p s", colpart.data_ptr(), int(colpart.shape[0]), int(ip),

@@ -152,15 +152,29 @@ def ln_bwd(dy, xin, mean, rstd, gamma, dgamma, dbeta, dx_add=None, drop=None, db
     return (dx, dxd) if drop is not None else dx
 
 
-def gelu_fwd(x):
+def _tanh(approximate, who):
+    if approximate not in ("none", "tanh"):
+        raise ValueError(f"{who}: approximate {approximate!r} (\"none\" or \"tanh\")")
+    return approximate == "tanh"
+
+
+def gelu_fwd(x, approximate="none"):
+    """y = gelu(x): the erf form, or with approximate="tanh" the tanh approximation
+    (torch's ``F.gelu`` argument; HF ``gelu_new``)."""
+    tanh = _tanh(approximate, "gelu_fwd")
     y = torch.empty_like(x)
-    HIP.call("kml_gelu_fwd", "p p l s", _p(x), _p(y), x.numel(), _s())
+    if tanh:
+        HIP.call("kml_gelu_tanh_fwd", "p p l s", _p(x), _p(y), x.numel(), _s())
+    else:
+        HIP.call("kml_gelu_fwd", "p p l s", _p(x), _p(y), x.numel(), _s())
     return y
 
 
-def gelu_bwd(dy, x, dbias=None):
+def gelu_bwd(dy, x, dbias=None, approximate="none"):
     """dx = dy * gelu'(x).  dbias (fp32 [N]) += column sums of dx over the rows of the
-    [M, N] map, from the same pass (the bias gradient of the Linear whose pre-activation x is)."""
+    [M, N] map, from the same pass (the bias gradient of the Linear whose pre-activation x is).
+    approximate: as :func:`gelu_fwd`."""
+    tanh = _tanh(approximate, "gelu_bwd")
     dx = torch.empty_like(dy)
     if dbias is not None:
         _chk(dbias, F32, "dbias")
@@ -169,9 +183,16 @@ def gelu_bwd(dy, x, dbias=None):
         if dbias.numel() < N:
             raise ValueError("dbias shorter than N")
         ws = torch.empty(HIP.raw("kml_gelu_bwd_colsum_ws_floats", M, N), dtype=F32, device=dy.device)
-        HIP.call("kml_gelu_bwd_colsum", "p p p p p l i s", _p(dy), _p(x), _p(dx), _p(dbias), _p(ws), M, N, _s())
+        if tanh:
+            HIP.call("kml_gelu_tanh_bwd_colsum", "p p p p p l i s", _p(dy), _p(x), _p(dx), _p(dbias), _p(ws), M, N,
+                     _s())
+        else:
+            HIP.call("kml_gelu_bwd_colsum", "p p p p p l i s", _p(dy), _p(x), _p(dx), _p(dbias), _p(ws), M, N, _s())
         return dx
-    HIP.call("kml_gelu_bwd", "p p p l s", _p(dy), _p(x), _p(dx), dy.numel(), _s())
+    if tanh:
+        HIP.call("kml_gelu_tanh_bwd", "p p p l s", _p(dy), _p(x), _p(dx), dy.numel(), _s())
+    else:
+        HIP.call("kml_gelu_bwd", "p p p l s", _p(dy), _p(x), _p(dx), dy.numel(), _s())
     return dx
 
 

@@ -7,6 +7,7 @@ causal flash-attention kernel (csrc/kernels/attention.hip); every GEMM, the 5025
 decoder included, runs on csrc/kernels/gemm.hip or the tile ops/gemm_tuning.json names.
 
     python tools/bench_gpt.py [--batch 16] [--seq 1024] [--steps 20] [--warmup 3] [--layers 12]
+                              [--activation gelu|gelu_tanh]
 Prints one JSON line (tokens/s over all processed tokens).  Single GPU: the model has no
 ``stages()`` for backward-overlapped gradient exchange yet.
 """
@@ -27,6 +28,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--layers", type=int, default=12)
     ap.add_argument("--no-graph", action="store_true")
+    ap.add_argument("--activation", choices=("gelu", "gelu_tanh"), default="gelu",
+                    help="FFN activation: the erf GELU or the tanh approximation of the released checkpoints")
     a = ap.parse_args()
 
     import torch
@@ -37,7 +40,7 @@ def main():
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     torch.manual_seed(0)
-    m = gpt2_small(layers=a.layers, seed=1).to(dev)
+    m = gpt2_small(layers=a.layers, seed=1, activation=a.activation).to(dev)
     sp = flatten_module(m)
     m.train()
     opt = AdamW(m.parameters(), lr=1e-4, weight_decay=0.01)
@@ -64,7 +67,7 @@ def main():
     dt = time.perf_counter() - t0
     print(json.dumps({"metric": "GPT-2 small causal-LM training tokens/s", "value": round(B * L * a.steps / dt, 1),
                       "unit": "tokens/s", "n_gpus": 1, "ms_per_step": round(dt / a.steps * 1e3, 3),
-                      "batch_per_gpu": B, "seq": L, "layers": a.layers,
+                      "batch_per_gpu": B, "seq": L, "layers": a.layers, "activation": a.activation,
                       "params": sum(p.numel() for p in m.parameters()),
                       "optimizer": "fused AdamW", "dtype": "bf16", "data": "synthetic tokens, random init",
                       "graph": not a.no_graph, "attention": "causal flash attention (attention.hip)",

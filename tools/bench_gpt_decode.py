@@ -117,7 +117,7 @@ def prompt_lookup(a, ks, graphed, alternate):
     from kubeml_amd.models.gpt import gpt2_small
     from kubeml_amd.nn import flatten_module
     torch.manual_seed(0)
-    model = gpt2_small(dropout=0.0).to(dev).eval()
+    model = gpt2_small(dropout=0.0, activation=a.activation).to(dev).eval()
     flatten_module(model)
     prompt, new = 128, a.new
     W = prompt + new
@@ -226,6 +226,8 @@ def main():
     ap.add_argument("--repetition-penalty", type=float, default=1.0)
     ap.add_argument("--prompt-lookup", default=None, metavar="K[,K...]",
                     help="only the prompt-lookup (speculative decoding) measurements, for these draft counts")
+    ap.add_argument("--activation", choices=("gelu", "gelu_tanh"), default="gelu",
+                    help="the model's FFN activation (the kernel sweeps keep their own)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import torch
@@ -271,7 +273,7 @@ def main():
                 for k, v in times.items()}
 
     res = {"device": torch.cuda.get_device_name(0), "chunk": D.attn_decode_chunk(), "rounds": a.rounds,
-           "iters": a.iters}
+           "iters": a.iters, "activation": a.activation}
     if a.prompt_lookup is not None:
         res["prompt_lookup"] = prompt_lookup(a, [int(k) for k in a.prompt_lookup.split(",")], graphed, alternate)
         line = json.dumps(res)
@@ -382,7 +384,7 @@ def main():
         from kubeml_amd.models.gpt import gpt2_small
         from kubeml_amd.nn import flatten_module
         torch.manual_seed(0)
-        model = gpt2_small(dropout=0.0).to(dev).eval()
+        model = gpt2_small(dropout=0.0, activation=a.activation).to(dev).eval()
         flatten_module(model)
         tr = model.transformer
         wbytes = 2 * (sum(l.out_pad * l.in_pad for blk in tr.h
