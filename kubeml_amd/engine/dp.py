@@ -68,7 +68,7 @@ def make_train_step(model: torch.nn.Module, space, optimizer, loss_fn: Callable,
                     extra_state: Sequence[torch.Tensor] = (), comm_dtype=None,
                     opt_overlap: Optional[bool] = None, advance=None, plan=None, peer=None,
                     ride: Optional[bool] = None,
-                    comm_timing: int = 0, forward: Optional[Callable] = None) -> GraphedTrainStep:
+                    comm_timing: int = 0, forward: Optional[Callable] = None, ema=None) -> GraphedTrainStep:
     """Build (not capture) the train step on static input buffers ``x``/``y``.
 
     pre():  runs first inside the step (e.g. on-device augmentation into ``x``)
@@ -108,7 +108,15 @@ def make_train_step(model: torch.nn.Module, space, optimizer, loss_fn: Callable,
     forward: ``forward(model, x, y) -> loss`` in place of ``loss_fn(model(x), y)`` (models whose
             call takes more than the batch, e.g. BERT MLM with its positions and labels, or a
             step that prepares its batch on the device first); the step is then not stage-split
+    ema:    a :class:`kubeml_amd.optim.EMA` of ``space``: ``ema.update()`` is the step's last launch,
+            after every update of the master (end-of-step launch, SGD riders, per-stage ranges), and
+            its device state joins the tensors restored after the capture warm-up.  The ZeRO-1 plans
+            leave the fp32 master complete only on the rank's own chunk, so with an EMA they run as
+            the exact all-reduce plan (warning logged).  Follow-up: keep the EMA per chunk and gather
+            it when it is read.  None: every launch and result is what it was.
     """
+    if ema is not None and ema.space is not space:
+        raise ValueError("make_train_step: the EMA must average this step's flat space")
     comm = world > 1 or force_comm
     # global-norm clipping (optimizer built with max_grad_norm) needs the whole reduced gradient
     # before any element is updated: no riders, no per-stage updates, no sharded update
@@ -139,8 +147,11 @@ def make_train_step(model: torch.nn.Module, space, optimizer, loss_fn: Callable,
         # the optimizer's capability is checked BEFORE the collective setup (the same answer on
         # every rank), so an optimizer that cannot update one flat range falls back like a node
         # without IPC buffers instead of failing after the self-test
-        can_shard = optimizer_can_shard(optimizer)
-        if on_gpu and clipping:
+        can_shard = optimizer_can_shard(optimizer) and ema is None
+        if on_gpu and ema is not None:
+            _log.warning("shard plan: a weight EMA follows the whole fp32 master, which a sharded update keeps "
+                         "complete only on the rank's own chunk; using the all-reduce plan")
+        elif on_gpu and clipping:
             _log.warning("shard plan: global-norm clipping needs the whole reduced gradient on every rank; "
                          "using the all-reduce plan")
         elif on_gpu and not can_shard:
@@ -203,6 +214,15 @@ def make_train_step(model: torch.nn.Module, space, optimizer, loss_fn: Callable,
                     user_post()
                 from ..ops import kernels as K
                 K.advance_counter_(*advance)
+    if ema is not None:
+        # the step's last launch: post() closes every route (whole step, riders, per-stage ranges)
+        inner_post = post
+        extra_state = list(extra_state) + ema.state_tensors()
+
+        def post():
+            if inner_post is not None:
+                inner_post()
+            ema.update()
     if (comm and overlap and staged_ok) or opt_overlap or staged_shard:
         from .staged import StagedForwardBackward
 

@@ -2136,6 +2136,50 @@ def kavg_async_apply_(x, flat, snap, shadow, world, n_params):
              x.numel(), int(n_params), _s())
 
 
+# ---- weight EMA (csrc/kernels/ema.hip) --------------------------------------------------------
+
+def _chk_ema_pair(name, a, b):
+    _chk(a, F32, "ema")
+    _chk(b, F32, name)
+    if a.numel() != b.numel() or a.numel() % 4 or a.device != b.device:
+        raise ValueError(f"{name}: ema and {name} must be fp32 of one size, a multiple of 4, on one device")
+    if a.data_ptr() % 16 or b.data_ptr() % 16:
+        raise ValueError(f"{name}: the buffers must be 16-byte aligned")
+
+
+def ema_update_(ema, w, decay, every, warmup, ctl, aout, ticket, max_blocks=0):
+    """One launch: ``ema += (w - ema) * (1 - d)`` iff ``(ctl[0] + 1) % every == 0``, with
+    ``d = min(decay, (1 + ctl[1]) / (10 + ctl[1]))`` under ``warmup`` (else ``decay``); then the last
+    block advances ``ctl`` (int32 [ticks, updates, applied, 0]) and leaves ``1 - d`` in ``aout``.  The
+    gate and the warm-up read device memory, so a captured launch follows them.  ``ticket``: one
+    zeroed int32 word, zero again when the launch ends."""
+    _chk_ema_pair("w", ema, w)
+    for t, dt, n, nm in ((ctl, torch.int32, 4, "ctl"), (aout, F32, 1, "aout"), (ticket, torch.int32, 1, "ticket")):
+        _chk(t, dt, nm)
+        if t.numel() < n or t.device != ema.device:
+            raise ValueError(f"ema_update_: {nm} must hold {n} element(s) on the buffers' device")
+    if not 0.0 <= float(decay) <= 1.0 or int(every) < 1:
+        raise ValueError("ema_update_: decay in [0, 1] and every >= 1")
+    HIP.call("kml_ema_update", "p p l f i i p p p i s", _p(ema), _p(w), ema.numel(), float(decay), int(every),
+             int(bool(warmup)), _p(ctl), _p(aout), _p(ticket), int(max_blocks), _s())
+
+
+def ema_swap_(state, ema, shadow, n_params):
+    """``state <-> ema`` element by element and ``shadow[:n_params] = bf16(new state[:n_params])``
+    in one launch; ``shadow`` may be None.  Two calls restore all three buffers."""
+    _chk_ema_pair("state", ema, state)
+    n_params = int(n_params)
+    if not 0 <= n_params <= ema.numel():
+        raise ValueError("ema_swap_: n_params outside the buffers")
+    if shadow is not None:
+        _chk(shadow, BF16, "shadow")
+        if shadow.numel() < n_params or shadow.device != ema.device or shadow.data_ptr() % 8:
+            raise ValueError("ema_swap_: shadow must be bf16 covering the parameters, 8-byte aligned")
+    else:
+        n_params = 0
+    HIP.call("kml_ema_swap", "p p p l l s", _p(state), _p(ema), _p(shadow), ema.numel(), n_params, _s())
+
+
 # --------------------------------------------------------------------------------------
 # data
 # --------------------------------------------------------------------------------------

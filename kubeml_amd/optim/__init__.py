@@ -39,6 +39,9 @@ LR scalar.  A single-group optimizer launches exactly what it always did.
 large-batch recipes: two launches per step (per-tensor norms, then the update), a table row per
 tensor instead of the granule bytes, everything else as above.
 
+:class:`~kubeml_amd.optim.ema.EMA` keeps an exponential moving average of the flat state prefix (weights
+and BN statistics) in one launch per step, for validation, checkpoints and inference.
+
 ``from_torch(opt)`` converts a user's ``torch.optim.SGD/Adam/AdamW`` (what
 ``KubeModel.configure_optimizers`` returns in reference code) into the fused one
 with identical hyper-parameters, group by group.
@@ -51,7 +54,7 @@ from typing import Dict, List
 import torch
 
 __all__ = ["SGD", "Adam", "AdamW", "LAMB", "LARS", "from_torch", "with_max_grad_norm", "no_decay_groups",
-           "layerwise_groups", "FusedOptimizer"]
+           "layerwise_groups", "FusedOptimizer", "EMA"]
 
 MAX_GROUPS = 8            # rows of the kernels' hyper-parameter table (KML_MAX_GROUPS)
 _PER_GROUP = ("lr", "weight_decay")     # what may differ between parameter groups
@@ -747,3 +750,4 @@ def no_decay_groups(module: torch.nn.Module, weight_decay: float):
 
 
 from .layerwise import LAMB, LARS, layerwise_groups  # noqa: E402  (needs FusedOptimizer above)
+from .ema import EMA  # noqa: E402

@@ -15,8 +15,8 @@ optimizer, flat parameter buffers, graphs) resident in HBM between tasks: the us
 ``main()`` runs once per job; later tasks call ``start()`` on the cached model.
 
 Messages (dicts): ``{"op": "task", "kind": init|train|val|infer, ...}``,
-``{"op": "checkpoint", "job", "path", "epoch"}``, ``{"op": "release", "job"}``,
-``{"op": "stats"}``, ``{"op": "shutdown"}``.  Replies: ``{"ok": True, "result": ...}`` or
+``{"op": "checkpoint", "job", "path", "epoch"}`` (saves the model's weight EMA with it, if it
+keeps one), ``{"op": "release", "job"}``, ``{"op": "stats"}``, ``{"op": "shutdown"}``.  Replies: ``{"ok": True, "result": ...}`` or
 the error envelope ``{"ok": False, "error", "code"}`` (server.py:133-151).
 """
 from __future__ import annotations
@@ -244,7 +244,7 @@ class Worker:
             self.ckpt = AsyncCheckpointer()
         try:
             prev = self.ckpt.save(km.network, msg["path"], job_id=msg["job"], epoch=int(msg.get("epoch", 0)),
-                                  extra=msg.get("extra"))
+                                  extra=msg.get("extra"), ema=getattr(km, "ema", None))
             if msg.get("wait"):
                 self.ckpt.wait()
         except Exception as e:

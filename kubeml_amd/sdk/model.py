@@ -31,6 +31,7 @@ What changed underneath (MI355X-first):
 """
 from __future__ import annotations
 
+import contextlib
 import logging
 import os
 import time
@@ -150,6 +151,8 @@ class KubeModel(ABC):
     def _initialize(self) -> List[str]:
         self._set_device()
         self.init()
+        if self.ema is not None:
+            self.ema.reset()               # init() may have written the weights
         return [name for name in self._network.state_dict()]
 
     # ---- optimizer -------------------------------------------------------------------------
@@ -232,7 +235,9 @@ class KubeModel(ABC):
             from ..runtime.worker import busy
             from ..store.ckpt import load_checkpoint
             with busy():
-                load_checkpoint(self._network, path)
+                meta = load_checkpoint(self._network, path, ema=self.ema)
+            if self.ema is not None and "ema" not in meta:
+                self.ema.reset()           # a checkpoint without an average: start from its weights
             self._restored_from = path
 
     def _on_train_end(self):
@@ -308,6 +313,8 @@ class KubeModel(ABC):
         # every worker starts the epoch from the same reference model
         with trace.span("broadcast"):
             self._averager.broadcast_(comm, 0)
+            if self.ema is not None:
+                self.ema.broadcast_(comm, 0)
         ctx = current_task()
         if ctx is not None and os.environ.get("KUBEML_CHECKSUMS", "1") != "0":
             with trace.span("checksum"):
@@ -336,7 +343,7 @@ class KubeModel(ABC):
                                        self.batch_size, self.device)
         loss_host, loss_dev, num_iterations = 0.0, None, 0
         self.sync_seconds = 0.0
-        grad_rounds = 0
+        grad_rounds = local_rounds = 0
         try:
             for r in range(rounds):
                 fault.point("round", rank=fid, epoch=self.epoch, round=r, task="train", job=self.args._job_id)
@@ -370,6 +377,7 @@ class KubeModel(ABC):
                 if self._sync_mode == "grad" and self._synced_steps == nb == 1:
                     grad_rounds += 1      # weights already identical on every rank
                     continue
+                local_rounds += 1
                 try:
                     t0 = time.perf_counter()
                     with trace.span("average", round=r):
@@ -400,6 +408,15 @@ class KubeModel(ABC):
                 t0 = time.perf_counter()
                 with trace.span("average_buffers"):
                     self._averager.average_buffers_(comm)
+                self.sync_seconds += time.perf_counter() - t0
+            if self.ema is not None and local_rounds:
+                # K-AVG rounds: every worker averaged its own trajectory.  The EMA is linear in the
+                # weights, so the mean of the workers' EMAs is the EMA of the mean trajectory; only
+                # ragged tail rounds (a worker without data takes no steps) depart from that.  A
+                # task of grad-sync rounds alone leaves the ranks bit-identical: nothing to do.
+                t0 = time.perf_counter()
+                with trace.span("average_ema"):
+                    self.ema.average_(comm)
                 self.sync_seconds += time.perf_counter() - t0
         finally:
             self._sync_mode = "local"
@@ -579,6 +596,8 @@ class KubeModel(ABC):
             ts += [p for p in self._network.parameters()]
             ts += [p.grad for p in self._network.parameters() if p.grad is not None]
             ts += [b for b in self._network.buffers()]
+        if self.ema is not None:
+            ts += self.ema.state_tensors()
         opt = self.optimizer
         host = None
         if opt is not None:
@@ -627,7 +646,13 @@ class KubeModel(ABC):
         self._averager.broadcast_(comm, 0)
         acc, loss, nb = 0.0, 0.0, 0
         dev_sums = None          # device-side [acc, loss] accumulation (one read-back)
-        with torch.no_grad():
+        # with an EMA (configure_ema, validate on) the pass runs on the averaged weights: swapped
+        # into the buffers the (captured) eval forwards read, and swapped back before returning
+        averaged = contextlib.nullcontext()
+        if self.ema is not None and self._ema_validate:
+            self.ema.broadcast_(comm, 0)      # as the model above (BN statistics differ per rank in-epoch)
+            averaged = self.ema.applied()
+        with torch.no_grad(), averaged:
             for idx, batch in enumerate(self._batches()):
                 _progress()
                 batch = self._batch_to_device(batch)
@@ -657,7 +682,8 @@ class KubeModel(ABC):
         self._set_device()
         if ctx is not None and ctx.checkpoint and getattr(self, "_infer_ckpt", None) != ctx.checkpoint:
             from ..store.ckpt import load_checkpoint
-            load_checkpoint(self._network, ctx.checkpoint)
+            # a function that validates on its EMA serves it too (the live weights if the file has none)
+            load_checkpoint(self._network, ctx.checkpoint, use_ema=self.ema is not None and self._ema_validate)
             self._infer_ckpt = ctx.checkpoint
         self._network.eval()
         with torch.no_grad():
@@ -675,6 +701,7 @@ class KubeModel(ABC):
     def _set_device(self):
         if self.platform == "cpu" or not torch.cuda.is_available():
             self.device = torch.device("cpu")
+            self._make_ema()
             return
         ctx = current_task()
         if ctx is not None and ctx.device is not None and getattr(ctx.device, "type", None) == "cuda":
@@ -686,6 +713,20 @@ class KubeModel(ABC):
             self._network.to(self.device)
             from ..nn.flat import flatten_module
             self._flat = flatten_module(self._network, self.device)
+        self._make_ema()
+
+    def _make_ema(self):
+        """Once per resident model, after the network sits in its buffers: ``configure_ema``."""
+        if self._ema_configured:
+            return
+        self._ema_configured = True
+        cfg = self.configure_ema()
+        if cfg is None:
+            return
+        cfg = dict(cfg)
+        self._ema_validate = bool(cfg.pop("validate", True))
+        from ..optim import EMA
+        self.ema = EMA(self._network, **cfg)
 
     # ---- MI355X helper: graph-captured step --------------------------------------------------
     MAX_GRAPHS = 8
@@ -728,6 +769,9 @@ class KubeModel(ABC):
         return float(opt.grad_norm_tensor().item())
 
     _last_norm = None        # CPU path with a stock torch optimizer: torch's returned norm
+    ema = None               # weight EMA (configure_ema), created once by _set_device
+    _ema_validate = False    # validation / inference run on the averaged weights
+    _ema_configured = False
     _step_max_norm = None    # threshold given through step(): kept across _config_optimizer
 
     def step(self, x, y, loss_fn=None, forward=None, max_grad_norm=None):
@@ -756,13 +800,16 @@ class KubeModel(ABC):
                 self._last_norm = torch.nn.utils.clip_grad_norm_(
                     [p for g in self.optimizer.param_groups for p in g["params"]], float(max_grad_norm))
             self.optimizer.step()
+            if self.ema is not None:
+                self.ema.update()
             return loss
         if torch_clip:
             raise ValueError("step(max_grad_norm=) on the GPU needs a fused optimizer (SGD / Adam / AdamW)")
         grad = self._sync_mode == "grad"
         comm = self._grad_comm if grad else None
         key = (tuple(x.shape), tuple(y.shape), x.dtype, y.dtype, id(forward or loss_fn), grad,
-               id(comm) if comm is not None else None, bool(getattr(self.optimizer, "clips", False)))
+               id(comm) if comm is not None else None, self.ema is not None,
+               bool(getattr(self.optimizer, "clips", False)))
         g = self._graphs.get(key)
         if g is None:
             g = self._build_step(key, x, y, loss_fn, comm, forward)
@@ -792,7 +839,7 @@ class KubeModel(ABC):
                                  group=comm.group if comm is not None else None,
                                  world=comm.world if comm is not None else 1,
                                  plan=plan, peer=peer, comm_timing=self.COMM_TIMING if comm is not None else 0,
-                                 forward=forward)
+                                 forward=forward, ema=self.ema)
             self.logger.info("train step graph: batch %s, comm %s, plan %s, transport %s", tuple(x.shape),
                              comm.world if comm is not None else 1, plan.tag() if plan is not None else None,
                              type(st.peer).__name__ if st.peer is not None else None)
@@ -882,6 +929,14 @@ class KubeModel(ABC):
     # ---- user hooks (network.py:463-476) --------------------------------------------------
     def configure_optimizers(self) -> torch.optim.Optimizer:
         pass
+
+    def configure_ema(self):
+        """None (no weight EMA), or a dict of :class:`kubeml_amd.optim.EMA` keyword arguments
+        (``decay``, ``update_every``, ``warmup``), optionally with ``validate`` (default True:
+        validation and inference run on the averaged weights).  ``self.step`` updates the EMA
+        inside its captured step; a hand-written loop calls ``self.ema.update()`` after
+        ``optimizer.step()``.  Checkpoints carry it as ``ema.<name>`` tensors."""
+        return None
 
     def init(self):
         pass

@@ -10,6 +10,11 @@ Loading never executes code from the file (safetensors only).
 
 Files: ``<store>/checkpoints/<jobId>.safetensors`` and a JSON sidecar with the epoch /
 history at save time, used for resume.
+
+A model trained with a weight EMA (:class:`kubeml_amd.optim.EMA`) adds the tensors
+``ema.<name>`` (one per fp32 ``state_dict`` entry) and ``ema.__ctl__`` (its int32 counters), and
+``"ema": {"decay", "updates"}`` to the sidecar.  They never reach ``module.load_state_dict``, so
+such a file still loads strictly into a plain model.
 """
 from __future__ import annotations
 
@@ -46,10 +51,17 @@ def state_dict_cpu(module: torch.nn.Module) -> Dict[str, torch.Tensor]:
     return out
 
 
+def _ema_side(ema) -> dict:
+    return {"ema": {"decay": ema.decay, "updates": ema.updates}}
+
+
 def save_checkpoint(module: torch.nn.Module, path: str, job_id: str = "", epoch: int = 0,
-                    extra: Optional[dict] = None) -> str:
+                    extra: Optional[dict] = None, ema=None) -> str:
     from safetensors.torch import save_file
     sd = state_dict_cpu(module)
+    if ema is not None:
+        sd.update(ema.state_dict())
+        extra = {**(extra or {}), **_ema_side(ema)}
     meta = {"format": FORMAT, "jobId": job_id, "epoch": str(epoch), "keys": "{jobId}:{name}"}
     os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
     tmp = path + ".tmp"
@@ -97,7 +109,7 @@ class AsyncCheckpointer:
         return out
 
     def save(self, module: torch.nn.Module, path: str, job_id: str = "", epoch: int = 0,
-             extra: Optional[dict] = None) -> Optional[BaseException]:
+             extra: Optional[dict] = None, ema=None) -> Optional[BaseException]:
         """Snapshot ``module`` now and write it in the background.  Returns the error of
         the PREVIOUS background write, if it failed (this snapshot is still taken and
         written: a failed epoch-``e`` write never costs the epoch-``e+1`` checkpoint, and
@@ -105,6 +117,9 @@ class AsyncCheckpointer:
         import threading
         prev = self._join()
         sd = self._snapshot(module)
+        if ema is not None:          # dense CPU copies of the averaged tensors and the counters
+            sd.update(ema.state_dict())
+            extra = {**(extra or {}), **_ema_side(ema)}
         meta = {"format": FORMAT, "jobId": job_id, "epoch": str(epoch), "keys": "{jobId}:{name}"}
         side = {"jobId": job_id, "epoch": epoch, "tensors": len(sd), **(extra or {})}
 
@@ -147,10 +162,23 @@ def load_state(path: str) -> Dict[str, torch.Tensor]:
     return load_file(path)
 
 
-def load_checkpoint(module: torch.nn.Module, path: str, strict: bool = True) -> dict:
+EMA_PREFIX, EMA_CTL = "ema.", "ema.__ctl__"
+
+
+def load_checkpoint(module: torch.nn.Module, path: str, strict: bool = True, ema=None,
+                    use_ema: bool = False) -> dict:
     """Load a checkpoint into ``module`` (any device / flat-buffer layout); returns the
-    sidecar metadata (epoch, ...) if present."""
+    sidecar metadata (epoch, ...) if present.  The ``ema.*`` tensors of a file saved with a weight
+    EMA go to ``ema`` (an :class:`kubeml_amd.optim.EMA` of ``module``) when one is given and never
+    to ``module.load_state_dict``; ``use_ema=True`` loads them as the model's weights instead of
+    the live ones (the live ones where the file has no average of a tensor)."""
     sd = load_state(path)
+    ema_sd = {}
+    if EMA_CTL in sd:
+        ema_sd = {k: v for k, v in sd.items() if k.startswith(EMA_PREFIX)}
+        sd = {k: v for k, v in sd.items() if k not in ema_sd}
+    if use_ema:
+        sd = {k: ema_sd.get(EMA_PREFIX + k, v) for k, v in sd.items()}
     own = module.state_dict()
     conv = {}
     for k, v in sd.items():
@@ -163,6 +191,8 @@ def load_checkpoint(module: torch.nn.Module, path: str, strict: bool = True) -> 
     sp = getattr(module, "_kml_flat", None)
     if sp is not None:
         sp.refresh_shadow()
+    if ema is not None and ema_sd:
+        ema.load_state_dict(ema_sd)
     side = path + ".json"
     return read_json(side) if os.path.exists(side) else {}
 
