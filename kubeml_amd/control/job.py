@@ -126,6 +126,7 @@ class TrainJob:
         self.thread: Optional[threading.Thread] = None
         self.images_per_second = 0.0
         self.last_sync_seconds = 0.0
+        self.last_lr = None            # the LR the last epoch ended on (functions with configure_lr_schedule)
         self.last_grad_rounds = 0
         self.done = threading.Event()
         self.resume_from = getattr(opts, "resume_from", "") or ""
@@ -295,6 +296,7 @@ class TrainJob:
                 hbm = max((v.get("hbm_bytes", 0) for v in ok.values()), default=0)
                 self.last_sync_seconds = max((v.get("sync_seconds", 0.0) for v in ok.values()), default=0.0)
                 self.last_grad_rounds = max((v.get("grad_rounds", 0) for v in ok.values()), default=0)
+                self.last_lr = next((v["lr"] for _, v in sorted(ok.items()) if "lr" in v), None)
                 modes = sorted({v.get("sync_mode") for v in ok.values() if v.get("sync_mode")})
                 if modes:
                     self.history.sync_mode.append("+".join(modes))
@@ -406,7 +408,7 @@ class TrainJob:
                 self._push_metrics()
                 self.log.info("epoch finished", epoch=self.epoch, loss=loss, seconds=elapsed,
                               parallelism=self.parallelism, images_per_second=self.images_per_second,
-                              sync_seconds=self.last_sync_seconds, grad_sync_rounds=self.last_grad_rounds,
+                              sync_seconds=self.last_sync_seconds, grad_sync_rounds=self.last_grad_rounds, lr=self.last_lr,
                               checksums={str(r): c for r, c in sorted(self.checksums[-1].items())}
                               if self.checksums else None)
                 if not self.static and self.epoch < E:

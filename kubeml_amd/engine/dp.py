@@ -68,7 +68,8 @@ def make_train_step(model: torch.nn.Module, space, optimizer, loss_fn: Callable,
                     extra_state: Sequence[torch.Tensor] = (), comm_dtype=None,
                     opt_overlap: Optional[bool] = None, advance=None, plan=None, peer=None,
                     ride: Optional[bool] = None,
-                    comm_timing: int = 0, forward: Optional[Callable] = None, ema=None) -> GraphedTrainStep:
+                    comm_timing: int = 0, forward: Optional[Callable] = None, ema=None,
+                    lr_schedule=None) -> GraphedTrainStep:
     """Build (not capture) the train step on static input buffers ``x``/``y``.
 
     pre():  runs first inside the step (e.g. on-device augmentation into ``x``)
@@ -114,7 +115,15 @@ def make_train_step(model: torch.nn.Module, space, optimizer, loss_fn: Callable,
             leave the fp32 master complete only on the rank's own chunk, so with an EMA they run as
             the exact all-reduce plan (warning logged).  Follow-up: keep the EMA per chunk and gather
             it when it is read.  None: every launch and result is what it was.
+    lr_schedule: a :class:`kubeml_amd.optim.LRSchedule` attached to ``optimizer``: its one launch runs in
+            ``post()``, on the compute stream after every LR reader of the step (end-of-step launch, SGD
+            riders, per-stage ranges, the update inside the shard collective: all joined by then) and
+            before every reader of the next, and writes the next step's LR; its counter and the LR words
+            join the tensors restored after the capture warm-up, so the first replay runs with the LR
+            that was in place before the capture.  None: every launch is what it was.
     """
+    if lr_schedule is not None and lr_schedule.optimizer is not optimizer:
+        raise ValueError("make_train_step: the LR schedule must be attached to this step's optimizer")
     if ema is not None and ema.space is not space:
         raise ValueError("make_train_step: the EMA must average this step's flat space")
     comm = world > 1 or force_comm
@@ -223,6 +232,14 @@ def make_train_step(model: torch.nn.Module, space, optimizer, loss_fn: Callable,
             if inner_post is not None:
                 inner_post()
             ema.update()
+    if lr_schedule is not None:
+        sched_post = post
+        extra_state = list(extra_state) + lr_schedule.state_tensors()
+
+        def post():
+            if sched_post is not None:
+                sched_post()
+            lr_schedule._write(1)
     if (comm and overlap and staged_ok) or opt_overlap or staged_shard:
         from .staged import StagedForwardBackward
 
@@ -352,6 +369,15 @@ def make_train_step(model: torch.nn.Module, space, optimizer, loss_fn: Callable,
 
         def on_replay():
             space._master_stale = True
+
+    if lr_schedule is not None:
+        # host side of a replay: the schedule's bound on t (float(t) must stay exact)
+        inner_replay = on_replay
+
+        def on_replay():
+            if inner_replay is not None:
+                inner_replay()
+            lr_schedule._replayed()
 
     optimizer.set_grad_scale(scale)
     step = step_ref["step"] = GraphedTrainStep(fwd_bwd, opt_step, [space.grad], group=group, use_graph=use_graph, warmup=warmup,

@@ -2180,6 +2180,45 @@ def ema_swap_(state, ema, shadow, n_params):
     HIP.call("kml_ema_swap", "p p p l l s", _p(state), _p(ema), _p(shadow), ema.numel(), n_params, _s())
 
 
+# ---- learning-rate schedules (csrc/kernels/lr_schedule.hip) -------------------------------------
+
+LR_KINDS = ("constant", "linear", "polynomial", "cosine", "step")     # the kernel's kind codes, in order
+LR_MAX_MILESTONES = 8                                                 # KML_LR_MILESTONES
+
+
+def lr_schedule_(out, rows, stride, base, ctl, pos, last, advance, kind, warmup, total, min_ratio=0.0,
+                 warmup_start=0.0, power=1.0, gamma=0.1, milestones=()):
+    """One single-block launch: ``out[r * stride] = base[r] * f(x)`` for ``r < rows``, every other word of
+    ``out`` untouched; ``x = pos[0] + float(ctl[0] + advance) * pos[1]``, then ``ctl[0] += advance`` and
+    ``last = [x, f]``.  ``f``: the warm-up ramp from ``warmup_start`` below ``warmup``, then ``min_ratio +
+    (1 - min_ratio) * d`` with ``d`` by ``kind`` (:data:`LR_KINDS`) over ``[warmup, total]``; ``step`` is
+    ``gamma ** (milestones <= x)`` and reads neither ``total`` nor ``min_ratio``.  The counter, the position
+    and the base LRs are read from device memory, so a captured launch follows them."""
+    rows, stride, advance = int(rows), int(stride), int(advance)
+    _chk(out, F32, "out")
+    if rows < 1 or stride < 1 or out.numel() < (rows - 1) * stride + 1:
+        raise ValueError(f"lr_schedule_: out holds {out.numel()} words, {rows} row(s) of stride {stride} do not fit")
+    for t, dt, n, nm in ((base, F32, rows, "base"), (ctl, torch.int32, 4, "ctl"), (pos, F32, 2, "pos"),
+                         (last, F32, 2, "last")):
+        _chk(t, dt, nm)
+        if t.numel() < n or t.device != out.device:
+            raise ValueError(f"lr_schedule_: {nm} must hold {n} element(s) on the device of out")
+    if advance not in (0, 1):
+        raise ValueError("lr_schedule_: advance is 0 or 1")
+    if kind not in LR_KINDS:
+        raise ValueError(f"lr_schedule_: kind is one of {LR_KINDS}, got {kind!r}")
+    ms = [float(v) for v in milestones]
+    if len(ms) > LR_MAX_MILESTONES:
+        raise ValueError(f"lr_schedule_: at most {LR_MAX_MILESTONES} milestones")
+    total = 0.0 if total is None else float(total)
+    if not float(warmup) >= 0.0 or (kind != "step" and not total > float(warmup)):
+        raise ValueError("lr_schedule_: warmup >= 0 and total > warmup")
+    ms8 = ms + [0.0] * (LR_MAX_MILESTONES - len(ms))
+    HIP.call("kml_lr_schedule", "p i i p p p p i i f f f f f f i f f f f f f f f s", _p(out), rows, stride, _p(base),
+             _p(ctl), _p(pos), _p(last), advance, LR_KINDS.index(kind), float(warmup), total, float(min_ratio),
+             float(warmup_start), float(power), float(gamma), len(ms), *ms8, _s())
+
+
 # --------------------------------------------------------------------------------------
 # data
 # --------------------------------------------------------------------------------------

@@ -39,6 +39,10 @@ LR scalar.  A single-group optimizer launches exactly what it always did.
 large-batch recipes: two launches per step (per-tensor norms, then the update), a table row per
 tensor instead of the granule bytes, everything else as above.
 
+:class:`~kubeml_amd.optim.lr_schedule.LRSchedule` moves the learning rate every step from the device: one
+single-block launch writes ``base * f(position)`` into the words the launches above read, so a captured
+step follows a warm-up / decay schedule without host work between replays.
+
 :class:`~kubeml_amd.optim.ema.EMA` keeps an exponential moving average of the flat state prefix (weights
 and BN statistics) in one launch per step, for validation, checkpoints and inference.
 
@@ -54,7 +58,7 @@ from typing import Dict, List
 import torch
 
 __all__ = ["SGD", "Adam", "AdamW", "LAMB", "LARS", "from_torch", "with_max_grad_norm", "no_decay_groups",
-           "layerwise_groups", "FusedOptimizer", "EMA"]
+           "layerwise_groups", "FusedOptimizer", "EMA", "LRSchedule", "lr_factor"]
 
 MAX_GROUPS = 8            # rows of the kernels' hyper-parameter table (KML_MAX_GROUPS)
 _PER_GROUP = ("lr", "weight_decay")     # what may differ between parameter groups
@@ -80,11 +84,17 @@ class _Tables:
     def __init__(self, space, rows):
         self.space, self.rows = space, rows
         self.hp = torch.tensor(rows, dtype=torch.float32).to(space.device)
+        self.scheduled = False     # column 0 (the LR) is written on the device by an LRSchedule
 
     def refresh(self, rows):
-        """hp := rows when they changed.  A capturing stream reads the table as it stands."""
+        """hp := rows when they changed.  A capturing stream reads the table as it stands.  The LR
+        column of a scheduled table is the schedule's: host values never overwrite it."""
         if rows != self.rows and not torch.cuda.is_current_stream_capturing():
-            self.hp.copy_(torch.tensor(rows, dtype=torch.float32))
+            new = torch.tensor(rows, dtype=torch.float32)
+            if self.scheduled:
+                self.hp[:, 1:].copy_(new[:, 1:])
+            else:
+                self.hp.copy_(new)
             self.rows = rows
 
 
@@ -96,6 +106,7 @@ class FusedOptimizer(torch.optim.Optimizer):
     _max_groups = MAX_GROUPS     # None: no limit (a table row per tensor, not per group)
     _STATE_NAMES = ()            # the per-element fp32 state buffers of a flat space
     _cpu_ranges = False          # step_range also has a torch form over a CPU flat space
+    _lr_schedule = None          # the attached optim.LRSchedule: it owns the device LR words
 
     def __init__(self, params, defaults):
         super().__init__(params, defaults)
@@ -143,6 +154,9 @@ class FusedOptimizer(torch.optim.Optimizer):
 
     def add_param_group(self, param_group):
         """torch's, then the checks of the constructor; the cached tables are rebuilt."""
+        if self._lr_schedule is not None:
+            raise ValueError("add_param_group after an LR schedule was attached: the schedule wrote this "
+                             "optimizer's LR tables; attach it after the last group")
         super().add_param_group(param_group)
         if hasattr(self, "_tables"):          # (torch's constructor adds the first groups itself)
             self._tables.clear()
@@ -236,7 +250,18 @@ class FusedOptimizer(torch.optim.Optimizer):
     def set_lr(self, lr):
         """A number sets every group's LR; a sequence sets one LR per group (in group order).
         The device scalar (group 0's LR) and the launches' tables follow, so a captured
-        step runs with the new values without re-capture."""
+        step runs with the new values without re-capture.  With an :class:`LRSchedule` attached these
+        are the base (peak) LRs: the schedule rewrites the current LR at its unchanged position."""
+        if self._lr_schedule is not None:
+            if isinstance(lr, (list, tuple)) or (isinstance(lr, torch.Tensor) and lr.dim() > 0):
+                lrs = [float(v) for v in lr]
+                if len(lrs) != len(self.param_groups):
+                    raise ValueError(f"set_lr: {len(lrs)} learning rates for {len(self.param_groups)} parameter "
+                                     f"groups")
+            else:
+                lrs = [float(lr)] * len(self.param_groups)
+            self._lr_schedule._set_base(lrs)
+            return
         if isinstance(lr, (list, tuple)) or (isinstance(lr, torch.Tensor) and lr.dim() > 0):
             lrs = [float(v) for v in lr]
             if len(lrs) != len(self.param_groups):
@@ -251,6 +276,14 @@ class FusedOptimizer(torch.optim.Optimizer):
             t.fill_(float(lr))
         for tb in self._tables.values():
             tb.refresh(self._hp_rows(tb.space))
+
+    def _lr_outputs(self):
+        """[(tensor, rows, row stride, parameter-group index per row)]: the device words the launches over
+        the GPU spaces read their LR from (after :meth:`prepare`), for an :class:`LRSchedule`."""
+        if self.grouped:
+            n = len(self.param_groups)
+            return [(tb.hp, n, 2, list(range(n))) for tb in self._tables.values()]
+        return [(t, 1, 1, [0]) for t in self._scalars_named("lr")]
 
     def set_grad_scale(self, s: float):
         """Folded into the step: the DP all-reduce SUMs, the optimizer averages."""
@@ -751,3 +784,4 @@ def no_decay_groups(module: torch.nn.Module, weight_decay: float):
 
 from .layerwise import LAMB, LARS, layerwise_groups  # noqa: E402  (needs FusedOptimizer above)
 from .ema import EMA  # noqa: E402
+from .lr_schedule import LRSchedule, lr_factor  # noqa: E402

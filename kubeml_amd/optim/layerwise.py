@@ -87,6 +87,12 @@ class _Layerwise(FusedOptimizer):
 
     _prepare_tables = layer_tables
 
+    def _lr_outputs(self):
+        """A row per tensor of every GPU space: column 0 of its [T, 4] table (a tensor in no group: None)."""
+        of = {id(p): k for k, g in enumerate(self.param_groups) for p in g["params"]}
+        return [(tb.hp, len(tb.space.params), 4, [of.get(id(p)) for p in tb.space.params])
+                for tb in self._tables.values()]
+
     def trust_ratios(self) -> torch.Tensor:
         """The last step's trust ratio of every tensor as one fp32 tensor: on a GPU the device tensor
         the step wrote (no synchronisation), in the flat space's parameter order (``space.params``);

@@ -220,6 +220,8 @@ class Worker:
                    "end_checksum": ctx.extra.get("end_checksum"),
                    "grad_rounds": int(ctx.extra.get("grad_rounds", 0)),
                    "sync_mode": ctx.extra.get("sync_mode")}
+            if "lr" in ctx.extra:       # configure_lr_schedule: the LR the task ended on
+                out["lr"] = float(ctx.extra["lr"])
             if self.use_gpu:
                 import torch
                 out["hbm_bytes"] = int(torch.cuda.max_memory_allocated(self.device))

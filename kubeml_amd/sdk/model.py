@@ -163,12 +163,14 @@ class KubeModel(ABC):
         optimizer that only differs in LR is kept and retuned through its device LR
         scalar, so captured hipGraphs stay valid."""
         opt = self.configure_optimizers()
-        if opt is not None and self.device is not None and self.device.type == "cuda":
+        sched_cfg = self._lr_schedule_config()
+        if opt is not None and self.device is not None and (self.device.type == "cuda" or sched_cfg is not None):
             from ..optim import from_torch
             try:
-                opt = from_torch(opt)
+                opt = from_torch(opt)       # (a schedule attaches to the fused classes, on the CPU too)
             except TypeError:
-                pass
+                if sched_cfg is not None:
+                    raise
         if self._step_max_norm is not None and getattr(opt, "clips", None) is False:
             # step(max_grad_norm=) turned clipping on: the fresh optimizer clips alike, so the
             # resident one (and its graphs) is kept below
@@ -189,6 +191,47 @@ class KubeModel(ABC):
         self.optimizer = opt
         if opt is not None and hasattr(opt, "set_grad_scale"):
             opt.set_grad_scale(1.0)
+        if sched_cfg is not None and opt is not None and (
+                self.lr_schedule is None or self.lr_schedule.optimizer is not opt):
+            # once per resident optimizer (the retune above moved its peak LR, nothing else)
+            from ..optim import LRSchedule
+            self.lr_schedule = LRSchedule(opt, **sched_cfg)
+
+    def _lr_schedule_config(self):
+        """``configure_lr_schedule`` with its epoch-unit keys renamed for :class:`LRSchedule`; asked once
+        per resident model."""
+        if not self._lr_schedule_asked:
+            self._lr_schedule_asked = True
+            cfg = self.configure_lr_schedule()
+            if cfg is not None:
+                cfg = dict(cfg)
+                for unit in ("warmup", "total"):
+                    if unit in cfg:
+                        raise ValueError(f"configure_lr_schedule measures position in epochs: give {unit}_epochs "
+                                         f"(step-unit schedules go through optim.LRSchedule in a hand-written loop)")
+                    if unit + "_epochs" in cfg:
+                        cfg[unit] = cfg.pop(unit + "_epochs")
+            self._lr_schedule_cfg = cfg
+        return self._lr_schedule_cfg
+
+    def _task_steps(self, intervals) -> int:
+        """Minibatches this worker runs over the document ranges ``intervals`` (documents are
+        64-sample subsets; the split's last one may be short): the batch plan of ``_train`` / ``_warm``."""
+        from ..api.types import STORAGE_SUBSET_SIZE
+        ds = self._dataset
+        n = int(ds._store.open(ds.dataset, "train")[1].shape[0])
+        steps = 0
+        for start, end in intervals:
+            rows = min(end * STORAGE_SUBSET_SIZE, n) - start * STORAGE_SUBSET_SIZE
+            steps += -(-max(rows, 0) // self.batch_size)
+        return steps
+
+    def last_lr(self):
+        """The learning rate now in place, one per parameter group (``configure_lr_schedule``: one
+        device read), else the optimizer's host values."""
+        if self.lr_schedule is not None:
+            return self.lr_schedule.last_lr()
+        return [float(g["lr"]) for g in self.optimizer.param_groups]
 
     def _drop_shards(self):
         """Close the sharded-update transports of this model (collective: every worker runs the
@@ -323,6 +366,12 @@ class KubeModel(ABC):
         assigned = splits[fid]
         per = max(get_subset_period(K, self.batch_size, assigned), 1)
         intervals = list(range(assigned.start, assigned.stop, per))
+        if self.lr_schedule is not None:
+            # position in epochs: x = epoch + i / steps over this task's steps, so every worker crosses
+            # [epoch, epoch + 1) once whatever its shard, K or this epoch's parallelism; t restarts at 0
+            steps = self._task_steps([(i, min(assigned.stop, i + per)) for i in intervals])
+            if steps:
+                self.lr_schedule.set_position(float(self.epoch), 1.0 / steps)
         rounds = max_rounds(num_docs, N, K, self.batch_size) if comm.world > 1 else len(intervals)
         # rounds in which EVERY worker has data (uneven shards differ by at most one doc)
         full_rounds = min(-(-len(sp) // max(get_subset_period(K, self.batch_size, sp), 1)) for sp in splits)
@@ -431,6 +480,8 @@ class KubeModel(ABC):
             ctx.extra["end_checksum"] = self.model_checksum()
         if ctx is not None:   # reported to the job driver with the task result (metrics)
             ctx.extra["sync_seconds"] = self.sync_seconds
+            if self.lr_schedule is not None:
+                ctx.extra["lr"] = self.lr_schedule.last_lr()[0]
             ctx.extra["grad_rounds"] = grad_rounds
             ctx.extra["sync_mode"] = ("grad-allreduce" if grad_rounds else
                                       "kavg-async-staleness1" if use_async else "kavg")
@@ -598,6 +649,8 @@ class KubeModel(ABC):
             ts += [b for b in self._network.buffers()]
         if self.ema is not None:
             ts += self.ema.state_tensors()
+        if self.lr_schedule is not None:
+            ts += self.lr_schedule.state_tensors()
         opt = self.optimizer
         host = None
         if opt is not None:
@@ -756,6 +809,11 @@ class KubeModel(ABC):
         self._drop_shards()
         self.optimizer = with_max_grad_norm(opt, v)
         self._step_max_norm = float(v)
+        if self.lr_schedule is not None:      # the schedule follows the optimizer, position and base LRs kept
+            from ..optim import LRSchedule
+            sd = self.lr_schedule.state_dict()
+            self.lr_schedule = LRSchedule(self.optimizer, **self.lr_schedule.shape)
+            self.lr_schedule.load_state_dict(sd)
         return False
 
     def last_grad_norm(self) -> float:
@@ -772,6 +830,9 @@ class KubeModel(ABC):
     ema = None               # weight EMA (configure_ema), created once by _set_device
     _ema_validate = False    # validation / inference run on the averaged weights
     _ema_configured = False
+    lr_schedule = None       # device LR schedule (configure_lr_schedule), attached to the resident optimizer
+    _lr_schedule_asked = False
+    _lr_schedule_cfg = None
     _step_max_norm = None    # threshold given through step(): kept across _config_optimizer
 
     def step(self, x, y, loss_fn=None, forward=None, max_grad_norm=None):
@@ -800,6 +861,8 @@ class KubeModel(ABC):
                 self._last_norm = torch.nn.utils.clip_grad_norm_(
                     [p for g in self.optimizer.param_groups for p in g["params"]], float(max_grad_norm))
             self.optimizer.step()
+            if self.lr_schedule is not None:
+                self.lr_schedule.step()
             if self.ema is not None:
                 self.ema.update()
             return loss
@@ -808,7 +871,7 @@ class KubeModel(ABC):
         grad = self._sync_mode == "grad"
         comm = self._grad_comm if grad else None
         key = (tuple(x.shape), tuple(y.shape), x.dtype, y.dtype, id(forward or loss_fn), grad,
-               id(comm) if comm is not None else None, self.ema is not None,
+               id(comm) if comm is not None else None, self.ema is not None, self.lr_schedule is not None,
                bool(getattr(self.optimizer, "clips", False)))
         g = self._graphs.get(key)
         if g is None:
@@ -839,7 +902,7 @@ class KubeModel(ABC):
                                  group=comm.group if comm is not None else None,
                                  world=comm.world if comm is not None else 1,
                                  plan=plan, peer=peer, comm_timing=self.COMM_TIMING if comm is not None else 0,
-                                 forward=forward, ema=self.ema)
+                                 forward=forward, ema=self.ema, lr_schedule=self.lr_schedule)
             self.logger.info("train step graph: batch %s, comm %s, plan %s, transport %s", tuple(x.shape),
                              comm.world if comm is not None else 1, plan.tag() if plan is not None else None,
                              type(st.peer).__name__ if st.peer is not None else None)
@@ -936,6 +999,16 @@ class KubeModel(ABC):
         validation and inference run on the averaged weights).  ``self.step`` updates the EMA
         inside its captured step; a hand-written loop calls ``self.ema.update()`` after
         ``optimizer.step()``.  Checkpoints carry it as ``ema.<name>`` tensors."""
+        return None
+
+    def configure_lr_schedule(self):
+        """None (the LR moves only through ``configure_optimizers``, once per epoch), or a dict of
+        :class:`kubeml_amd.optim.LRSchedule` keyword arguments with position measured in epochs, e.g.
+        ``dict(kind="cosine", warmup_epochs=5, total_epochs=90, min_ratio=0.0)`` (``kind``,
+        ``warmup_epochs``, ``total_epochs``, ``min_ratio``, ``warmup_start``, ``power``, ``gamma``,
+        ``milestones`` in epochs).  The LR of ``configure_optimizers`` is the peak; ``self.step`` moves the
+        LR every step inside its captured step, a hand-written loop calls ``self.lr_schedule.step()``
+        after ``optimizer.step()``.  ``self.last_lr()`` reads the current value."""
         return None
 
     def init(self):
