@@ -2295,6 +2295,123 @@ def mix_plan(ctr, n, B, H, W, mixup_alpha=0.0, cutmix_alpha=0.0, mix_prob=1.0, s
     return out
 
 
+def _pair(v, name):
+    """An int or a pair of ints as ``(h, w)``."""
+    hw = (v, v) if isinstance(v, int) else tuple(v)
+    if len(hw) != 2 or not all(isinstance(s, int) and s >= 1 for s in hw):
+        raise ValueError(f"{name} must be a positive int or a pair of them, got {v!r}")
+    return hw
+
+
+def _chk_rrc(scale, ratio):
+    s0, s1 = (float(v) for v in scale)
+    r0, r1 = (float(v) for v in ratio)
+    if not (0.0 < s0 <= s1 < math.inf):
+        raise ValueError(f"scale must be a range 0 < s0 <= s1, got {tuple(scale)}")
+    if not (0.0 < r0 <= r1 < math.inf):
+        raise ValueError(f"ratio must be a range 0 < r0 <= r1, got {tuple(ratio)}")
+    return s0, s1, r0, r1
+
+
+def resize_geometry(Hs, Ws, resize, crop):
+    """``Resize(resize)`` + ``CenterCrop(crop)`` of an ``Hs x Ws`` image with torchvision's
+    arithmetic, as ``(Rh, Rw, oy, ox)``: the shorter side becomes ``resize`` and the other one
+    ``int(resize * long / short)``; the crop window (``crop``: an int or ``(h, w)``) starts at
+    ``int(round((R - crop) / 2.0))`` (Python's ``round``).  A crop larger than a resized side is
+    a ``ValueError`` (torchvision would pad)."""
+    ch, cw = _pair(crop, "crop")
+    if Hs < 1 or Ws < 1 or not isinstance(resize, int) or resize < 1:
+        raise ValueError(f"resize_geometry: image {Hs} x {Ws}, resize {resize!r}")
+    if Ws <= Hs:
+        Rw, Rh = resize, int(resize * Hs / Ws)
+    else:
+        Rh, Rw = resize, int(resize * Ws / Hs)
+    if ch > Rh or cw > Rw:
+        raise ValueError(f"resize_geometry: crop {ch} x {cw} exceeds the resized image {Rh} x {Rw}")
+    return Rh, Rw, int(round((Rh - ch) / 2.0)), int(round((Rw - cw) / 2.0))
+
+
+def augment_resample(src_u8, labels_src, ctr, B, size, out=None, labels_out=None, targets_out=None, CP=8, train=True,
+                     flip=True, scale=(0.08, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0), resize=None,
+                     mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), mixup_alpha=0.0, cutmix_alpha=0.0,
+                     mix_prob=1.0, switch_prob=0.5):
+    """src_u8 [N,Hs,Ws,C] uint8 on device -> [B,Ho,Wo,CP] bf16 normalised batch of ``size`` (an
+    int or ``(Ho, Wo)``) starting at ctr[2], in one launch.
+
+    ``train=True`` is ``RandomResizedCrop(size, scale, ratio)`` + horizontal flip: every sample's
+    box follows torchvision's ``get_params`` and is a function of ``(ctr[0], ctr[1], sample)``
+    alone (:func:`rrc_plan` reads it back).  ``train=False`` is ``Resize(resize)`` +
+    ``CenterCrop(size)`` (:func:`resize_geometry`; ``resize`` defaults to ``round(max(size) /
+    0.875)``) and reads no randomness.
+
+    The filter is torch's antialiased bilinear one (``F.interpolate(mode="bilinear",
+    antialias=True, align_corners=False)``, PIL's) applied to the box: taps are clamped to the
+    box and renormalised there, "crop, then resize".  The raw 0..255 values are resampled in
+    fp32, normalised, and rounded once to bf16; unlike PIL there is no rounding to uint8 in
+    between, so the batch keeps those bits.
+
+    A mixup / CutMix alpha > 0 (training only) mixes as :func:`augment_mix` does, with the mix
+    plan ``mix_plan(ctr, 1, B, Ho, Wo, ...)`` over the output size, and returns packed fp32
+    ``[B, 3]`` targets in place of the int64 labels."""
+    _chk(src_u8, torch.uint8, "src", 4)
+    _chk(labels_src, torch.int64, "labels_src", 1)
+    _chk(ctr, F32, "ctr")
+    _chk_mix(mixup_alpha, cutmix_alpha, mix_prob, switch_prob)
+    s0, s1, r0, r1 = _chk_rrc(scale, ratio)
+    Ho, Wo = _pair(size, "size")
+    N, Hs, Ws, C = src_u8.shape
+    if C < 1 or C > 4 or CP < C or B < 1 or N < 1 or labels_src.numel() < N or ctr.numel() < 3 or len(mean) < C or \
+            len(std) < C:
+        raise ValueError(f"augment_resample: source {tuple(src_u8.shape)}, CP {CP}, B {B}")
+    Rh, Rw, oy, ox = Ho, Wo, 0, 0
+    if not train:
+        Rh, Rw, oy, ox = resize_geometry(Hs, Ws, int(round(max(Ho, Wo) / 0.875)) if resize is None else resize,
+                                         (Ho, Wo))
+    mix = bool(train) and (mixup_alpha > 0 or cutmix_alpha > 0)
+    if out is None:
+        out = torch.empty((B, Ho, Wo, CP), dtype=BF16, device=src_u8.device)
+    _chk(out, BF16, "out")
+    if out.numel() != B * Ho * Wo * CP:
+        raise ValueError("augment_resample: out does not match the batch")
+    if mix:
+        if targets_out is None:
+            targets_out = torch.empty((B, 3), dtype=F32, device=src_u8.device)
+        _chk(targets_out, F32, "targets_out")
+        second, want = targets_out, 3 * B
+    else:
+        if labels_out is None:
+            labels_out = torch.empty((B,), dtype=torch.int64, device=src_u8.device)
+        _chk(labels_out, torch.int64, "labels_out")
+        second, want = labels_out, B
+    if second.numel() != want:
+        raise ValueError("augment_resample: labels_out / targets_out do not match the batch")
+    mean_a = (torch.tensor(list(mean) + [0.0] * (4 - len(mean)), dtype=F32))
+    std_a = (torch.tensor(list(std) + [1.0] * (4 - len(std)), dtype=F32))
+    HIP.call("kml_augment_resample", "p p p p p p i i i i i i i i i i f f f f i i i i p p f f f f s", _p(src_u8),
+             _p(labels_src), _p(out), _p(None if mix else labels_out), _p(targets_out if mix else None), _p(ctr),
+             N, Hs, Ws, C, CP, B, Ho, Wo, int(bool(train)), int(bool(flip)), s0, s1, r0, r1, Rh, Rw, oy, ox,
+             mean_a.data_ptr(), std_a.data_ptr(), float(mixup_alpha), float(cutmix_alpha), float(mix_prob),
+             float(switch_prob), _s())
+    return out, second
+
+
+def rrc_plan(ctr, n, B, Hs, Ws, scale=(0.08, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0), flip=True, N=None):
+    """The boxes :func:`augment_resample` draws in train mode from an ``Hs x Ws`` source at steps
+    ``ctr[1] .. ctr[1] + n - 1`` for batch rows ``0 .. B - 1``, that is for the samples ``(ctr[2]
+    + b) % N`` (``N``: the number of stored samples; left out, the index does not wrap): fp32
+    ``[n, B, 6]`` rows ``(i, j, h, w, flip, fallback)`` with the box ``[i, i + h) x [j, j + w)``
+    and ``fallback`` 1 where all ten tries were rejected and the central crop was taken."""
+    _chk(ctr, F32, "ctr")
+    s0, s1, r0, r1 = _chk_rrc(scale, ratio)
+    N = 2 ** 31 - 1 if N is None else int(N)
+    if n < 1 or B < 1 or Hs < 1 or Ws < 1 or N < 1 or ctr.numel() < 3:
+        raise ValueError(f"rrc_plan: n {n}, B {B}, source {Hs} x {Ws}, N {N}")
+    out = torch.empty((n, B, 6), dtype=F32, device=ctr.device)
+    HIP.call("kml_rrc_plan", "p p i i i i i f f f f i s", _p(ctr), _p(out), int(n), int(B), N, int(Hs), int(Ws),
+             s0, s1, r0, r1, int(bool(flip)), _s())
+    return out
+
+
 # --------------------------------------------------------------------------------------
 # layout / misc
 # --------------------------------------------------------------------------------------
