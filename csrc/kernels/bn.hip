@@ -207,6 +207,96 @@ struct EarlyRows {
   }
 };
 
+// Per-channel vectors (gamma, beta, running / saved statistics, old gradients) are cold: the
+// optimizer or the previous step wrote them last.  Read inside the coefficient loop they cost one
+// more dependent memory round trip after the row reduction's barriers (two more in block 0, which
+// read-modify-writes the running statistics), so every kernel requests them at its top, beside the
+// partial rows and the data, for the thread's first BN_HOIST channels c = tid, tid + NT, ...;
+// later channels are loaded inside the loop, all of an iteration's loads before any use.
+// Two iterations cover C <= 512 at 256 threads (every BN of ResNet-18/34, the first two stages of
+// ResNet-50) without costing a register-path kernel a wave: hoisting eight (C = 2048) took the
+// backward applies from 3 waves per SIMD to 2 (profiles/r19/bn_one_round_trip.md).
+constexpr int BN_HOIST = 2;
+
+template <int NT, int HH = BN_HOIST>
+struct ChanRegs {
+  static constexpr int H = HH;
+  float v[H > 0 ? H : 1];
+  // nothing is requested when !on (a null pointer, a vector only block 0 needs: a uniform
+  // branch); channels past C load the clamped, valid index C - 1 and are never used (no branch
+  // around a single load: straight-line vmcnt)
+  __device__ __forceinline__ void issue(const float* __restrict__ p, bool on, int C, float dflt) {
+#pragma unroll
+    for (int h = 0; h < H; ++h) v[h] = dflt;
+    if (on) {
+#pragma unroll
+      for (int h = 0; h < H; ++h) v[h] = p[min((int)threadIdx.x + h * NT, C - 1)];
+    }
+  }
+};
+
+// the forward coefficient loop's operands: gamma, beta and (eval mode: every block; training:
+// the block `first` that updates them) the running statistics
+template <int NT, int H = BN_HOIST>
+struct FwdChan {
+  ChanRegs<NT, H> g, b, rm, rv;
+  __device__ __forceinline__ static bool needs_running(const float* run_mean, int mode, bool first) {
+    return mode != 0 || (first && run_mean != nullptr);
+  }
+  __device__ __forceinline__ void issue(const float* gamma, const float* beta, const float* run_mean,
+                                        const float* run_var, int mode, bool first, int C) {
+    const bool rs = needs_running(run_mean, mode, first);
+    g.issue(gamma, gamma != nullptr, C, 1.f);
+    b.issue(beta, beta != nullptr, C, 0.f);
+    rm.issue(run_mean, rs, C, 0.f);
+    rv.issue(run_var, rs, C, 0.f);
+  }
+};
+
+// scale / shift of every channel into LDS slot(c); block `first` also stores the saved statistics
+// and updates the running ones (training).  st: the summed [sum | sumsq] (training).
+template <int NT, int H, class Slot>
+__device__ __forceinline__ void bn_fwd_coefs(const FwdChan<NT, H>& ops, const float* st, const float* __restrict__ gamma,
+                                             const float* __restrict__ beta, float* __restrict__ save_mean,
+                                             float* __restrict__ save_rstd, float* __restrict__ run_mean,
+                                             float* __restrict__ run_var, long long M, int C, float eps,
+                                             float momentum, int mode, bool first, float* scale, float* shift,
+                                             Slot slot) {
+  auto coef = [&](int c, float g, float bb, float rm, float rv) {
+    float mean, var;
+    if (mode == 0) {
+      mean = st[c] / (float)M;
+      var = fmaxf(st[C + c] / (float)M - mean * mean, 0.f);
+    } else {
+      mean = rm;
+      var = rv;
+    }
+    const float rstd = rsqrtf(var + eps);
+    const int s = slot(c);
+    scale[s] = g * rstd;
+    shift[s] = bb - mean * g * rstd;
+    if (mode == 0 && first) {
+      if (save_mean) { save_mean[c] = mean; save_rstd[c] = rstd; }
+      if (run_mean) {
+        const float unb = M > 1 ? var * (float)M / (float)(M - 1) : var;
+        run_mean[c] = (1.f - momentum) * rm + momentum * mean;
+        run_var[c] = (1.f - momentum) * rv + momentum * unb;
+      }
+    }
+  };
+#pragma unroll
+  for (int h = 0; h < H; ++h) {
+    const int c = (int)threadIdx.x + h * NT;
+    if (c < C) coef(c, ops.g.v[h], ops.b.v[h], ops.rm.v[h], ops.rv.v[h]);
+  }
+  const bool rs = FwdChan<NT, H>::needs_running(run_mean, mode, first);
+  for (int c = (int)threadIdx.x + H * NT; c < C; c += NT) {
+    const float g = gamma ? gamma[c] : 1.f, bb = beta ? beta[c] : 0.f;
+    const float rm = rs ? run_mean[c] : 0.f, rv = rs ? run_var[c] : 0.f;
+    coef(c, g, bb, rm, rv);
+  }
+}
+
 // y = act((x - mean) * rstd * gamma + beta [+ res])
 // mode 0: training (stats = [sum, sumsq] over M rows); mode 1: eval (running stats)
 template <int NT>
@@ -223,6 +313,8 @@ __global__ __launch_bounds__(NT) void k_bn_apply(
   // this load are two dependent memory round trips otherwise)
   const long long n8 = M * C / 8;
   const long long i0 = blockIdx.x * (long long)NT + threadIdx.x;
+  FwdChan<NT> ops;
+  ops.issue(gamma, beta, run_mean, run_var, mode, blockIdx.x == 0, C);
   uint4 x0 = make_uint4(0, 0, 0, 0), r0 = make_uint4(0, 0, 0, 0);
   if (i0 < n8) {
     x0 = reinterpret_cast<const uint4*>(x)[i0];
@@ -234,28 +326,8 @@ __global__ __launch_bounds__(NT) void k_bn_apply(
     sum_partial_rows<NT>(stats, stats_rows, 2 * C, sums, reinterpret_cast<float4*>(sh + 4 * C));
     st = sums;
   }
-  for (int c = threadIdx.x; c < C; c += NT) {
-    float mean, var;
-    if (mode == 0) {
-      mean = st[c] / (float)M;
-      var = fmaxf(st[C + c] / (float)M - mean * mean, 0.f);
-    } else {
-      mean = run_mean[c];
-      var = run_var[c];
-    }
-    const float rstd = rsqrtf(var + eps);
-    const float g = gamma ? gamma[c] : 1.f, bb = beta ? beta[c] : 0.f;
-    scale[c] = g * rstd;
-    shift[c] = bb - mean * g * rstd;
-    if (mode == 0 && blockIdx.x == 0) {
-      if (save_mean) { save_mean[c] = mean; save_rstd[c] = rstd; }
-      if (run_mean) {
-        const float unb = M > 1 ? var * (float)M / (float)(M - 1) : var;
-        run_mean[c] = (1.f - momentum) * run_mean[c] + momentum * mean;
-        run_var[c] = (1.f - momentum) * run_var[c] + momentum * unb;
-      }
-    }
-  }
+  bn_fwd_coefs<NT>(ops, st, gamma, beta, save_mean, save_rstd, run_mean, run_var, M, C, eps, momentum, mode,
+                   blockIdx.x == 0, scale, shift, [](int c) { return c; });
   __syncthreads();
   const int CH = C / 8;
   for (long long i = i0; i < n8; i += (long long)gridDim.x * NT) {
@@ -449,6 +521,58 @@ __global__ __launch_bounds__(TPB) void k_bn_bwd_reduce2(
   }
 }
 
+// the backward coefficient loop's operands (ChanRegs): gamma, mean, rstd and the gradients — for
+// the kernels that sum partial rows the OLD dbeta / dgamma, which only block `first` needs and only
+// when it accumulates (with acc == 0 their contents are garbage and are never read)
+template <int NT, int H = BN_HOIST>
+struct BwdChan {
+  ChanRegs<NT, H> g, mu, rs, db, dg;
+  __device__ __forceinline__ void issue(const float* gamma, const float* mean, const float* rstd,
+                                        const float* dbeta, const float* dgamma, bool grads, int C) {
+    g.issue(gamma, gamma != nullptr, C, 1.f);
+    mu.issue(mean, true, C, 0.f);
+    rs.issue(rstd, true, C, 0.f);
+    db.issue(dbeta, grads, C, 0.f);
+    dg.issue(dgamma, grads, C, 0.f);
+  }
+};
+
+// Coefficients ka = gamma * rstd, kb = dbeta / M, kc = dgamma / M, mu, rs of every channel into
+// co[k * stride + slot(c)], k = 0..4, from the row sums sums[c] | sums[C + c] (which may be co's
+// own kb | kc area: a channel's sums are read before its coefficients are written).  Block `first`
+// stores the sums into dbeta / dgamma (acc: adds them onto the old values).
+template <int NT, int H, class Slot>
+__device__ __forceinline__ void bn_bwd_coefs(const BwdChan<NT, H>& ops, const float* sums, const float* __restrict__ gamma,
+                                             const float* __restrict__ mean, const float* __restrict__ rstd,
+                                             float* __restrict__ dgamma, float* __restrict__ dbeta, long long M, int C,
+                                             int acc, bool first, float* co, int stride, Slot slot) {
+  const float invM = 1.f / (float)M;
+  auto coef = [&](int c, float gm, float mu, float rs, float odb, float odg) {
+    const float sb = sums[c], sg = sums[C + c];
+    if (first) {  // one writer: store (overwrite) or add (accumulate)
+      dbeta[c] = acc ? odb + sb : sb;
+      dgamma[c] = acc ? odg + sg : sg;
+    }
+    const int s = slot(c);
+    co[s] = gm * rs;
+    co[stride + s] = sb * invM;
+    co[2 * stride + s] = sg * invM;
+    co[3 * stride + s] = mu;
+    co[4 * stride + s] = rs;
+  };
+#pragma unroll
+  for (int h = 0; h < H; ++h) {
+    const int c = (int)threadIdx.x + h * NT;
+    if (c < C) coef(c, ops.g.v[h], ops.mu.v[h], ops.rs.v[h], ops.db.v[h], ops.dg.v[h]);
+  }
+  const bool grads = first && acc;
+  for (int c = (int)threadIdx.x + H * NT; c < C; c += NT) {
+    const float gm = gamma ? gamma[c] : 1.f, mu = mean[c], rs = rstd[c];
+    const float odb = grads ? dbeta[c] : 0.f, odg = grads ? dgamma[c] : 0.f;
+    coef(c, gm, mu, rs, odb, odg);
+  }
+}
+
 __global__ __launch_bounds__(TPB) void k_bn_bwd_apply(
     const bf16_t* __restrict__ dy, const bf16_t* __restrict__ y, const bf16_t* __restrict__ x,
     const float* __restrict__ mean, const float* __restrict__ rstd, const float* __restrict__ gamma,
@@ -461,13 +585,15 @@ __global__ __launch_bounds__(TPB) void k_bn_bwd_apply(
   float* mu = sh + 3 * C;
   float* rs = sh + 4 * C;
   const float invM = 1.f / (float)M;
+  // no reduction precedes this loop: every channel's five loads are issued before its first use
   for (int c = threadIdx.x; c < C; c += TPB) {
     const float g = gamma ? gamma[c] : 1.f;
-    ka[c] = g * rstd[c];
-    kb[c] = dbeta[c] * invM;
-    kc[c] = dgamma[c] * invM;
-    mu[c] = mean[c];
-    rs[c] = rstd[c];
+    const float r = rstd[c], m = mean[c], sb = dbeta[c], sg = dgamma[c];
+    ka[c] = g * r;
+    kb[c] = sb * invM;
+    kc[c] = sg * invM;
+    mu[c] = m;
+    rs[c] = r;
   }
   __syncthreads();
   const long long n8 = M * C / 8;
@@ -512,8 +638,9 @@ __global__ __launch_bounds__(NT) void k_bn_bwd_apply_fin(
   float* kc = ka + 2 * C;
   float* mu = ka + 3 * C;
   float* rs = ka + 4 * C;
-  const float invM = 1.f / (float)M;
-  // first iteration's operands in flight while the partial rows are summed
+  // per-channel operands and the first iteration's data in flight while the partial rows are summed
+  BwdChan<NT> ops;
+  ops.issue(gamma, mean, rstd, dbeta, dgamma, blockIdx.x == 0 && acc, C);
   const long long n8 = M * C / 8;
   const long long i0 = blockIdx.x * (long long)NT + threadIdx.x;
   uint4 dy0 = make_uint4(0, 0, 0, 0), x0 = dy0, y0 = dy0;
@@ -550,19 +677,9 @@ __global__ __launch_bounds__(NT) void k_bn_bwd_apply_fin(
     }
     __syncthreads();
   }
-  for (int c = threadIdx.x; c < C; c += NT) {
-    const float sb = kb[c], sg = kc[c];
-    if (blockIdx.x == 0) {  // one writer: store (overwrite) or add (accumulate)
-      dbeta[c] = acc ? dbeta[c] + sb : sb;
-      dgamma[c] = acc ? dgamma[c] + sg : sg;
-    }
-    const float gm = gamma ? gamma[c] : 1.f;
-    ka[c] = gm * rstd[c];
-    kb[c] = sb * invM;
-    kc[c] = sg * invM;
-    mu[c] = mean[c];
-    rs[c] = rstd[c];
-  }
+  // kb | kc hold the sums and are contiguous; the coefficients go to ka kb kc mu rs in place
+  bn_bwd_coefs(ops, kb, gamma, mean, rstd, dgamma, dbeta, M, C, acc, blockIdx.x == 0, ka, C,
+                   [](int c) { return c; });
   __syncthreads();
   const int CH = C / 8;
   for (long long i = i0; i < n8; i += (long long)gridDim.x * NT) {
@@ -607,9 +724,17 @@ __host__ __device__ constexpr int bn_tslots(int C) { return 8 * bn_tstride(C >> 
 // channels: their scale / shift (or the backward coefficients) are read from LDS once,
 // into registers, and no per-element channel division or LDS read remains.  All V chunks
 // of every operand are loaded up front — before the statistics prologue — so the data
-// round trip overlaps the partial-row reduction instead of following it, and a thread
-// never waits on more than one memory round trip.  Out-of-range chunks load a clamped
-// (valid) index and skip the store (no branch around a load: straight-line vmcnt).
+// round trip overlaps the partial-row reduction instead of following it.  The per-channel
+// vectors of the coefficient loop (gamma, beta, block 0's running statistics; backward:
+// gamma, mean, rstd, block 0's old gradients when it accumulates) are requested there too
+// (ChanRegs, for C <= BN_HOIST * 256 = 512; later channels inside the loop), so the loop
+// only computes and stores and a thread never waits on more than one memory round trip —
+// with more than 16 partial rows per slice, one per further batch of rows.  Two exceptions,
+// both to keep the third wave per SIMD: the forward kernels with V >= 2 chunks per thread
+// hoist one iteration (C <= 256), and the pipelined backward kernel hoists none (its loop
+// loads every channel's vectors before their first use).  Out-of-range
+// chunks load a clamped (valid) index and skip the store (no branch around a load:
+// straight-line vmcnt).
 // ---------------------------------------------------------------------------------------
 struct BnApArgs {
   const bf16_t* x;
@@ -656,6 +781,10 @@ __device__ __forceinline__ void bn_apply_body(const BnApArgs& p, int bid, int nb
   const bool early = parts && BN_EARLY_ROWS(C, NT);
   EarlyRows er;
   if (early) er.issue(stats, stats_rows, 2 * C, NT);
+  // (one iteration, C <= 256, with two or more chunks per thread: the second costs the V = 2
+  // kernels their third wave per SIMD)
+  FwdChan<NT, V == 1 ? BN_HOIST : 1> ops;
+  ops.issue(gamma, beta, run_mean, run_var, mode, bid == 0, C);
   uint4 xv[V], rv[V];
 #pragma unroll
   for (int v = 0; v < V; ++v) xv[v] = reinterpret_cast<const uint4*>(x)[min(i0 + v * T, n8 - 1)];
@@ -670,31 +799,10 @@ __device__ __forceinline__ void bn_apply_body(const BnApArgs& p, int bid, int nb
     else sum_partial_rows<NT>(stats, stats_rows, 2 * C, sums, reinterpret_cast<float4*>(sh + 2 * TS + 2 * C));
     st = sums;
   }
-  for (int c = threadIdx.x; c < C; c += NT) {
-    float mean, var;
-    if (mode == 0) {
-      mean = st[c] / (float)M;
-      var = fmaxf(st[C + c] / (float)M - mean * mean, 0.f);
-    } else {
-      mean = run_mean[c];
-      var = run_var[c];
-    }
-    const float rstd = rsqrtf(var + eps);
-    const float g = gamma ? gamma[c] : 1.f, bb = beta ? beta[c] : 0.f;
-    // channel-transposed slots (bn_tstride): the 8-channel reads below hit consecutive words
-    // across consecutive lanes, these writes 64 distinct banks
-    const int tslot = (c & 7) * TSTR + (c >> 3);
-    scale[tslot] = g * rstd;
-    shift[tslot] = bb - mean * g * rstd;
-    if (mode == 0 && bid == 0) {
-      if (save_mean) { save_mean[c] = mean; save_rstd[c] = rstd; }
-      if (run_mean) {
-        const float unb = M > 1 ? var * (float)M / (float)(M - 1) : var;
-        run_mean[c] = (1.f - momentum) * run_mean[c] + momentum * mean;
-        run_var[c] = (1.f - momentum) * run_var[c] + momentum * unb;
-      }
-    }
-  }
+  // channel-transposed slots (bn_tstride): the 8-channel reads below hit consecutive words
+  // across consecutive lanes, these writes 64 distinct banks
+  bn_fwd_coefs<NT>(ops, st, gamma, beta, save_mean, save_rstd, run_mean, run_var, M, C, eps, momentum, mode,
+                   bid == 0, scale, shift, [TSTR](int c) { return (c & 7) * TSTR + (c >> 3); });
   __syncthreads();
   const int CH8 = C >> 3, j8 = i0 % CH8;
   float sc[8], sf[8];
@@ -812,16 +920,16 @@ __device__ __forceinline__ void bn_bwd_apply_body(const BnbArgs& p, int bid, int
   float4* red4 = reinterpret_cast<float4*>(sh);
   float* ka = sh + 4 * NT;
   float* kb = ka + C;
-  float* kc = ka + 2 * C;
-  float* mu = ka + 3 * C;
-  float* rs = ka + 4 * C;
-  const float invM = 1.f / (float)M;
   const int n8 = (int)(M * C / 8);
   const int T = nblk * NT;
   const int i0 = bid * NT + (int)threadIdx.x;
   const bool early = BN_EARLY_ROWS(C, NT);
   EarlyRows er;
   if (early) er.issue(part, G, 2 * C, NT);
+  // (not in the pipelined variant: its launches run several batches per thread, where one round
+  // trip is nothing and the ten registers are the third wave per SIMD)
+  BwdChan<NT, PIPE ? 0 : BN_HOIST> ops;
+  ops.issue(gamma, mean, rstd, dbeta, dgamma, bid == 0 && acc, C);
   uint4 dv[V], xv[V], yv[V];
 #pragma unroll
   for (int v = 0; v < V; ++v) {
@@ -842,20 +950,8 @@ __device__ __forceinline__ void bn_bwd_apply_body(const BnbArgs& p, int bid, int
   // reads below hit consecutive words across consecutive lanes (no LDS bank conflicts)
   float* tco = ka + 5 * C;  // [5][TS]: ka, kb/M, kc/M, mu, rs transposed (bn_tstride)
   const int TS = bn_tslots(C), TSTR = bn_tstride(C >> 3);
-  for (int c = threadIdx.x; c < C; c += NT) {
-    const float sb = kb[c], sg = kc[c];
-    if (bid == 0) {  // one writer: store (overwrite) or add (accumulate)
-      dbeta[c] = acc ? dbeta[c] + sb : sb;
-      dgamma[c] = acc ? dgamma[c] + sg : sg;
-    }
-    const float gm = gamma ? gamma[c] : 1.f;
-    const int tslot = (c & 7) * TSTR + (c >> 3);
-    tco[tslot] = gm * rstd[c];
-    tco[TS + tslot] = sb * invM;
-    tco[2 * TS + tslot] = sg * invM;
-    tco[3 * TS + tslot] = mean[c];
-    tco[4 * TS + tslot] = rstd[c];
-  }
+  bn_bwd_coefs(ops, kb, gamma, mean, rstd, dgamma, dbeta, M, C, acc, bid == 0, tco, TS,
+                   [TSTR](int c) { return (c & 7) * TSTR + (c >> 3); });
   __syncthreads();
   const int CH8 = C >> 3, j8 = i0 % CH8;
   float a8[8], b8[8], g8[8], m8[8], r8[8];
@@ -1089,6 +1185,8 @@ __global__ __launch_bounds__(NT) void k_bn_relu_maxpool(
   float* shift = sh + C;
   const long long M = (long long)B * H * W;
   const float* sums = stats;
+  FwdChan<NT> ops;
+  ops.issue(gamma, beta, run_mean, run_var, 0, blockIdx.x == 0, C);
   if (stats_rows > 0) {  // same row-summation order as k_bn_apply_v: bit-identical statistics
     float* acc = sh + 2 * C;
     if (C / 2 <= NT) {
@@ -1100,22 +1198,8 @@ __global__ __launch_bounds__(NT) void k_bn_relu_maxpool(
     }
     sums = acc;
   }
-  for (int c = threadIdx.x; c < C; c += NT) {
-    const float mean = sums[c] / (float)M;
-    const float var = fmaxf(sums[C + c] / (float)M - mean * mean, 0.f);
-    const float rstd = rsqrtf(var + eps);
-    const float g = gamma ? gamma[c] : 1.f, bb = beta ? beta[c] : 0.f;
-    scale[c] = g * rstd;
-    shift[c] = bb - mean * g * rstd;
-    if (blockIdx.x == 0) {
-      if (save_mean) { save_mean[c] = mean; save_rstd[c] = rstd; }
-      if (run_mean) {
-        const float unb = M > 1 ? var * (float)M / (float)(M - 1) : var;
-        run_mean[c] = (1.f - momentum) * run_mean[c] + momentum * mean;
-        run_var[c] = (1.f - momentum) * run_var[c] + momentum * unb;
-      }
-    }
-  }
+  bn_fwd_coefs<NT>(ops, sums, gamma, beta, save_mean, save_rstd, run_mean, run_var, M, C, eps, momentum, 0,
+                   blockIdx.x == 0, scale, shift, [](int c) { return c; });
   __syncthreads();
   const int CH = C / 8;
   const long long total = (long long)B * OH * OW * CH;
@@ -1182,6 +1266,8 @@ __global__ __launch_bounds__(NT) void k_bn_relu_maxpool3(
   const bool early = parts && C / 2 <= NT;
   EarlyRows er;
   if (early) er.issue(stats, stats_rows, 2 * C, NT);
+  FwdChan<NT> ops;
+  ops.issue(gamma, beta, run_mean, run_var, 0, blockIdx.x == 0, C);
   uint4 v[IPT][9];
   unsigned okm[IPT];
   auto load = [&](long long base) {
@@ -1215,22 +1301,8 @@ __global__ __launch_bounds__(NT) void k_bn_relu_maxpool3(
     else sum_partial_rows<NT>(stats, stats_rows, 2 * C, acc, reinterpret_cast<float4*>(sh + 4 * C));
     sums = acc;
   }
-  for (int c = threadIdx.x; c < C; c += NT) {
-    const float mean = sums[c] / (float)M;
-    const float var = fmaxf(sums[C + c] / (float)M - mean * mean, 0.f);
-    const float rstd = rsqrtf(var + eps);
-    const float g = gamma ? gamma[c] : 1.f, bb = beta ? beta[c] : 0.f;
-    scale[c] = g * rstd;
-    shift[c] = bb - mean * g * rstd;
-    if (blockIdx.x == 0) {
-      if (save_mean) { save_mean[c] = mean; save_rstd[c] = rstd; }
-      if (run_mean) {
-        const float unb = M > 1 ? var * (float)M / (float)(M - 1) : var;
-        run_mean[c] = (1.f - momentum) * run_mean[c] + momentum * mean;
-        run_var[c] = (1.f - momentum) * run_var[c] + momentum * unb;
-      }
-    }
-  }
+  bn_fwd_coefs<NT>(ops, sums, gamma, beta, save_mean, save_rstd, run_mean, run_var, M, C, eps, momentum, 0,
+                   blockIdx.x == 0, scale, shift, [](int c) { return c; });
   __syncthreads();
   for (long long base = i0, it = 0; base < total; base += IPT * T, ++it) {
     if (it > 0) load(base);

@@ -1540,11 +1540,28 @@ __device__ __forceinline__ void HaloBody<MODE, C, HW, IMG, BN, D>::run(const Con
   constexpr int BQ = 2 * C / 4, BS = 256 / BQ;   // float4 columns of a statistics row, row slices
   float4 brow_early[16];
   const bool bnin = MODE == FWD && a.ibn_rows != nullptr;
+  // ... and with them the per-channel vectors of the coefficient loop (channels tid, tid + 256, ...;
+  // cold: last written a step ago), so that loop only computes and stores; the running statistics
+  // only in the block that updates them
+  constexpr int BCI = (C + 255) / 256;
+  float bgam[BCI], bbet[BCI], brm[BCI], brv[BCI];
   if constexpr (MODE == FWD) {
     if (bnin && tid / BQ < BS) {
       const float4* p4 = reinterpret_cast<const float4*>(a.ibn_rows) + tid % BQ;
 #pragma unroll
       for (int uu = 0; uu < 16; ++uu) brow_early[uu] = p4[(long long)min(tid / BQ + uu * BS, a.ibn_G - 1) * BQ];
+    }
+#pragma unroll
+    for (int h = 0; h < BCI; ++h) { bgam[h] = 1.f; bbet[h] = 0.f; brm[h] = 0.f; brv[h] = 0.f; }
+    if (bnin) {
+      const bool upd = bk.x == 0 && bk.y == 0 && a.ibn_rmean != nullptr;
+#pragma unroll
+      for (int h = 0; h < BCI; ++h) {
+        const int c = min(tid + h * 256, C - 1);   // clamped (valid) index past C, never used
+        if (a.ibn_gamma) bgam[h] = a.ibn_gamma[c];
+        if (a.ibn_beta) bbet[h] = a.ibn_beta[c];
+        if (upd) { brm[h] = a.ibn_rmean[c]; brv[h] = a.ibn_rvar[c]; }
+      }
     }
   }
 
@@ -1668,19 +1685,22 @@ __device__ __forceinline__ void HaloBody<MODE, C, HW, IMG, BN, D>::run(const Con
         reinterpret_cast<float4*>(sums)[tid] = t4;
       }
       __syncthreads();
-      for (int c = tid; c < C; c += 256) {
+#pragma unroll
+      for (int h = 0; h < BCI; ++h) {
+        const int c = tid + h * 256;
+        if (c >= C) break;
         const float mean = sums[c] / (float)a.ibn_M;
         const float var = fmaxf(sums[C + c] / (float)a.ibn_M - mean * mean, 0.f);
         const float rstd = rsqrtf(var + a.ibn_eps);
-        const float g = a.ibn_gamma ? a.ibn_gamma[c] : 1.f, bb = a.ibn_beta ? a.ibn_beta[c] : 0.f;
+        const float g = bgam[h], bb = bbet[h];
         bsc[c] = g * rstd;
         bsf[c] = bb - mean * g * rstd;
         if (bk.x == 0 && bk.y == 0) {
           if (a.ibn_mean) { a.ibn_mean[c] = mean; a.ibn_rstd[c] = rstd; }
           if (a.ibn_rmean) {
             const float unb = a.ibn_M > 1 ? var * (float)a.ibn_M / (float)(a.ibn_M - 1) : var;
-            a.ibn_rmean[c] = (1.f - a.ibn_mom) * a.ibn_rmean[c] + a.ibn_mom * mean;
-            a.ibn_rvar[c] = (1.f - a.ibn_mom) * a.ibn_rvar[c] + a.ibn_mom * unb;
+            a.ibn_rmean[c] = (1.f - a.ibn_mom) * brm[h] + a.ibn_mom * mean;
+            a.ibn_rvar[c] = (1.f - a.ibn_mom) * brv[h] + a.ibn_mom * unb;
           }
         }
       }
