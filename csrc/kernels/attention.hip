@@ -66,6 +66,7 @@ struct AttnArgs {
   float pdrop;         // dropout probability (0: off)
   int xcd;             // XCD-aware block order (attn_blk); 0: plain grid order (A/B switch)
   unsigned char* keep; // dropout keep bits written by the forward, read by the backward (Drop), or null
+  int G;               // grouped-query attention: query heads per K/V head (H = Hkv * G); 1: one K/V head each
 };
 
 __device__ __forceinline__ unsigned ahash(unsigned a, unsigned b, unsigned c) {
@@ -140,14 +141,28 @@ __device__ __forceinline__ int swz(int r, int c) { return r * 128 + ((c ^ (r & 7
 // one), so with the plain (tile, b*h) grid the 8 tiles of one head land on 8 different L2s
 // and each XCD fetches that head's K/V (or Q/dO) again.  Renumbered so each XCD runs a
 // contiguous range of ids, tile fastest: the tiles of one head share one L2.
+//
+// GROUP (grouped-query forward / dQ, grid.y = B * H): the G query heads of a K/V head read the
+// same K/V tiles.  Their ids stay inside one XCD's contiguous range (bh = kvbh * G + hg), and
+// within the group the head runs fastest and the tile next: id = (kvbh * gx + xt) * G + hg, so the
+// G blocks of one (K/V head, tile) are dispatched back to back on that XCD and walk the same K/V
+// lines of its L2 together (causal: they also carry the same amount of work).
+template <bool GROUP = false>
 __device__ __forceinline__ void attn_blk(const AttnArgs& a, int& xt, int& bh) {
   const int gx = (int)gridDim.x, nwg = gx * (int)gridDim.y;
   const int lin = (int)blockIdx.y * gx + (int)blockIdx.x;
   if (!a.xcd) { xt = (int)blockIdx.x; bh = (int)blockIdx.y; return; }
   const int q = nwg >> 3, r = nwg & 7, x = lin & 7, k = lin >> 3;
   const int id = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + k;
-  bh = id / gx;
-  xt = id - bh * gx;
+  if constexpr (GROUP) {
+    const int t = id / a.G, hg = id - t * a.G;
+    const int kvbh = t / gx;
+    xt = t - kvbh * gx;
+    bh = kvbh * a.G + hg;
+  } else {
+    bh = id / gx;
+    xt = id - bh * gx;
+  }
 }
 
 struct TileRegs { uint4 v[2]; };
@@ -219,8 +234,10 @@ __device__ __forceinline__ void store4(bf16_t* p, const f32x4_t& v, float s) {
 // register trade of each kernel was measured, profiles/bert_base_r3.md)
 // DM: dropout mode (0 none, 1 hashed keep decisions, stored as bits when a.keep is set), BIAS:
 // additive key bias — compile-time like the backward kernels
-template <int OCC, int DM, bool BIAS, bool CAUSAL>
-__global__ __launch_bounds__(256, OCC) void k_attn_fwd(AttnArgs a) {
+// GQA: the block of query head h reads K / V at column 64 (h / G); everything else, the dropout
+// hash (keyed by the query bh) and the LSE rows included, is per query head as with G = 1
+template <int DM, bool BIAS, bool CAUSAL, bool GQA>
+__device__ __forceinline__ void attn_fwd_body(const AttnArgs& a) {
   // K/V double-buffered (40 KB: 4 blocks per CU, the VGPR occupancy): one barrier per key
   // tile, and the register-staged next tile is stored after this tile's MFMAs, a whole tile
   // after its global loads were issued
@@ -229,12 +246,13 @@ __global__ __launch_bounds__(256, OCC) void k_attn_fwd(AttnArgs a) {
   __shared__ __attribute__((aligned(16))) char sV2[2][8192];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, g = lane >> 4;
   int xt, bh;
-  attn_blk(a, xt, bh);
+  attn_blk<GQA>(a, xt, bh);
   const int b = bh / a.H, h = bh - b * a.H;
+  const int hk = GQA ? h / a.G : h;   // K/V head
   const int L = a.L, q0 = xt * 64;
   const bf16_t* Qb = a.q + (long long)b * L * a.ldq + h * 64;
-  const bf16_t* Kb = a.k + (long long)b * L * a.ldk + h * 64;
-  const bf16_t* Vb = a.v + (long long)b * L * a.ldv + h * 64;
+  const bf16_t* Kb = a.k + (long long)b * L * a.ldk + hk * 64;
+  const bf16_t* Vb = a.v + (long long)b * L * a.ldv + hk * 64;
   const float sl2 = a.scale * LOG2E;
   const float* bias = BIAS ? a.bias + (long long)b * L : nullptr;
   Drop drop;
@@ -362,23 +380,33 @@ __global__ __launch_bounds__(256, OCC) void k_attn_fwd(AttnArgs a) {
   }
 }
 
+template <int OCC, int DM, bool BIAS, bool CAUSAL>
+__global__ __launch_bounds__(256, OCC) void k_attn_fwd(AttnArgs a) {
+  attn_fwd_body<DM, BIAS, CAUSAL, false>(a);
+}
+template <int OCC, int DM, bool BIAS, bool CAUSAL>
+__global__ __launch_bounds__(256, OCC) void k_attn_gqa_fwd(AttnArgs a) {
+  attn_fwd_body<DM, BIAS, CAUSAL, true>(a);
+}
+
 // ------------------------------------------------------------------------------ backward: dQ (+D)
 // DM: dropout mode (0 none, 1 the forward's keep bits, 2 re-hashed), BIAS: additive key bias —
 // compile-time, so the per-probability code carries no uniform branches (a branch per element
 // was a scheduling barrier between the VALU work and the MFMAs around it)
-template <int OCC, int DM, bool BIAS, bool CAUSAL>
-__global__ __launch_bounds__(256, OCC) void k_attn_bwd_dq(AttnArgs a) {
+template <int DM, bool BIAS, bool CAUSAL, bool GQA>
+__device__ __forceinline__ void attn_bwd_dq_body(const AttnArgs& a) {
   __shared__ __attribute__((aligned(16))) char sK2[2][8192];   // K/V double-buffered (k_attn_fwd)
   __shared__ __attribute__((aligned(16))) char sV2[2][8192];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, g = lane >> 4;
   int xt, bh;
-  attn_blk(a, xt, bh);
+  attn_blk<GQA>(a, xt, bh);
   const int b = bh / a.H, h = bh - b * a.H;
+  const int hk = GQA ? h / a.G : h;   // K/V head
   const int L = a.L;
   const int q = xt * 64 + 16 * w + (lane & 15);
   const bool qok = q < L;
-  const bf16_t* Kb = a.k + (long long)b * L * a.ldk + h * 64;
-  const bf16_t* Vb = a.v + (long long)b * L * a.ldv + h * 64;
+  const bf16_t* Kb = a.k + (long long)b * L * a.ldk + hk * 64;
+  const bf16_t* Vb = a.v + (long long)b * L * a.ldv + hk * 64;
   const float sl2 = a.scale * LOG2E;
   const float* bias = BIAS ? a.bias + (long long)b * L : nullptr;
 
@@ -489,11 +517,29 @@ __global__ __launch_bounds__(256, OCC) void k_attn_bwd_dq(AttnArgs a) {
   }
 }
 
+template <int OCC, int DM, bool BIAS, bool CAUSAL>
+__global__ __launch_bounds__(256, OCC) void k_attn_bwd_dq(AttnArgs a) {
+  attn_bwd_dq_body<DM, BIAS, CAUSAL, false>(a);
+}
+template <int OCC, int DM, bool BIAS, bool CAUSAL>
+__global__ __launch_bounds__(256, OCC) void k_attn_gqa_bwd_dq(AttnArgs a) {
+  attn_bwd_dq_body<DM, BIAS, CAUSAL, true>(a);
+}
+
 // ------------------------------------------------------------------------------ backward: dK, dV
 // DM / BIAS as k_attn_bwd_dq.  Without a bias the keys past L keep a zero bias: their dK / dV
 // rows are never stored and no other key's rows read them.
-template <int OCC, int DM, bool BIAS, bool CAUSAL>
-__global__ __launch_bounds__(256, OCC) void k_attn_bwd_dkv(AttnArgs a) {
+//
+// GQA (grid.y = B * Hkv): one block per (key tile, b, K/V head).  K and V fragments are loaded
+// once; the block walks the G query heads of its group in ascending head order and, within a
+// head, the query tiles a G = 1 block walks (causal: from the diagonal tile).  The walk is one
+// flat sequence of (head, query tile) steps, so the Q / dO / LSE / D / keep-bit double buffer
+// simply runs on: the first tile of head h + 1 is requested during the last tile of head h.
+// Every head accumulates into the same fp32 dK / dV MFMA accumulators, rounded to bf16 once at
+// the end — no atomics, no partial buffers, a fixed summation order (bit-reproducible).  With
+// G = 1 the sequence is the query-tile loop of before, step for step.
+template <int DM, bool BIAS, bool CAUSAL, bool GQA>
+__device__ __forceinline__ void attn_bwd_dkv_body(const AttnArgs& a) {
   // double-buffered like k_attn_fwd: Q, dO, LSE, D and the keep bits of a query tile
   __shared__ __attribute__((aligned(16))) char sQ2[2][8192];
   __shared__ __attribute__((aligned(16))) char sO2[2][8192];  // dO tile
@@ -503,22 +549,25 @@ __global__ __launch_bounds__(256, OCC) void k_attn_bwd_dkv(AttnArgs a) {
   // lane's four queries 16t + 4g + i are one ds_read_b128 (like LSE and D)
   __shared__ __attribute__((aligned(16))) unsigned sM2[2][2][64];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, g = lane >> 4;
-  int xt, bh;
-  attn_blk(a, xt, bh);
-  const int b = bh / a.H, h = bh - b * a.H;
+  int xt, bkv;   // bkv: b * Hkv + K/V head (G = 1: the query bh)
+  attn_blk(a, xt, bkv);
+  const int G = GQA ? a.G : 1;
+  const int Hkv = GQA ? a.H / G : a.H;
+  const int b = bkv / Hkv, hk = bkv - b * Hkv;
+  const int bh0 = GQA ? b * a.H + hk * G : bkv;   // query bh of the group's first head
   const int L = a.L;
   const int key = xt * 64 + 16 * w + (lane & 15);
   const bool kok = key < L;
-  const bf16_t* Qb = a.q + (long long)b * L * a.ldq + h * 64;
-  const bf16_t* Ob = a.dout + (long long)b * L * a.lddo + h * 64;
+  const bf16_t* Qb = a.q + (long long)b * L * a.ldq + (bh0 - b * a.H) * 64;
+  const bf16_t* Ob = a.dout + (long long)b * L * a.lddo + (bh0 - b * a.H) * 64;
   const float sl2 = a.scale * LOG2E;
-  const bf16_t* krow = a.k + (long long)(b * L + (kok ? key : 0)) * a.ldk + h * 64;
-  const bf16_t* vrow = a.v + (long long)(b * L + (kok ? key : 0)) * a.ldv + h * 64;
+  const bf16_t* krow = a.k + (long long)(b * L + (kok ? key : 0)) * a.ldk + hk * 64;
+  const bf16_t* vrow = a.v + (long long)(b * L + (kok ? key : 0)) * a.ldv + hk * 64;
   const bf16x8_t kf0 = load_frag_g(krow, 0, g, kok), kf1 = load_frag_g(krow, 1, g, kok);
   const bf16x8_t vf0 = load_frag_g(vrow, 0, g, kok), vf1 = load_frag_g(vrow, 1, g, kok);
   const float kb2 = BIAS ? (!kok ? -INFINITY : a.bias[(long long)b * L + key] * LOG2E) : 0.f;
   Drop drop;
-  drop.init(a, bh);
+  drop.init(a, bh0);
 
   f32x4_t adk[4], adv[4];
 #pragma unroll
@@ -527,21 +576,29 @@ __global__ __launch_bounds__(256, OCC) void k_attn_bwd_dkv(AttnArgs a) {
   // stored keep bits (Drop): the 512-byte tile of words (q = qb*64.., this key tile) is
   // staged in LDS; this lane's key sits at bit kbit of each word
   constexpr bool kbits = DM == 1;
-  const uint4* kw = reinterpret_cast<const uint4*>(a.keep + ((long long)bh * nqb + xt) * (nqb * 64) * 8);
   const int kl = 16 * w + (lane & 15), kbit = 16 * ((kl >> 2) & 3) + 4 * (kl >> 4) + (kl & 3);
   TileRegs rq, ro;
   float pl = 0.f, pd = 0.f;
   uint4 mnext = make_uint4(0, 0, 0, 0);
-  auto fetch = [&](int qbn) {
-    const int nq0 = qbn * 64;
-    tile_load(rq, Qb, a.ldq, nq0, L, tid);
-    tile_load(ro, Ob, a.lddo, nq0, L, tid);
+  // causal: query tiles xt .. nqb-1 (earlier queries never see this key tile)
+  const int qs = CAUSAL ? xt : 0;
+  // the walk: step it = (head in group fh, query tile fq), tile fastest; fetch() requests the
+  // next step's operands and moves on, across the head boundary too
+  const int nit = GQA ? G * (nqb - qs) : nqb - qs;
+  int fh = 0, fq = qs;
+  auto fetch = [&]() {
+    const int nq0 = fq * 64, bh = bh0 + fh;
+    tile_load(rq, Qb + fh * 64, a.ldq, nq0, L, tid);
+    tile_load(ro, Ob + fh * 64, a.lddo, nq0, L, tid);
     if (tid < 64) {
       const int qq = nq0 + tid;
       pl = qq < L ? a.lse[(long long)bh * L + qq] : INFINITY;
       pd = qq < L ? a.dsum[(long long)bh * L + qq] : 0.f;
     }
-    if (kbits && tid < 32) mnext = kw[qbn * 32 + tid];
+    if (kbits && tid < 32)
+      mnext = reinterpret_cast<const uint4*>(a.keep + ((long long)bh * nqb + xt) * (nqb * 64) * 8)[fq * 32 + tid];
+    ++fq;
+    if (GQA && fq == nqb) { fq = qs; ++fh; }
   };
   auto stage = [&](int j) {
     tile_store(sQ2[j], rq, tid);
@@ -552,15 +609,16 @@ __global__ __launch_bounds__(256, OCC) void k_attn_bwd_dkv(AttnArgs a) {
       *reinterpret_cast<uint2*>(&sM2[j][1][2 * tid]) = make_uint2(mnext.y, mnext.w);
     }
   };
-  // causal: query tiles xt .. nqb-1 (earlier queries never see this key tile); the double
-  // buffer alternates from the first visited tile
-  const int qs = CAUSAL ? xt : 0;
-  fetch(qs);
+  // the double buffer alternates from the first visited step
+  fetch();
   stage(0);
-  if (qs + 1 < nqb) fetch(qs + 1);
+  if (1 < nit) fetch();
   __syncthreads();
-  for (int qb = qs; qb < nqb; ++qb) {
-    const int cur = CAUSAL ? (qb - qs) & 1 : qb & 1;
+  int hg = 0, qb = qs;   // this step's head in the group and query tile
+  for (int it = 0; it < nit; ++it) {
+    const int cur = it & 1;
+    // re-hashed dropout is keyed by the query bh: a new head, a new key
+    if (GQA && DM == 2 && qb == qs) drop.init(a, bh0 + hg);
     // causal diagonal tile: queries 16t + i < lim come before this lane's key (masked)
     const int lim = CAUSAL && qb == xt ? kl - 4 * g : 0;
     const char* sQ = sQ2[cur];
@@ -613,21 +671,32 @@ __global__ __launch_bounds__(256, OCC) void k_attn_bwd_dkv(AttnArgs a) {
       adk[d] = MFMA16(frag_tr(sQ, 16 * d, 0, lane), d0, adk[d]);
       adk[d] = MFMA16(frag_tr(sQ, 16 * d, 1, lane), d1, adk[d]);
     }
-    if (qb + 1 < nqb) {   // buffer cur^1 last held tile qb-1: every wave left it at the last barrier
-      stage(CAUSAL ? cur ^ 1 : (qb + 1) & 1);
-      if (qb + 2 < nqb) fetch(qb + 2);
+    if (it + 1 < nit) {   // buffer cur^1 last held step it-1: every wave left it at the last barrier
+      stage(cur ^ 1);
+      if (it + 2 < nit) fetch();
       __syncthreads();
     }
+    ++qb;
+    if (GQA && qb == nqb) { qb = qs; ++hg; }
   }
   if (kok) {
-    bf16_t* kp = a.dk + (long long)(b * L + key) * a.lddk + h * 64;
-    bf16_t* vp = a.dv + (long long)(b * L + key) * a.lddv + h * 64;
+    bf16_t* kp = a.dk + (long long)(b * L + key) * a.lddk + hk * 64;
+    bf16_t* vp = a.dv + (long long)(b * L + key) * a.lddv + hk * 64;
 #pragma unroll
     for (int d = 0; d < 4; ++d) {
       store4(kp + 16 * d + 4 * g, adk[d], a.scale);
       store4(vp + 16 * d + 4 * g, adv[d], drop.sc);
     }
   }
+}
+
+template <int OCC, int DM, bool BIAS, bool CAUSAL>
+__global__ __launch_bounds__(256, OCC) void k_attn_bwd_dkv(AttnArgs a) {
+  attn_bwd_dkv_body<DM, BIAS, CAUSAL, false>(a);
+}
+template <int OCC, int DM, bool BIAS, bool CAUSAL>
+__global__ __launch_bounds__(256, OCC) void k_attn_gqa_bwd_dkv(AttnArgs a) {
+  attn_bwd_dkv_body<DM, BIAS, CAUSAL, true>(a);
 }
 
 bool aligned16(const void* p) { return (((unsigned long long)p) & 15ull) == 0; }
@@ -637,38 +706,45 @@ bool aligned16(const void* p) { return (((unsigned long long)p) & 15ull) == 0; }
 // q/k/v/out: token-major [B*L, ld*] bf16, head h at column 64h (head_dim must be 64)
 // ctr/salt/pdrop: attention-probability dropout (ctr null or pdrop 0: none); keep: null or a
 // [B*H, nkb, 64*nkb] u64 buffer (nkb = ceil(L/64)) that receives the keep bits (Drop)
-template <bool CAUSAL>
+// GQA (G = H / Hkv > 1 query heads per K/V head): k / v hold Hkv heads; G = 1 is the kernels of before
+template <bool CAUSAL, bool GQA = false>
 static int attn_fwd_launch(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* out, float* lse,
                            const float* bias, int ldq, int ldk, int ldv, int ldout, int B, int H, int L, float scale,
-                           const float* ctr, int salt, float pdrop, unsigned char* keep, hipStream_t s) {
+                           const float* ctr, int salt, float pdrop, unsigned char* keep, hipStream_t s, int G = 1) {
   if (L <= 0 || B <= 0 || H <= 0 || ldq % 8 || ldk % 8 || ldv % 8 || ldout % 4) return (int)hipErrorInvalidValue;
   if (!aligned16(q) || !aligned16(k) || !aligned16(v)) return (int)hipErrorInvalidValue;
   AttnArgs a{};
   a.q = q; a.k = k; a.v = v; a.out = out; a.lse = lse; a.bias = bias;
   a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldout = ldout;
   a.B = B; a.H = H; a.L = L; a.scale = scale;
-  a.ctr = ctr; a.salt = (unsigned)salt; a.pdrop = pdrop; a.xcd = 1; a.keep = keep;
+  a.ctr = ctr; a.salt = (unsigned)salt; a.pdrop = pdrop; a.xcd = 1; a.keep = keep; a.G = G;
   if (pdrop < 0.f || pdrop >= 1.f) return (int)hipErrorInvalidValue;
   const dim3 grid((L + 63) / 64, B * H);
   const bool dm = ctr != nullptr && pdrop > 0.f;
+#define KML_ATTN_FWD(DM, BI)                                                                        \
+  do {                                                                                              \
+    if constexpr (GQA) hipLaunchKernelGGL((k_attn_gqa_fwd<4, DM, BI, CAUSAL>), grid, dim3(256), 0, s, a); \
+    else hipLaunchKernelGGL((k_attn_fwd<4, DM, BI, CAUSAL>), grid, dim3(256), 0, s, a);             \
+  } while (0)
   if (bias) {
-    if (dm) hipLaunchKernelGGL((k_attn_fwd<4, 1, true, CAUSAL>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((k_attn_fwd<4, 0, true, CAUSAL>), grid, dim3(256), 0, s, a);
+    if (dm) KML_ATTN_FWD(1, true);
+    else KML_ATTN_FWD(0, true);
   } else {
-    if (dm) hipLaunchKernelGGL((k_attn_fwd<4, 1, false, CAUSAL>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((k_attn_fwd<4, 0, false, CAUSAL>), grid, dim3(256), 0, s, a);
+    if (dm) KML_ATTN_FWD(1, false);
+    else KML_ATTN_FWD(0, false);
   }
+#undef KML_ATTN_FWD
   KML_LAUNCH_CHECK();
 }
 
 // dq/dk/dv may point into one fused [B*L, 3*H*64] buffer (ld = 3*H*64); dsum: [B*H*L] fp32 scratch;
 // keep: the forward's keep bits (read instead of re-hashing), or null
-template <bool CAUSAL>
+template <bool CAUSAL, bool GQA = false>
 static int attn_bwd_launch(const bf16_t* q, const bf16_t* k, const bf16_t* v, const bf16_t* o, const bf16_t* dout,
                            const float* lse, float* dsum, const float* bias, bf16_t* dq, bf16_t* dk, bf16_t* dv,
                            int ldq, int ldk, int ldv, int ldo, int lddo, int lddq, int lddk, int lddv, int B, int H,
                            int L, float scale, const float* ctr, int salt, float pdrop, const unsigned char* keep,
-                           hipStream_t s) {
+                           hipStream_t s, int G = 1) {
   if (L <= 0 || ldq % 8 || ldk % 8 || ldv % 8 || ldo % 8 || lddo % 8 || lddq % 4 || lddk % 4 || lddv % 4)
     return (int)hipErrorInvalidValue;
   AttnArgs a{};
@@ -678,8 +754,10 @@ static int attn_bwd_launch(const bf16_t* q, const bf16_t* k, const bf16_t* v, co
   a.B = B; a.H = H; a.L = L; a.scale = scale;
   a.ctr = ctr; a.salt = (unsigned)salt; a.pdrop = pdrop; a.xcd = 1;
   a.keep = const_cast<unsigned char*>(keep);
+  a.G = G;
   if (pdrop < 0.f || pdrop >= 1.f) return (int)hipErrorInvalidValue;
   const dim3 grid((L + 63) / 64, B * H);
+  const dim3 grid_kv((L + 63) / 64, B * (H / G));   // dKV: one block per (key tile, b, K/V head)
   // occupancy from the register budgets (profiles/bert_base_r3.md): dQ at 4 waves per SIMD
   // (124 VGPRs, no spills), dKV at 2 (~211 VGPRs; 3 spills and doubles its time)
   const int dm = (ctr == nullptr || pdrop <= 0.f) ? 0 : (keep != nullptr ? 1 : 2);
@@ -688,9 +766,14 @@ static int attn_bwd_launch(const bf16_t* q, const bf16_t* k, const bf16_t* v, co
   // less, so that no causal instantiation spills (profiles/r11/causal_attention.md)
 #define KML_ATTN_BWD(DM, BI)                                                                             \
   do {                                                                                                   \
-    hipLaunchKernelGGL((k_attn_bwd_dq<(CAUSAL && DM == 2) ? 3 : 4, DM, BI, CAUSAL>), grid, dim3(256), 0, s, a); \
-    hipLaunchKernelGGL((k_attn_bwd_dkv<(CAUSAL && DM == 2) ? DKV_OCC - 1 : DKV_OCC, DM, BI, CAUSAL>), grid,  \
-                       dim3(256), 0, s, a);                                                              \
+    constexpr int QO = (CAUSAL && DM == 2) ? 3 : 4, KO = (CAUSAL && DM == 2) ? DKV_OCC - 1 : DKV_OCC;      \
+    if constexpr (GQA) {                                                                                 \
+      hipLaunchKernelGGL((k_attn_gqa_bwd_dq<QO, DM, BI, CAUSAL>), grid, dim3(256), 0, s, a);             \
+      hipLaunchKernelGGL((k_attn_gqa_bwd_dkv<KO, DM, BI, CAUSAL>), grid_kv, dim3(256), 0, s, a);         \
+    } else {                                                                                             \
+      hipLaunchKernelGGL((k_attn_bwd_dq<QO, DM, BI, CAUSAL>), grid, dim3(256), 0, s, a);                 \
+      hipLaunchKernelGGL((k_attn_bwd_dkv<KO, DM, BI, CAUSAL>), grid_kv, dim3(256), 0, s, a);             \
+    }                                                                                                    \
   } while (0)
   if (bias) {
     if (dm == 0) KML_ATTN_BWD(0, true);
@@ -737,4 +820,36 @@ KML_API int kml_attn_causal_bwd(const bf16_t* q, const bf16_t* k, const bf16_t* 
                                 float pdrop, const unsigned char* keep, hipStream_t s) {
   return attn_bwd_launch<true>(q, k, v, o, dout, lse, dsum, bias, dq, dk, dv, ldq, ldk, ldv, ldo, lddo, lddq, lddk,
                                lddv, B, H, L, scale, ctr, salt, pdrop, keep, s);
+}
+
+// grouped-query attention: q holds H heads, k / v hold Hkv heads (H % Hkv == 0), query head h
+// reads K/V head h / (H / Hkv).  lse / dsum rows and the keep bits are per query head, as above;
+// dk / dv have Hkv * 64 columns (each the sum over its group's query heads, accumulated in fp32
+// in a fixed order).  Hkv == H runs the kernels of kml_attn_fwd / kml_attn_causal_fwd themselves.
+KML_API int kml_attn_gqa_fwd(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* out, float* lse,
+                             const float* bias, int ldq, int ldk, int ldv, int ldout, int B, int H, int Hkv, int L,
+                             float scale, const float* ctr, int salt, float pdrop, unsigned char* keep, int causal,
+                             hipStream_t s) {
+  if (H <= 0 || Hkv <= 0 || H % Hkv) return (int)hipErrorInvalidValue;
+  const int G = H / Hkv;
+#define KML_GQA_FWD(C, Q) \
+  attn_fwd_launch<C, Q>(q, k, v, out, lse, bias, ldq, ldk, ldv, ldout, B, H, L, scale, ctr, salt, pdrop, keep, s, G)
+  if (G == 1) return causal ? KML_GQA_FWD(true, false) : KML_GQA_FWD(false, false);
+  return causal ? KML_GQA_FWD(true, true) : KML_GQA_FWD(false, true);
+#undef KML_GQA_FWD
+}
+
+KML_API int kml_attn_gqa_bwd(const bf16_t* q, const bf16_t* k, const bf16_t* v, const bf16_t* o, const bf16_t* dout,
+                             const float* lse, float* dsum, const float* bias, bf16_t* dq, bf16_t* dk, bf16_t* dv,
+                             int ldq, int ldk, int ldv, int ldo, int lddo, int lddq, int lddk, int lddv, int B, int H,
+                             int Hkv, int L, float scale, const float* ctr, int salt, float pdrop,
+                             const unsigned char* keep, int causal, hipStream_t s) {
+  if (B <= 0 || H <= 0 || Hkv <= 0 || H % Hkv) return (int)hipErrorInvalidValue;
+  const int G = H / Hkv;
+#define KML_GQA_BWD(C, Q)                                                                                        \
+  attn_bwd_launch<C, Q>(q, k, v, o, dout, lse, dsum, bias, dq, dk, dv, ldq, ldk, ldv, ldo, lddo, lddq, lddk, lddv, B, \
+                        H, L, scale, ctr, salt, pdrop, keep, s, G)
+  if (G == 1) return causal ? KML_GQA_BWD(true, false) : KML_GQA_BWD(false, false);
+  return causal ? KML_GQA_BWD(true, true) : KML_GQA_BWD(false, true);
+#undef KML_GQA_BWD
 }

@@ -7,6 +7,7 @@ Workloads shipped by the reference and the north-star configs:
   resnet50    ResNet-50 / ImageNet-shape (north-star config 3)
   vgg16       VGG-16-BN / CIFAR-100     (north-star config 4; function_vgg11.py family)
   bert_base   BERT-base MLM             (north-star config 5)
+  gpt2, llama decoder LMs: models/gpt.py (GPT2LMHeadModel), models/llama.py (LlamaForCausalLM)
 """
 from __future__ import annotations
 
@@ -28,4 +29,14 @@ def get_model(name: str, **kw):
     if name in ("bert_base", "bert"):
         from .bert import bert_base_mlm
         return bert_base_mlm(**kw)
+    if name in ("llama", "llama_tiny"):
+        from . import llama
+        return llama.llama_tiny(**kw) if name == "llama_tiny" else llama.LlamaForCausalLM(**kw)
     raise KeyError(f"unknown model {name!r}")
+
+
+def __getattr__(name):
+    if name in ("LlamaForCausalLM", "llama_tiny"):
+        from . import llama
+        return getattr(llama, name)
+    raise AttributeError(name)

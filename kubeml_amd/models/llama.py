@@ -1,0 +1,269 @@
+"""Llama-style decoder-only language model (HuggingFace ``LlamaForCausalLM`` architecture and
+``state_dict`` names: ``model.embed_tokens.weight``, ``model.layers.{i}.self_attn.q_proj.weight``,
+..., ``lm_head.weight``) on the MI355X layers, head dim 64:
+
+* RMSNorm with the pre-norm residual stream carried inside its launches — a chain of
+  :meth:`RMSNorm.add_norm`, as ``GPT2Model`` chains ``LayerNorm.add_norm`` (csrc/kernels/llama.hip);
+* one fused ``qkv`` projection ``[(H + 2 Hkv) * 64, hidden]`` without bias (head dim 64, whatever
+  ``hidden / heads`` is), rotary position embedding in place on its output (``kml_rope``),
+  grouped-query causal flash attention (``kml_attn_gqa_fwd / _bwd``: ``Hkv`` K/V heads shared by
+  groups of ``H / Hkv`` query heads);
+* gated SiLU MLP: one fused ``gate_up`` projection ``[2 I, hidden]``, ``kml_swiglu_fwd / _bwd``,
+  ``down_proj``;
+* one token table (no position table), optionally tied to ``lm_head``; shifted labels and the
+  fused cross entropy as in ``GPT2LMHeadModel``.
+
+``state_dict`` / ``load_state_dict`` split and concatenate the fused ``qkv`` / ``gate_up``
+parameters, so HF checkpoints of the family load directly.  Build from a checkpoint's
+``config.json`` with :meth:`LlamaForCausalLM.from_hf_config`.  Training only: there is no
+``generate`` (the decode kernels need RoPE at the cache position and an ``Hkv``-head cache).
+"""
+from __future__ import annotations
+
+import json
+import os
+
+import torch
+import torch.nn as tnn
+from torch.autograd import Function
+
+from ..nn.flat import grad_storage_of, shadow_of
+from ..nn.modules import Linear, cross_entropy
+from ..nn.transformer import RMSNorm, _AttnFn, _bf, attention_reference, rope, rope_table, swiglu
+
+
+class _TokEmbFn(Function):
+    """Token embedding: the row-gather kernel; backward = the word-table scatter-add."""
+
+    @staticmethod
+    def forward(ctx, ids, wte, L):
+        from ..ops import transformer as T
+        ctx.save = (ids, wte)
+        ctx.L = L
+        return T.gather_rows(shadow_of(wte), ids)
+
+    @staticmethod
+    def backward(ctx, dsum):
+        from ..ops import transformer as T
+        ids, wte = ctx.save
+        T.embed_bwd(ids, None, _bf(dsum).contiguous(), grad_storage_of(wte), None, None, ctx.L)
+        ctx.save = None
+        return None, None, None
+
+
+class LlamaAttention(tnn.Module):
+    """Fused ``qkv`` Linear (rows: H query heads | Hkv key heads | Hkv value heads) + RoPE +
+    grouped-query causal attention + ``o_proj``; HF's ``q_proj`` / ``k_proj`` / ``v_proj`` through
+    the state-dict hooks."""
+
+    def __init__(self, hidden, heads, kv_heads):
+        super().__init__()
+        if kv_heads < 1 or heads % kv_heads:
+            raise ValueError(f"kv_heads {kv_heads} must divide heads {heads}")
+        self.hidden, self.heads, self.kv_heads = hidden, heads, kv_heads
+        self.qkv = Linear(hidden, (heads + 2 * kv_heads) * 64, bias=False)
+        self.o_proj = Linear(heads * 64, hidden, bias=False)   # head dim is 64 whatever hidden / heads is
+        self._register_state_dict_hook(LlamaAttention._sd_hook)
+        self._register_load_state_dict_pre_hook(LlamaAttention._load_hook, with_module=True)
+
+    @staticmethod
+    def _sd_hook(mod, sd, prefix, local_metadata):
+        w = sd.pop(prefix + "qkv.weight")
+        D, E = mod.heads * 64, mod.kv_heads * 64
+        sd[prefix + "q_proj.weight"], sd[prefix + "k_proj.weight"], sd[prefix + "v_proj.weight"] = \
+            w[:D], w[D:D + E], w[D + E:]
+        sd[prefix + "o_proj.weight"] = sd.pop(prefix + "o_proj.weight")   # HF order: q, k, v, o
+        return sd
+
+    @staticmethod
+    def _load_hook(mod, sd, prefix, local_metadata, strict, missing, unexpected, errors):
+        names = [prefix + n + "_proj.weight" for n in ("q", "k", "v")]
+        if all(n in sd for n in names):
+            sd[prefix + "qkv.weight"] = torch.cat([sd.pop(n) for n in names], 0)
+
+    def forward(self, x, B, L, table, bias=None):
+        H, Hkv = self.heads, self.kv_heads
+        qkv = rope(self.qkv(x), table, L, H, Hkv)
+        if not x.is_cuda:
+            ctx = attention_reference(qkv, B, H, L, bias, causal=True, kv_heads=Hkv)
+        else:
+            ctx = _AttnFn.apply(qkv, B, H, L, bias, None, True, Hkv)
+        return self.o_proj(ctx)
+
+
+class LlamaMLP(tnn.Module):
+    """``down_proj(silu(gate_proj(x)) * up_proj(x))`` with gate and up as one ``gate_up`` Linear
+    (gate rows first); HF's ``gate_proj`` / ``up_proj`` through the state-dict hooks."""
+
+    def __init__(self, hidden, inter):
+        super().__init__()
+        if inter % 8:
+            raise ValueError("the SwiGLU kernel needs inter % 8 == 0")
+        self.inter = inter
+        self.gate_up = Linear(hidden, 2 * inter, bias=False)
+        self.down_proj = Linear(inter, hidden, bias=False)
+        self._register_state_dict_hook(LlamaMLP._sd_hook)
+        self._register_load_state_dict_pre_hook(LlamaMLP._load_hook, with_module=True)
+
+    @staticmethod
+    def _sd_hook(mod, sd, prefix, local_metadata):
+        w = sd.pop(prefix + "gate_up.weight")
+        sd[prefix + "gate_proj.weight"], sd[prefix + "up_proj.weight"] = w[:mod.inter], w[mod.inter:]
+        sd[prefix + "down_proj.weight"] = sd.pop(prefix + "down_proj.weight")   # HF order: gate, up, down
+        return sd
+
+    @staticmethod
+    def _load_hook(mod, sd, prefix, local_metadata, strict, missing, unexpected, errors):
+        names = [prefix + n + "_proj.weight" for n in ("gate", "up")]
+        if all(n in sd for n in names):
+            sd[prefix + "gate_up.weight"] = torch.cat([sd.pop(n) for n in names], 0)
+
+    def forward(self, x):
+        return self.down_proj(swiglu(self.gate_up(x)))
+
+
+class LlamaDecoderLayer(tnn.Module):
+    """``h += attn(input_layernorm(h))``, ``h += mlp(post_attention_layernorm(h))``.  The layer
+    receives ``input_layernorm(h)`` already computed (by the previous layer's closing add-and-
+    normalise) and returns its MLP branch and the stream; the caller's next ``add_norm`` closes it."""
+
+    def __init__(self, hidden, heads, kv_heads, inter, eps):
+        super().__init__()
+        self.self_attn = LlamaAttention(hidden, heads, kv_heads)
+        self.mlp = LlamaMLP(hidden, inter)
+        self.input_layernorm = RMSNorm(hidden, eps)
+        self.post_attention_layernorm = RMSNorm(hidden, eps)
+
+    def forward(self, x, s, B, L, table, bias=None):
+        a = self.self_attn(x, B, L, table, bias)
+        x2, s2 = self.post_attention_layernorm.add_norm(a, residual=s)
+        return self.mlp(x2), s2
+
+
+class LlamaModel(tnn.Module):
+    def __init__(self, vocab, hidden, layers, heads, kv_heads, inter, max_pos, eps, rope_theta):
+        super().__init__()
+        self.embed_tokens = tnn.Embedding(vocab, hidden)
+        self.layers = tnn.ModuleList([LlamaDecoderLayer(hidden, heads, kv_heads, inter, eps) for _ in range(layers)])
+        self.norm = RMSNorm(hidden, eps)
+        self.max_pos = max_pos
+        # cos | sin of every position: built in fp64, rounded to fp32 once; a buffer, not a parameter
+        self.register_buffer("rope_table", rope_table(max_pos, rope_theta), persistent=False)
+        # storage rows padded to 8 so a tied lm_head Linear can share the token table
+        vp = -(-vocab // 8) * 8
+        self.embed_tokens.weight._kml_storage_shape = (vp, hidden)
+        self.embed_tokens.weight._kml_view = lambda st: st[:vocab, :hidden]
+
+    def forward(self, ids, attention_mask=None):
+        B, L = ids.shape
+        if L > self.max_pos:
+            raise ValueError(f"sequence length {L} exceeds max_pos {self.max_pos}")
+        bias = None
+        if attention_mask is not None:
+            bias = ((1.0 - attention_mask.float()) * -10000.0).reshape(B, L).contiguous()
+        if not ids.is_cuda:
+            e = self.embed_tokens(ids).reshape(B * L, -1)
+            if bias is not None:
+                bias = bias.to(e.dtype)
+        else:
+            e = _TokEmbFn.apply(ids.reshape(-1).contiguous(), self.embed_tokens.weight, L)
+        # from here on (x, s) = (RMSNorm(s), stream)
+        x, s = self.layers[0].input_layernorm.add_norm(e)
+        closers = [lay.input_layernorm for lay in self.layers[1:]] + [self.norm]
+        for lay, norm in zip(self.layers, closers):
+            m, s = lay(x, s, B, L, self.rope_table, bias)
+            x, s = norm.add_norm(m, residual=s)
+        return x
+
+
+class LlamaForCausalLM(tnn.Module):
+    def __init__(self, vocab=32000, hidden=576, layers=30, heads=9, kv_heads=3, inter=1536, max_pos=2048, eps=1e-5,
+                 rope_theta=10000.0, tie_word_embeddings=False, seed: int = 0):
+        super().__init__()
+        self.vocab = vocab
+        self.tie_word_embeddings = bool(tie_word_embeddings)
+        self.seed = seed
+        self.model = LlamaModel(vocab, hidden, layers, heads, kv_heads, inter, max_pos, eps, rope_theta)
+        self.lm_head = Linear(hidden, vocab, bias=False)
+        if self.tie_word_embeddings:   # lm_head.weight IS the token table
+            self.lm_head.weight = self.model.embed_tokens.weight
+        self._init_weights()
+        self._register_load_state_dict_pre_hook(LlamaForCausalLM._load_hook, with_module=True)
+
+    @classmethod
+    def from_hf_config(cls, config, **overrides):
+        """Build the model a HuggingFace Llama ``config`` describes: a ``LlamaConfig``, a dict, or
+        the path of a ``config.json``.  Maps the sizes, ``rms_norm_eps``, ``rope_theta`` and
+        ``tie_word_embeddings``.  Raises ``ValueError`` for what this model does not implement:
+        a head dim other than 64, ``hidden_act`` other than ``silu``, a ``rope_scaling``,
+        ``attention_bias`` / ``mlp_bias``, a non-zero ``attention_dropout``.  ``overrides`` replace
+        constructor arguments.  Follow with ``load_state_dict(hf_model.state_dict())``."""
+        if isinstance(config, (str, os.PathLike)):
+            with open(config) as f:
+                config = json.load(f)
+        elif hasattr(config, "to_dict"):
+            config = config.to_dict()
+        if not isinstance(config, dict):
+            raise TypeError(f"from_hf_config: a LlamaConfig, a dict or a path, got {type(config).__name__}")
+        c = config
+        hidden, heads = c.get("hidden_size", 4096), c.get("num_attention_heads", 32)
+        head_dim = c.get("head_dim") or hidden // heads
+        if head_dim != 64:
+            raise ValueError(f"from_hf_config: head dim {head_dim} (hidden {hidden}, {heads} heads); only 64 is "
+                             "implemented")
+        if c.get("hidden_act", "silu") != "silu":
+            raise ValueError(f"from_hf_config: hidden_act {c.get('hidden_act')!r} (supported: 'silu')")
+        if c.get("rope_scaling") is not None:
+            raise ValueError("from_hf_config: rope_scaling is not implemented")
+        for k in ("attention_bias", "mlp_bias"):
+            if c.get(k, False):
+                raise ValueError(f"from_hf_config: {k} is not implemented")
+        if c.get("attention_dropout", 0.0) != 0.0:
+            raise ValueError("from_hf_config: attention_dropout is not implemented")
+        kvh = c.get("num_key_value_heads")
+        kw = dict(vocab=c.get("vocab_size", 32000), hidden=hidden, layers=c.get("num_hidden_layers", 32), heads=heads,
+                  kv_heads=heads if kvh is None else kvh, inter=c.get("intermediate_size", 11008),
+                  max_pos=c.get("max_position_embeddings", 2048), eps=c.get("rms_norm_eps", 1e-6),
+                  rope_theta=c.get("rope_theta", 10000.0), tie_word_embeddings=c.get("tie_word_embeddings", False))
+        kw.update(overrides)
+        return cls(**kw)
+
+    def _init_weights(self):
+        g = torch.Generator().manual_seed(self.seed)
+        for m in self.modules():
+            if isinstance(m, (Linear, tnn.Embedding)):
+                if m is self.lm_head and self.tie_word_embeddings:
+                    continue
+                with torch.no_grad():
+                    m.weight.normal_(0.0, 0.02, generator=g)
+            elif isinstance(m, RMSNorm):
+                tnn.init.ones_(m.weight)
+
+    @staticmethod
+    def _load_hook(mod, sd, prefix, local_metadata, strict, missing, unexpected, errors):
+        if mod.tie_word_embeddings and prefix + "lm_head.weight" not in sd \
+                and prefix + "model.embed_tokens.weight" in sd:
+            sd[prefix + "lm_head.weight"] = sd[prefix + "model.embed_tokens.weight"]
+
+    def forward(self, ids, attention_mask=None, labels=None, return_correct=False):
+        """ids [B, L]; labels [B, L] (may be ``ids`` itself): position t is scored against
+        labels[:, t + 1], the last position of every sequence is ignored.  Returns logits
+        ``[B*L, vocab]``, or the mean loss (and the correct count) when labels are given."""
+        z = self.model(ids, attention_mask)
+        if labels is None:
+            return self.lm_head(z)
+        if ids.is_cuda:
+            from ..ops import transformer as T
+            tgt = T.lm_shift_labels(labels, -100)
+        else:
+            tgt = torch.cat([labels[:, 1:], torch.full_like(labels[:, :1], -100)], 1)
+        logits = self.lm_head(z, keep_pad=True)   # vocab-padded logits used in place
+        return cross_entropy(logits, tgt.reshape(-1), ignore_index=-100, return_correct=return_correct,
+                             classes=self.vocab)
+
+
+def llama_tiny(**kw) -> LlamaForCausalLM:
+    """2-layer, 128-hidden, 4-head / 2-KV-head variant for tests (gpt2_tiny's scale)."""
+    cfg = dict(vocab=1000, hidden=128, layers=2, heads=4, kv_heads=2, inter=352, max_pos=256)
+    cfg.update(kw)
+    return LlamaForCausalLM(**cfg)

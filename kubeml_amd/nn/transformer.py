@@ -8,6 +8,9 @@ fp32 stock-torch path on CPU with identical parameters / ``state_dict`` names).
   attention kernel + output projection; ``state_dict`` exposes HuggingFace's
   ``query/key/value`` names via state-dict hooks
 * :class:`Embeddings`    — word + position + token-type gather and LayerNorm
+* :class:`RMSNorm`, :func:`rope`, :func:`swiglu` — the Llama block's norm (fused residual add),
+  rotary embedding (in place on the fused QKV buffer) and gated SiLU (csrc/kernels/llama.hip);
+  ``_AttnFn`` / :func:`attention_reference` take ``kv_heads`` for grouped-query attention
 """
 from __future__ import annotations
 
@@ -238,16 +241,21 @@ class Dropout(tnn.Module):
 
 
 # ====================================================================================== attention
+def _split_qkv(qkv, H, kv_heads):
+    """(q, k, v) column views of a fused ``[T, (H + 2 Hkv) * 64]`` buffer: H*64 | Hkv*64 | Hkv*64."""
+    D, E = H * 64, (H if kv_heads is None else kv_heads) * 64
+    return qkv[:, :D], qkv[:, D:D + E], qkv[:, D + E:D + 2 * E]
+
+
 class _AttnFn(Function):
     @staticmethod
-    def forward(ctx, qkv, B, H, L, bias, drop=None, causal=False):
+    def forward(ctx, qkv, B, H, L, bias, drop=None, causal=False, kv_heads=None):
         from ..ops import transformer as T
-        D = H * 64
-        q, k, v = qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:]
+        q, k, v = _split_qkv(qkv, H, kv_heads)
         keep = T.attn_keep_buffer(B, H, L, qkv.device) if drop is not None and drop[2] > 0.0 else None
-        out, lse = T.attn_fwd(q, k, v, B, H, L, bias=bias, drop=drop, keep=keep, causal=causal)
+        out, lse = T.attn_fwd(q, k, v, B, H, L, bias=bias, drop=drop, keep=keep, causal=causal, kv_heads=kv_heads)
         ctx.save = (qkv, out, lse, bias, keep)
-        ctx.dims = (B, H, L)
+        ctx.dims = (B, H, L, kv_heads)
         ctx.drop = drop
         ctx.causal = causal
         return out
@@ -256,22 +264,26 @@ class _AttnFn(Function):
     def backward(ctx, dout):
         from ..ops import transformer as T
         qkv, out, lse, bias, keep = ctx.save
-        B, H, L = ctx.dims
-        D = H * 64
+        B, H, L, kv_heads = ctx.dims
         dqkv = torch.empty_like(qkv)
-        T.attn_bwd(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], out, _bf(dout).contiguous(), lse, B, H, L, bias=bias,
-                   dq=dqkv[:, :D], dk=dqkv[:, D:2 * D], dv=dqkv[:, 2 * D:], drop=ctx.drop, keep=keep,
-                   causal=ctx.causal)
+        q, k, v = _split_qkv(qkv, H, kv_heads)
+        dq, dk, dv = _split_qkv(dqkv, H, kv_heads)
+        T.attn_bwd(q, k, v, out, _bf(dout).contiguous(), lse, B, H, L, bias=bias, dq=dq, dk=dk, dv=dv, drop=ctx.drop,
+                   keep=keep, causal=ctx.causal, kv_heads=kv_heads)
         ctx.save = None
-        return dqkv, None, None, None, None, None, None
+        return dqkv, None, None, None, None, None, None, None
 
 
-def attention_reference(qkv, B, H, L, bias=None, keep=None, causal=False):
+def attention_reference(qkv, B, H, L, bias=None, keep=None, causal=False, kv_heads=None):
     """fp32 torch attention on a fused [B*L, 3*H*64] buffer (CPU path / tests); keep:
     optional [B, H, L, L] dropout multiplier (0 or 1/(1-p)) applied to the probabilities;
-    causal: lower-triangular mask (query t attends keys <= t)."""
+    causal: lower-triangular mask (query t attends keys <= t); kv_heads: grouped-query attention
+    on a [B*L, (H + 2 kv_heads)*64] buffer (query head h reads K/V head h // (H // kv_heads))."""
     D = H * 64
-    q, k, v = (qkv[:, i * D:(i + 1) * D].reshape(B, L, H, 64).permute(0, 2, 1, 3) for i in range(3))
+    Hkv = H if kv_heads is None else kv_heads
+    q, k, v = (t.reshape(B, L, -1, 64).permute(0, 2, 1, 3) for t in _split_qkv(qkv, H, kv_heads))
+    if Hkv != H:
+        k, v = (t.repeat_interleave(H // Hkv, dim=1) for t in (k, v))
     s = q @ k.transpose(-1, -2) / math.sqrt(64)
     if bias is not None:
         s = s + bias.view(B, 1, 1, L)
@@ -354,6 +366,143 @@ class SelfAttention(tnn.Module):
                 drop = (self.rng.tensor(x.device), self.salt, self.attn_dropout)
             ctx = _AttnFn.apply(qkv.contiguous(), B, self.heads, L, bias, drop, self.causal)
         return self.out(ctx)
+
+
+# ====================================================================================== Llama block ops
+class _RMSFn(Function):
+    """(RMSNorm(s), s) with s = x + res on the RMSNorm kernels alone: the forward writes the
+    stream beside the normalised row, the backward takes the stream gradient as its ``dx_add``
+    addend (the LayerNorm ``add_norm`` chain without mean, beta or dropout)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, mod, res):
+        from ..ops import transformer as T
+        y, s, rstd = T.rmsnorm_fwd(x, master_of(weight), res=res, eps=mod.eps)
+        if s is x:   # no residual: the stream is the input itself
+            s = x.view_as(x)
+        ctx.save = (s, rstd)
+        ctx.mod = mod
+        ctx.has_res = res is not None
+        ctx.set_materialize_grads(False)
+        return y, s
+
+    @staticmethod
+    def backward(ctx, dy, ds):
+        from ..ops import transformer as T
+        s, rstd = ctx.save
+        mod = ctx.mod
+        if dy is None:
+            raise RuntimeError("RMSNorm: the normalised output must take part in the loss")
+        dx = T.rmsnorm_bwd(_bf(dy).contiguous(), s, rstd, master_of(mod.weight), grad_storage_of(mod.weight),
+                           dx_add=None if ds is None else _bf(ds).contiguous())
+        ctx.save = None
+        return dx, None, None, (dx if ctx.has_res else None)
+
+
+class RMSNorm(tnn.Module):
+    """``x * rsqrt(mean(x^2) + eps) * weight`` over the last dim (Llama's norm: no mean, no bias).
+    ``forward(x, residual)`` normalises ``x + residual``; :meth:`add_norm` also returns the sum —
+    the pre-norm residual stream carried inside the norm launch, forward and backward."""
+
+    def __init__(self, hidden: int, eps: float = 1e-5):
+        super().__init__()
+        self.hidden, self.eps = hidden, eps
+        self.weight = tnn.Parameter(torch.ones(hidden))
+
+    def extra_repr(self):
+        return f"{self.hidden}, eps={self.eps}"
+
+    def add_norm(self, x, residual=None):
+        """``(RMSNorm(s), s)`` with ``s = x + residual`` (2-d token-major inputs)."""
+        if not x.is_cuda:
+            s = x if residual is None else x + residual
+            return s * torch.rsqrt(s.pow(2).mean(-1, keepdim=True) + self.eps) * self.weight, s
+        r2 = None if residual is None else _bf(residual).contiguous()
+        return _RMSFn.apply(_bf(x).contiguous(), self.weight, self, r2)
+
+    def forward(self, x, residual=None):
+        shp = x.shape
+        if x.is_cuda:
+            x = x.reshape(-1, shp[-1])
+            residual = None if residual is None else residual.reshape(-1, shp[-1])
+        return self.add_norm(x, residual)[0].view(shp)
+
+
+def rope_table(max_pos, theta=10000.0, device=None):
+    """fp32 ``[max_pos, 64]`` table of the rotary embedding: row p = cos(p f_i) (32) | sin(p f_i)
+    (32), f_i = theta^(-i/32), computed in fp64 on the host and rounded once."""
+    f = torch.tensor(float(theta), dtype=torch.float64) ** (-torch.arange(32, dtype=torch.float64) / 32)
+    ang = torch.arange(max_pos, dtype=torch.float64)[:, None] * f[None]
+    t = torch.cat([ang.cos(), ang.sin()], 1).to(torch.float32)
+    return t if device is None else t.to(device)
+
+
+def rope_reference(qkv, table, L, H, kv_heads):
+    """Stock-torch rotary embedding of a fused ``[B*L, (H + 2 Hkv)*64]`` buffer (HF ``rotate_half``:
+    element i < 32 of a head pairs with i + 32); table: :func:`rope_table`."""
+    T_ = qkv.shape[0]
+    n = (H + kv_heads) * 64
+    pos = torch.arange(T_, device=qkv.device) % L
+    tb = table.to(qkv.dtype)[pos]
+    c, s = tb[:, None, :32], tb[:, None, 32:]
+    x = qkv[:, :n].reshape(T_, H + kv_heads, 64)
+    a, b = x[..., :32], x[..., 32:]
+    rot = torch.cat([a * c - b * s, b * c + a * s], -1).reshape(T_, n)
+    return torch.cat([rot, qkv[:, n:]], 1)
+
+
+class _RopeFn(Function):
+    """Rotates Q and K of the fused buffer in place (``kml_rope``); the backward applies the
+    transpose rotation in place to dQ / dK of the incoming ``dqkv``.  The buffer is the qkv
+    Linear's output, which nothing else reads and whose backward does not need it; autograd sees
+    the result as a view of it (``mark_dirty`` is refused on the output of a custom Function that
+    is itself a view, as the GEMM launcher's is)."""
+
+    @staticmethod
+    def forward(ctx, qkv, table, L, H, kv_heads):
+        from ..ops import transformer as T
+        ctx.args = (table, L, H, kv_heads)
+        T.rope_(qkv, table, L, H, kv_heads)
+        return qkv.view_as(qkv)
+
+    @staticmethod
+    def backward(ctx, dqkv):
+        from ..ops import transformer as T
+        table, L, H, kv_heads = ctx.args
+        dqkv = _bf(dqkv).contiguous()
+        T.rope_(dqkv, table, L, H, kv_heads, backward=True)
+        return dqkv, None, None, None, None
+
+
+def rope(qkv, table, L, H, kv_heads):
+    """Rotary position embedding of the Q and K heads of a fused projection buffer (position =
+    row % L).  GPU: in place, one launch; CPU: :func:`rope_reference`."""
+    if not qkv.is_cuda:
+        return rope_reference(qkv, table, L, H, kv_heads)
+    return _RopeFn.apply(_bf(qkv).contiguous(), table, L, H, kv_heads)
+
+
+class _SwiGLUFn(Function):
+    @staticmethod
+    def forward(ctx, gu):
+        from ..ops import transformer as T
+        ctx.gu = gu
+        return T.swiglu_fwd(gu)
+
+    @staticmethod
+    def backward(ctx, dh):
+        from ..ops import transformer as T
+        dgu = T.swiglu_bwd(_bf(dh).contiguous(), ctx.gu)
+        ctx.gu = None
+        return dgu
+
+
+def swiglu(gu):
+    """``silu(gate) * up`` of the fused gate/up projection ``gu = [T, 2*I]`` (gate first)."""
+    if not gu.is_cuda:
+        g, u = gu.chunk(2, -1)
+        return F.silu(g) * u
+    return _SwiGLUFn.apply(_bf(gu).contiguous())
 
 
 # ====================================================================================== embeddings

@@ -56,16 +56,27 @@ def _keep_arg(keep, B, H, L, drop):
     return keep.data_ptr()
 
 
-def attn_fwd(q, k, v, B, H, L, bias=None, out=None, scale=None, drop=None, keep=None, causal=False):
+def _kv_heads(H, kv_heads):
+    """Hkv of a grouped-query call (None: H, the one-K/V-head-per-query-head entry points)."""
+    Hkv = H if kv_heads is None else int(kv_heads)
+    if Hkv < 1 or H % Hkv:
+        raise ValueError(f"kv_heads {kv_heads} must divide heads {H}")
+    return Hkv
+
+
+def attn_fwd(q, k, v, B, H, L, bias=None, out=None, scale=None, drop=None, keep=None, causal=False, kv_heads=None):
     """q/k/v: [B*L, ld] bf16 views with head h at columns 64h..64h+63 (may be column
-    slices of one fused QKV buffer).  drop: (ctr, salt, p) attention-probability dropout;
+    slices of one fused QKV buffer).  kv_heads: grouped-query attention — k / v hold ``kv_heads``
+    heads and query head h reads K/V head ``h // (H // kv_heads)`` (None: H heads, the plain entry
+    points).  drop: (ctr, salt, p) attention-probability dropout;
     keep: optional :func:`attn_keep_buffer` that receives the dropout keep bits, so
     :func:`attn_bwd` reads them instead of re-hashing.  causal: query t attends keys <= t only
     (the key tiles above the diagonal are skipped).  Returns (out [B*L, H*64], lse [B*H, L])."""
-    for n, t in (("q", q), ("k", k), ("v", v)):
+    Hkv = _kv_heads(H, kv_heads)
+    for n, t, hh in (("q", q, H), ("k", k, Hkv), ("v", v, Hkv)):
         _chk_view(t, n)
-        if t.shape[0] != B * L or t.shape[1] < H * 64:
-            raise ValueError(f"{n}: expected a row-major [B*L, >= {H * 64}] view, got {tuple(t.shape)}")
+        if t.shape[0] != B * L or t.shape[1] < hh * 64:
+            raise ValueError(f"{n}: expected a row-major [B*L, >= {hh * 64}] view, got {tuple(t.shape)}")
     if bias is not None:
         _chk(bias, F32, "bias")
         if bias.numel() != B * L:
@@ -75,6 +86,12 @@ def attn_fwd(q, k, v, B, H, L, bias=None, out=None, scale=None, drop=None, keep=
     lse = torch.empty((B * H, L), dtype=F32, device=q.device)
     scale = 1.0 / math.sqrt(64) if scale is None else scale
     c, salt, pd = _drop_args(drop)
+    if kv_heads is not None:
+        HIP.call("kml_attn_gqa_fwd", "p p p p p p i i i i i i i i f p i f p i s",
+                 _p(q), _p(k), _p(v), _p(out), _p(lse), _p(bias), q.stride(0), k.stride(0), v.stride(0),
+                 out.stride(0), B, H, Hkv, L, float(scale), c, salt, pd, _keep_arg(keep, B, H, L, drop),
+                 int(bool(causal)), _s())
+        return out, lse
     HIP.call("kml_attn_causal_fwd" if causal else "kml_attn_fwd", "p p p p p p i i i i i i i f p i f p s",
              _p(q), _p(k), _p(v), _p(out), _p(lse), _p(bias), q.stride(0), k.stride(0), v.stride(0), out.stride(0),
              B, H, L, float(scale), c, salt, pd, _keep_arg(keep, B, H, L, drop), _s())
@@ -82,26 +99,36 @@ def attn_fwd(q, k, v, B, H, L, bias=None, out=None, scale=None, drop=None, keep=
 
 
 def attn_bwd(q, k, v, o, dout, lse, B, H, L, bias=None, dq=None, dk=None, dv=None, scale=None, drop=None,
-             keep=None, causal=False):
+             keep=None, causal=False, kv_heads=None):
     """Gradients of attention; dq/dk/dv may be column views of one [B*L, 3*H*64] buffer.
     keep: the keep-bit buffer the forward filled (same drop), or None to re-hash the mask;
-    causal: as given to :func:`attn_fwd`."""
+    causal, kv_heads: as given to :func:`attn_fwd`.  Grouped-query: dk / dv have ``kv_heads * 64``
+    columns, each head the sum over its group of query heads (fp32 accumulators, fixed order)."""
     dev = q.device
+    Hkv = _kv_heads(H, kv_heads)
     if dq is None:
         dq = torch.empty((B * L, H * 64), dtype=BF16, device=dev)
     if dk is None:
-        dk = torch.empty((B * L, H * 64), dtype=BF16, device=dev)
+        dk = torch.empty((B * L, Hkv * 64), dtype=BF16, device=dev)
     if dv is None:
-        dv = torch.empty((B * L, H * 64), dtype=BF16, device=dev)
-    for n, t in (("q", q), ("k", k), ("v", v), ("o", o), ("dout", dout), ("dq", dq), ("dk", dk), ("dv", dv)):
+        dv = torch.empty((B * L, Hkv * 64), dtype=BF16, device=dev)
+    for n, t, hh in (("q", q, H), ("k", k, Hkv), ("v", v, Hkv), ("o", o, H), ("dout", dout, H), ("dq", dq, H),
+                     ("dk", dk, Hkv), ("dv", dv, Hkv)):
         _chk_view(t, n)
-        if t.shape[0] != B * L or t.shape[1] < H * 64:
-            raise ValueError(f"{n}: expected [B*L, >= {H * 64}], got {tuple(t.shape)}")
+        if t.shape[0] != B * L or t.shape[1] < hh * 64:
+            raise ValueError(f"{n}: expected [B*L, >= {hh * 64}], got {tuple(t.shape)}")
     if lse.shape != (B * H, L) or lse.dtype != F32:
         raise ValueError("lse must be fp32 [B*H, L] from attn_fwd")
     dsum = torch.empty((B * H, L), dtype=F32, device=dev)
     scale = 1.0 / math.sqrt(64) if scale is None else scale
     c, salt, pd = _drop_args(drop)
+    if kv_heads is not None:
+        HIP.call("kml_attn_gqa_bwd", "p p p p p p p p p p p i i i i i i i i i i i i f p i f p i s",
+                 _p(q), _p(k), _p(v), _p(o), _p(dout), _p(lse), _p(dsum), _p(bias), _p(dq), _p(dk), _p(dv),
+                 q.stride(0), k.stride(0), v.stride(0), o.stride(0), dout.stride(0), dq.stride(0), dk.stride(0),
+                 dv.stride(0), B, H, Hkv, L, float(scale), c, salt, pd, _keep_arg(keep, B, H, L, drop),
+                 int(bool(causal)), _s())
+        return dq, dk, dv
     HIP.call("kml_attn_causal_bwd" if causal else "kml_attn_bwd",
              "p p p p p p p p p p p i i i i i i i i i i i f p i f p s",
              _p(q), _p(k), _p(v), _p(o), _p(dout), _p(lse), _p(dsum), _p(bias), _p(dq), _p(dk), _p(dv),
@@ -150,6 +177,89 @@ def ln_bwd(dy, xin, mean, rstd, gamma, dgamma, dbeta, dx_add=None, drop=None, db
              _p(dx), _p(dx_add), _p(dgamma), _p(dbeta), _p(ws), _p(cnt), M, N, _p(dxd), _p(ctr),
              int(salt) & 0x7FFFFFFF, float(p), _p(dbias_in), _s())
     return (dx, dxd) if drop is not None else dx
+
+
+def rmsnorm_fwd(x, gamma, res=None, eps=1e-5, keep_sum=True):
+    """RMSNorm over the last dim of a [T, N] bf16 tensor (optionally of x + res).  Returns
+    (y, norm_input, rstd) — norm_input is x + res (or x itself without a residual)."""
+    _chk(x, BF16, "x")
+    N = x.shape[-1]
+    M = x.numel() // N
+    if res is not None:
+        _chk(res, BF16, "res")
+        if res.shape != x.shape:
+            raise ValueError("res must have x's shape")
+    if gamma.numel() < N:
+        raise ValueError("gamma shorter than N")
+    y = torch.empty_like(x)
+    s = torch.empty_like(x) if (res is not None and keep_sum) else None
+    rstd = torch.empty(M, dtype=F32, device=x.device)
+    HIP.call("kml_rmsnorm_fwd", "p p p p p p l i f s", _p(x), _p(res), _p(gamma), _p(y), _p(s), _p(rstd), M, N,
+             float(eps), _s())
+    return y, (s if s is not None else x), rstd
+
+
+def rmsnorm_bwd(dy, xin, rstd, gamma, dgamma, dx_add=None):
+    """dx (+ dx_add); dgamma += column sums of dy * xin * rstd — per-block partial rows folded in
+    block order by the last block of the same launch (deterministic, no float atomics)."""
+    _chk(dy, BF16, "dy")
+    _chk(xin, BF16, "xin")
+    _chk(dgamma, F32, "dgamma")
+    N = dy.shape[-1]
+    M = dy.numel() // N
+    if xin.shape != dy.shape or rstd.numel() != M or dgamma.numel() < N or gamma.numel() < N:
+        raise ValueError("rmsnorm_bwd: shapes of xin / rstd / gamma / dgamma do not match dy")
+    if dx_add is not None:
+        _chk(dx_add, BF16, "dx_add")
+        if dx_add.shape != dy.shape:
+            raise ValueError("dx_add must have dy's shape")
+    dx = torch.empty_like(dy)
+    ws = torch.empty(HIP.raw("kml_rmsnorm_bwd_ws_floats", M, N), dtype=F32, device=dy.device)
+    cnt = _COUNTERS.take(dy.device, 1)
+    HIP.call("kml_rmsnorm_bwd", "p p p p p p p p p l i s", _p(dy), _p(xin), _p(rstd), _p(gamma), _p(dx), _p(dx_add),
+             _p(dgamma), _p(ws), _p(cnt), M, N, _s())
+    return dx
+
+
+def rope_(qkv, table, L, H, kv_heads, backward=False):
+    """Rotary embedding in place on the fused ``[B*L, (H + 2 kv_heads) * 64]`` projection buffer (or
+    its gradient with ``backward``: the transpose rotation): the H query and kv_heads key heads are
+    rotated by the position ``row % L``, V is left alone.  table: ``nn.transformer.rope_table``."""
+    _chk_view(qkv, "qkv")
+    _chk(table, F32, "table")
+    if table.dim() != 2 or table.shape[1] != 64 or L > table.shape[0]:
+        raise ValueError(f"rope_: table must be [max_pos >= {L}, 64], got {tuple(table.shape)}")
+    if qkv.shape[1] != (H + 2 * kv_heads) * 64 or qkv.shape[0] % L:
+        raise ValueError(f"rope_: expected [B*{L}, {(H + 2 * kv_heads) * 64}], got {tuple(qkv.shape)}")
+    HIP.call("kml_rope", "p i p l i i i i i s", _p(qkv), qkv.stride(0), _p(table), qkv.shape[0], L, H, kv_heads,
+             table.shape[0], int(bool(backward)), _s())
+    return qkv
+
+
+def _chk_gu(gu, name):
+    _chk_view(gu, name)
+    if gu.shape[1] % 16:
+        raise ValueError(f"{name}: expected [T, 2*I] with I % 8 == 0, got {tuple(gu.shape)}")
+    return gu.shape[0], gu.shape[1] // 2
+
+
+def swiglu_fwd(gu):
+    """h = silu(gu[:, :I]) * gu[:, I:] of the fused gate/up projection ``[T, 2*I]``."""
+    T_, I = _chk_gu(gu, "gu")
+    h = torch.empty((T_, I), dtype=BF16, device=gu.device)
+    HIP.call("kml_swiglu_fwd", "p i p l i s", _p(gu), gu.stride(0), _p(h), T_, I, _s())
+    return h
+
+
+def swiglu_bwd(dh, gu):
+    """dgu ``[T, 2*I]`` = [dh u sig(g) (1 + g (1 - sig(g))) | dh silu(g)] from dh ``[T, I]``."""
+    T_, I = _chk_gu(gu, "gu")
+    _chk(dh, BF16, "dh")
+    if tuple(dh.shape) != (T_, I) or not dh.is_contiguous() or gu.stride(0) != 2 * I:
+        raise ValueError(f"swiglu_bwd: dh must be contiguous [{T_}, {I}] and gu contiguous")
+    dgu = torch.empty_like(gu)
+    HIP.call("kml_swiglu_bwd", "p p i p l i s", _p(dh), _p(gu), gu.stride(0), _p(dgu), T_, I, _s())
+    return dgu
 
 
 def _tanh(approximate, who):
