@@ -73,6 +73,20 @@ __device__ __forceinline__ float kml_gelu_tanh_grad(float x) {
   return fmaf(x * s * (1.f - s), 1.5957691216057308f * fmaf(0.134145f, xc * xc, 1.f), s);
 }
 
+// sigmoid through one v_exp_f32 and one rcp: exp2(-g log2 e) is +inf for g << 0 (rcp: 0) and 0
+// for g >> 0 (sigmoid 1), so every finite g gives finite values forward and backward.
+__device__ __forceinline__ float sigmoidf_fast(float g) {
+  return __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-g * 1.4426950408889634f));
+}
+
+// One pair of the rotary embedding (HF rotate_half: a = element i < 32 of a head, b = element
+// i + 32): (a, b) -> (a c - b s, b c + a s).  One definition for kml_rope and the decode append,
+// so a key rotated by either has the same bits.
+__device__ __forceinline__ void kml_rope_pair(float a, float b, float c, float s, float& oa, float& ob) {
+  oa = a * c - b * s;
+  ob = b * c + a * s;
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

@@ -1,4 +1,4 @@
-// decode.hip — one-token-at-a-time inference for the decoder LMs (models/gpt.py) on gfx950:
+// decode.hip — one-token-at-a-time inference for the decoder LMs (models/gpt.py, models/llama.py) on gfx950:
 //   kml_kv_append       K / V columns of a token-major fused QKV buffer -> head-major cache
 //   kml_attn_decode     one query per (sequence, head) against the cached keys, split over the key
 //                       range in chunks of a FIXED number of keys; the last block of a (b, h) to
@@ -14,6 +14,12 @@
 //                       bit-identical to the one-row kernels at that length
 //   kml_draft_lookup    n-gram (prompt lookup) drafter over a sequence's own history
 //   kml_verify_pick     the pick of every row, then accept / commit on the device
+//   Llama-style decoders (models/llama.py: RoPE, grouped-query heads, gated MLP):
+//   kml_kv_append_rope   Q rotated in place, K rotated into / V copied to an Hkv-head cache, one launch
+//   kml_attn_decode_gqa  kml_attn_decode over the Hkv-head cache: a block loads its chunk of a K/V
+//                        head once and the query heads of the group take turns against it
+//   kml_gemm_skinny_glu  silu(x · Wgᵀ) * (x · Wuᵀ): the skinny GEMM with two accumulators and the
+//                        gate in its epilogue
 // Sequence lengths, the sampling temperature, seed, step and eos live in device memory, so one
 // captured step replays for every token.  No float atomics anywhere: every reduction has a fixed
 // order (lane butterflies, wave order in LDS, chunk / split order in the fold).
@@ -60,6 +66,13 @@ __device__ __forceinline__ void unpack8(const uint4 v, float* f) {
   f[4] = lo_bf(v.z); f[5] = hi_bf(v.z); f[6] = lo_bf(v.w); f[7] = hi_bf(v.w);
 }
 
+__device__ __forceinline__ uint4 pack8(const float* f) {
+  uint4 v;
+  v.x = pack_bf2(f[0], f[1]); v.y = pack_bf2(f[2], f[3]);
+  v.z = pack_bf2(f[4], f[5]); v.w = pack_bf2(f[6], f[7]);
+  return v;
+}
+
 // ------------------------------------------------------------------------------------ KV append
 // One thread per 16 bytes: (token row, head, K | V, 8 columns).  Prefill: row t of sequence b goes
 // to cache row t; decode: to cache row lens[b] + t (Lq = 1 in a plain step, the rows of a verify
@@ -80,6 +93,60 @@ __global__ __launch_bounds__(256) void k_kv_append(const bf16_t* __restrict__ qk
   const uint4 v = *reinterpret_cast<const uint4*>(qkv + tr * ldq + (long long)(1 + isv) * H * 64 + h * 64 + c8 * 8);
   bf16_t* dst = (isv ? vc : kc) + (((long long)b * H + h) * Lcap + row) * 64 + c8 * 8;
   *reinterpret_cast<uint4*>(dst) = v;
+}
+
+// --------------------------------------------------------------------- KV append + RoPE (Llama)
+// The fused projection row of a grouped-query model: H query heads | Hkv key heads | Hkv value
+// heads of 64.  One thread per (token row, head, 8 pairs): 16 bytes from each half of the head,
+// the pairing of kml_rope.  Q heads are rotated in place, K heads are rotated on their way into
+// cache row r of the [B, Hkv, Lcap, 64] key cache (the buffer keeps the unrotated key: nothing
+// reads it), V heads are copied.  r = lens[b] + t (decode) or t (prefill); the rotation position
+// is r clamped to the table; rows outside [0, Lcap) are dropped as k_kv_append drops them.
+// rotate == 0: append only (the prefill has run kml_rope over the whole buffer already).  The
+// rotation is kml_rope's own (kml_rope_pair, same table, one rounding): a key appended by a step
+// has the bits the prefill would have stored at that position.
+__global__ __launch_bounds__(256) void k_kv_append_rope(bf16_t* __restrict__ qkv, int ldq, bf16_t* __restrict__ kc,
+                                                        bf16_t* __restrict__ vc, const int* __restrict__ lens,
+                                                        const float* __restrict__ table, int B, int H, int Hkv,
+                                                        int Lq, int Lcap, int max_pos, int decode, int rotate) {
+  const int HT = H + 2 * Hkv;
+  const long long total = (long long)B * Lq * HT * 4;
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  const int c = (int)(i & 3);
+  const long long rh = i >> 2;
+  const int head = (int)(rh % HT);
+  const long long tr = rh / HT;          // token row b * Lq + t
+  const int b = (int)(tr / Lq), t = (int)(tr % Lq);
+  const int row = decode ? lens[b] + t : t;
+  const bool isq = head < H, isv = head >= H + Hkv;
+  const bool fits = row >= 0 && row < Lcap;
+  if (isq ? !rotate : !fits) return;     // nothing to write
+  bf16_t* p = qkv + tr * ldq + head * 64 + c * 8;
+  uint4 lo = *reinterpret_cast<const uint4*>(p);
+  uint4 hi = *reinterpret_cast<const uint4*>(p + 32);
+  if (rotate && !isv) {
+    const int pos = row < 0 ? 0 : (row > max_pos - 1 ? max_pos - 1 : row);
+    const float* tb = table + (long long)pos * 64 + c * 8;
+    const float4 c0 = *reinterpret_cast<const float4*>(tb), c1 = *reinterpret_cast<const float4*>(tb + 4);
+    const float4 s0 = *reinterpret_cast<const float4*>(tb + 32), s1 = *reinterpret_cast<const float4*>(tb + 36);
+    const float cs[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w};
+    const float sn[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
+    float a[8], bb[8], oa[8], ob[8];
+    unpack8(lo, a);
+    unpack8(hi, bb);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) kml_rope_pair(a[k], bb[k], cs[k], sn[k], oa[k], ob[k]);
+    lo = pack8(oa);
+    hi = pack8(ob);
+  }
+  bf16_t* dst = p;
+  if (!isq) {
+    const int hk = isv ? head - H - Hkv : head - H;
+    dst = (isv ? vc : kc) + (((long long)b * Hkv + hk) * Lcap + row) * 64 + c * 8;
+  }
+  *reinterpret_cast<uint4*>(dst) = lo;
+  *reinterpret_cast<uint4*>(dst + 32) = hi;
 }
 
 // ------------------------------------------------------------------------------ decode attention
@@ -297,6 +364,101 @@ static inline SkinnyPlan skinny_plan(int N, int K, int splits) {
   p.S = (nk + p.cps - 1) / p.cps;
   p.groups = n16;
   return p;
+}
+
+// --------------------------------------------------------------------- skinny GEMM, gated (SwiGLU)
+// h[M <= 16][I] = silu(x · Wgᵀ) * (x · Wuᵀ), w = [2 I, K] the fused gate_up weight, gate rows first.
+// k_gemm_skinny with two accumulators: grid (ceil(I / 16), S), a block owns gate rows n0 .. n0 + 15
+// and up rows I + n0 .. I + n0 + 15 and `cps` 64-wide K chunks.  Per chunk a wave loads its x
+// fragments once and issues them against the gate slab and the up slab, so every weight byte is
+// read once and the [M, 2 I] gate / up values never reach memory.  Rows n0 + r >= I of the last
+// group are masked in BOTH slabs (I % 8 == 0 is all that is promised: the last gate group would
+// otherwise read up rows).  The wave partials of both tiles are summed in wave order through LDS
+// (2 x 16 x 16 fp32 per wave); with S > 1 they go to a workspace of 512 floats per (group, split)
+// and the last block folds splits 0 .. S-1 in that order.  The gate is applied once, after the
+// fold, in fp32 — k_swiglu_fwd's expression — and the product is rounded once to bf16.  Block
+// shape and split: skinny_plan(I, K), so a row's result depends on neither M nor the other rows.
+template <int NW, int U>
+__global__ __launch_bounds__(NW * 64) void k_gemm_skinny_glu(const bf16_t* __restrict__ x, int ldx,
+                                                             const bf16_t* __restrict__ w, int ldw,
+                                                             bf16_t* __restrict__ y, int ldy, int M, int I, int K,
+                                                             int cps, float* __restrict__ ws,
+                                                             unsigned* __restrict__ cnt) {
+  constexpr int NT = NW * 64, E = 256;
+  __shared__ float red[NW][2][E];
+  __shared__ unsigned sh_last;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int r = lane & 15, g = lane >> 4;
+  const int nb = blockIdx.x, sp = blockIdx.y, S = gridDim.y;
+  const int n0 = nb * 16;
+  const int nk = (K + 63) >> 6;
+  const int c0 = sp * cps;
+  const int c1 = c0 + cps < nk ? c0 + cps : nk;
+  const bool xok = r < M, wok = n0 + r < I;
+  const bf16_t* gp = w + (long long)(wok ? n0 + r : 0) * ldw + g * 16;
+  const bf16_t* up = gp + (long long)I * ldw;
+  const bf16_t* xp = x + (long long)(xok ? r : 0) * ldx + g * 16;
+  const bf16x8_t zero = {0, 0, 0, 0, 0, 0, 0, 0};
+  f32x4_t accg = {0.f, 0.f, 0.f, 0.f}, accu = {0.f, 0.f, 0.f, 0.f};
+  for (int cb = c0 + wv; cb < c1; cb += NW * U) {
+    bf16x8_t ag[U][2], au[U][2], bq[U][2];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int c = cb + NW * u;
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const bool ok = c < c1 && c * 64 + g * 16 + j * 8 < K;   // K % 8 == 0: a fragment is in or out
+        ag[u][j] = ok && wok ? *reinterpret_cast<const bf16x8_t*>(gp + c * 64 + j * 8) : zero;
+        au[u][j] = ok && wok ? *reinterpret_cast<const bf16x8_t*>(up + c * 64 + j * 8) : zero;
+        bq[u][j] = ok && xok ? *reinterpret_cast<const bf16x8_t*>(xp + c * 64 + j * 8) : zero;
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        accg = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ag[u][j], bq[u][j], accg, 0, 0, 0);
+        accu = __builtin_amdgcn_mfma_f32_16x16x32_bf16(au[u][j], bq[u][j], accu, 0, 0, 0);
+      }
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    red[wv][0][i * 64 + lane] = accg[i];
+    red[wv][1][i * 64 + lane] = accu[i];
+  }
+  __syncthreads();
+  // element e = 64 i + lane of a 16 x 16 tile, as stored above
+  auto finish = [&](int e, float gt, float uv) {
+    const int m = e & 15, n = n0 + ((e & 63) >> 4) * 4 + (e >> 6);
+    if (m >= M || n >= I) return;
+    y[(long long)m * ldy + n] = f2bf(gt * sigmoidf_fast(gt) * uv);
+  };
+  float* mine = ws + ((long long)nb * S + sp) * (2 * E);
+  for (int e = threadIdx.x; e < E; e += NT) {
+    float gt = red[0][0][e], uv = red[0][1][e];
+#pragma unroll
+    for (int k = 1; k < NW; ++k) {
+      gt += red[k][0][e];
+      uv += red[k][1][e];
+    }
+    if (S > 1) {
+      st_part(mine + e, gt);
+      st_part(mine + E + e, uv);
+    } else {
+      finish(e, gt, uv);
+    }
+  }
+  if (S == 1) return;
+  if (!last_block(cnt + nb, (unsigned)S, &sh_last)) return;
+  const float* p0 = ws + (long long)nb * S * (2 * E);
+  for (int e = threadIdx.x; e < E; e += NT) {
+    float gt = ld_part(p0 + e), uv = ld_part(p0 + E + e);
+    for (int s2 = 1; s2 < S; ++s2) {
+      gt += ld_part(p0 + (long long)s2 * (2 * E) + e);
+      uv += ld_part(p0 + (long long)s2 * (2 * E) + E + e);
+    }
+    finish(e, gt, uv);
+  }
 }
 
 // ------------------------------------------------------------------------------- embedding at lens
@@ -793,6 +955,126 @@ __global__ __launch_bounds__(256) void k_attn_decode_multi(const bf16_t* __restr
   }
 }
 
+// ------------------------------------------------- decode attention, grouped-query (Hkv-head cache)
+// k_attn_decode over a [B, Hkv, Lcap, 64] cache whose K/V head hk serves the G = H / Hkv query
+// heads hk G .. hk G + G - 1.  grid (ceil(Lcap / C), B * Hkv, ceil(G / QG)): a block owns one
+// chunk of one (sequence, K/V head) and up to QG query heads of its group.  It loads the chunk's K
+// and V rows ONCE (k_attn_decode's lane -> key map; keys past lens[b] are never loaded) and keeps
+// them in registers; the query heads then take turns against them as the queries of
+// k_attn_decode_multi do — here every turn has the same length and its own query row.  For query
+// head h every sum is k_attn_decode's, so the result is bit-identical to that kernel on a cache
+// whose K/V heads were repeat-interleaved G times, while the key / value stream is read once per
+// group and not G times (QG = 1: one head per block, the group's blocks side by side — the launcher
+// picks by the size of the grid).  Partials: ws[((b H + h) nch + ch) * ATTN_WS]; one ticket per
+// (b, K/V head, head group); the last block folds chunks 0 .. lens[b] / C in chunk order, wave w
+// the heads w, w + 4, ... of the group.
+template <int C, int QG>
+__global__ __launch_bounds__(256) void k_attn_decode_gqa(const bf16_t* __restrict__ q, int ldq,
+                                                         const bf16_t* __restrict__ kc,
+                                                         const bf16_t* __restrict__ vc, const int* __restrict__ lens,
+                                                         float* __restrict__ ws, unsigned* __restrict__ cnt,
+                                                         bf16_t* __restrict__ out, int ldo, int H, int Hkv, int Lcap,
+                                                         float scale) {
+  constexpr int R = C / 32;
+  __shared__ float sm[QG][4], ss[QG][4], so[QG][4][64];
+  __shared__ unsigned sh_last;
+  const int ch = blockIdx.x, bk = blockIdx.y, nch = gridDim.x;
+  const int b = bk / Hkv, hk = bk % Hkv, G = H / Hkv;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  int len = lens[b];
+  len = len < 0 ? 0 : (len > Lcap - 1 ? Lcap - 1 : len);
+  const int n = len + 1, j0 = ch * C;
+  const int g0 = blockIdx.z * QG, ng = g0 + QG < G ? QG : G - g0;   // this block's heads of the group
+  const int h0 = hk * G + g0;
+  if (j0 < n) {   // block-uniform: a chunk wholly past the sequence writes nothing
+    const int c8 = lane & 7, kr = lane >> 3;
+    const float sc = scale * LOG2E;
+    const long long base = (long long)bk * Lcap * 64 + c8 * 8;
+    uint4 kk[R], vv[R];
+#pragma unroll
+    for (int i = 0; i < R; ++i) {
+      const int j = j0 + i * 32 + wv * 8 + kr;
+      kk[i] = j < n ? *reinterpret_cast<const uint4*>(kc + base + (long long)j * 64) : make_uint4(0, 0, 0, 0);
+    }
+#pragma unroll
+    for (int i = 0; i < R; ++i) {
+      const int j = j0 + i * 32 + wv * 8 + kr;
+      vv[i] = j < n ? *reinterpret_cast<const uint4*>(vc + base + (long long)j * 64) : make_uint4(0, 0, 0, 0);
+    }
+#pragma unroll 1
+    for (int g = 0; g < ng; ++g) {
+      float qf[8];
+      unpack8(*reinterpret_cast<const uint4*>(q + (long long)b * ldq + (h0 + g) * 64 + c8 * 8), qf);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) qf[k] *= sc;
+      float s[R];
+      float mx = -INFINITY;
+#pragma unroll
+      for (int i = 0; i < R; ++i) {
+        const int j = j0 + i * 32 + wv * 8 + kr;
+        float kf[8], d = 0.f;
+        unpack8(kk[i], kf);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) d = fmaf(qf[k], kf[k], d);
+        d += __shfl_xor(d, 1, 64);
+        d += __shfl_xor(d, 2, 64);
+        d += __shfl_xor(d, 4, 64);
+        s[i] = j < n ? d : -INFINITY;
+        mx = fmaxf(mx, s[i]);
+      }
+      mx = wave_max(mx);
+      if (lane == 0) sm[g][wv] = mx;
+      __syncthreads();
+      mx = fmaxf(fmaxf(sm[g][0], sm[g][1]), fmaxf(sm[g][2], sm[g][3]));   // finite: key j0 is valid
+      float o[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, ls = 0.f;
+#pragma unroll
+      for (int i = 0; i < R; ++i) {
+        const int j = j0 + i * 32 + wv * 8 + kr;
+        const float p = j < n ? __builtin_amdgcn_exp2f(s[i] - mx) : 0.f;
+        float vf[8];
+        unpack8(vv[i], vf);
+        ls += p;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) o[k] = fmaf(p, vf[k], o[k]);
+      }
+#pragma unroll
+      for (int sh = 8; sh < 64; sh <<= 1) {
+        ls += __shfl_xor(ls, sh, 64);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) o[k] += __shfl_xor(o[k], sh, 64);
+      }
+      if (lane < 8) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) so[g][wv][c8 * 8 + k] = o[k];
+      }
+      if (lane == 0) ss[g][wv] = ls;
+    }
+    __syncthreads();
+    for (int g = wv; g < ng; g += 4) {   // wave-uniform
+      float* part = ws + ((long long)(b * H + h0 + g) * nch + ch) * ATTN_WS;
+      st_part(part + 2 + lane, ((so[g][0][lane] + so[g][1][lane]) + so[g][2][lane]) + so[g][3][lane]);
+      if (lane == 0) {
+        st_part(part, fmaxf(fmaxf(sm[g][0], sm[g][1]), fmaxf(sm[g][2], sm[g][3])));
+        st_part(part + 1, ((ss[g][0] + ss[g][1]) + ss[g][2]) + ss[g][3]);
+      }
+    }
+  }
+  if (!last_block(cnt + (long long)bk * gridDim.z + blockIdx.z, (unsigned)nch, &sh_last)) return;
+  const int nv = len / C + 1;   // <= nch: len < Lcap
+  for (int g = wv; g < ng; g += 4) {
+    const float* p0 = ws + (long long)(b * H + h0 + g) * nch * ATTN_WS;
+    float M = -INFINITY;
+    for (int c = 0; c < nv; ++c) M = fmaxf(M, ld_part(p0 + c * ATTN_WS));
+    float S = 0.f, O = 0.f;
+    for (int c = 0; c < nv; ++c) {
+      const float w = __builtin_amdgcn_exp2f(ld_part(p0 + c * ATTN_WS) - M);
+      S = fmaf(w, ld_part(p0 + c * ATTN_WS + 1), S);
+      O = fmaf(w, ld_part(p0 + c * ATTN_WS + 2 + lane), O);
+    }
+    out[(long long)b * ldo + (h0 + g) * 64 + lane] = f2bf(O / S);
+  }
+}
+
 // --------------------------------------------------------------------------- n-gram drafter
 // Prompt lookup: one block per sequence over its history tokens[b, 0 .. L], L = lens[b].  For
 // g = min(G, L) .. 1: the suffix of g tokens ending at L is searched at the starts s <= L - g (an
@@ -940,6 +1222,24 @@ KML_API int kml_kv_append(const bf16_t* qkv, int ldq, bf16_t* kc, bf16_t* vc, co
   KML_LAUNCH_CHECK();
 }
 
+// qkv [B * Lq, ldq]: H query | Hkv key | Hkv value heads of 64; kc / vc [B, Hkv, Lcap, 64]; table: fp32
+// [max_pos][64] = cos(32) | sin(32) (kml_rope's).  decode: cache row lens[b] + t, else row t.  rotate: Q heads
+// rotated in place and K heads on their way to the cache; 0 appends an already rotated buffer.
+KML_API int kml_kv_append_rope(bf16_t* qkv, int ldq, bf16_t* kc, bf16_t* vc, const int* lens, const float* table,
+                               int B, int H, int Hkv, int Lq, int Lcap, int max_pos, int decode, int rotate,
+                               hipStream_t s) {
+  if (!qkv || !kc || !vc || B < 1 || H < 1 || Hkv < 1 || Lq < 1 || Lcap < 64 || Lcap % 64 || ldq % 8 ||
+      ldq < (H + 2 * Hkv) * 64 || (((unsigned long long)qkv | (unsigned long long)kc | (unsigned long long)vc) & 15ull))
+    return (int)hipErrorInvalidValue;
+  if (rotate && (!table || max_pos < 1 || ((unsigned long long)table & 15ull))) return (int)hipErrorInvalidValue;
+  if (decode && (Lq > 16 || !lens)) return (int)hipErrorInvalidValue;
+  if (!decode && Lq > Lcap) return (int)hipErrorInvalidValue;
+  const long long total = (long long)B * Lq * (H + 2 * Hkv) * 4;
+  hipLaunchKernelGGL(k_kv_append_rope, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, qkv, ldq, kc, vc, lens,
+                     table, B, H, Hkv, Lq, Lcap, max_pos, decode, rotate);
+  KML_LAUNCH_CHECK();
+}
+
 // keys per chunk of kml_attn_decode (profiles/r12/kv_decode.md has the sweep)
 #define KML_DECODE_CHUNK 256
 
@@ -984,6 +1284,43 @@ KML_API int kml_attn_decode_sweep(int chunk, const bf16_t* q, int ldq, const bf1
   return attn_decode_launch(chunk, q, ldq, kc, vc, lens, ws, cnt, out, ldo, B, H, Lcap, scale, s);
 }
 
+// Query heads a block of kml_attn_decode_gqa serves in turn (larger groups go over blockIdx.z): ATTN_GQ, or
+// one head per block while the grid is small.  The turns of a block are serial (a block-wide maximum
+// each, ~1.6 us a turn), so while one head per block gives at most GQA_SMALL_GRID blocks (two per CU) the
+// heads of a group run side by side and the K/V chunk they share comes from L2; past that the blocks
+// queue anyway and the chunk is loaded once for ATTN_GQ heads.  Same bits either way
+// (profiles/r21/llama_decode.md has both, and 2 and 8 heads per block, which lost).
+constexpr int ATTN_GQ = 4;
+constexpr long long GQA_SMALL_GRID = 512;
+
+// floats of workspace of kml_attn_decode_gqa: the chunk partials of H query heads (the cache has Hkv)
+KML_API long long kml_attn_decode_gqa_ws_floats(int B, int H, int Lcap) {
+  return (long long)B * H * ((Lcap + 63) / 64) * ATTN_WS;
+}
+
+// kml_attn_decode for H query heads over a cache of Hkv K/V heads (H % Hkv == 0): q row b of a [B, ldq] buffer,
+// head h at columns 64h; kc / vc [B, Hkv, Lcap, 64]; ws from kml_attn_decode_gqa_ws_floats; cnt: B*H zeroed tickets
+// (one per (b, K/V head, group of query heads) is used).  Head h: the bits of kml_attn_decode on the cache with
+// its K/V heads repeated H / Hkv times.  heads_per_block: 0 = by the size of the grid, 1 or 4 = that (tuning).
+KML_API int kml_attn_decode_gqa(const bf16_t* q, int ldq, const bf16_t* kc, const bf16_t* vc, const int* lens,
+                                float* ws, unsigned* cnt, bf16_t* out, int ldo, int B, int H, int Hkv, int Lcap,
+                                float scale, int heads_per_block, hipStream_t s) {
+  if (!q || !kc || !vc || !lens || !ws || !cnt || !out || B < 1 || H < 1 || Hkv < 1 || H % Hkv || Lcap < 64 ||
+      Lcap % 64 || ldq % 8 || ldq < H * 64 || ldo < H * 64 || (long long)B * Hkv > 65535 ||
+      (heads_per_block != 0 && heads_per_block != 1 && heads_per_block != ATTN_GQ))
+    return (int)hipErrorInvalidValue;
+  const int G = H / Hkv, nch = (Lcap + KML_DECODE_CHUNK - 1) / KML_DECODE_CHUNK;
+  const int qg = heads_per_block ? heads_per_block : ((long long)nch * B * H <= GQA_SMALL_GRID ? 1 : ATTN_GQ);
+  const dim3 grid((unsigned)nch, (unsigned)(B * Hkv), (unsigned)((G + qg - 1) / qg));
+  if (qg == 1)
+    hipLaunchKernelGGL((k_attn_decode_gqa<KML_DECODE_CHUNK, 1>), grid, dim3(256), 0, s, q, ldq, kc, vc, lens, ws, cnt,
+                       out, ldo, H, Hkv, Lcap, scale);
+  else
+    hipLaunchKernelGGL((k_attn_decode_gqa<KML_DECODE_CHUNK, ATTN_GQ>), grid, dim3(256), 0, s, q, ldq, kc, vc, lens, ws,
+                       cnt, out, ldo, H, Hkv, Lcap, scale);
+  KML_LAUNCH_CHECK();
+}
+
 // K splits kml_gemm_skinny takes for an (N, K) weight by default.  With S > 1 splits the caller
 // provides a workspace of ceil(N / 16) * S * 256 floats and ceil(N / 16) zeroed tickets.
 KML_API int kml_gemm_skinny_splits(int N, int K) {
@@ -1007,6 +1344,33 @@ KML_API int kml_gemm_skinny(const bf16_t* x, int ldx, const bf16_t* w, int ldw, 
   else
     hipLaunchKernelGGL((k_gemm_skinny<16, 4>), grid, dim3(1024), 0, s, x, ldx, w, ldw, bias, y, ldy, M, N, K, p.cps,
                        act, ws, cnt);
+  KML_LAUNCH_CHECK();
+}
+
+// K splits kml_gemm_skinny_glu takes for an [2 I, K] gate_up weight by default.  With S > 1 splits the caller
+// provides a workspace of ceil(I / 16) * S * 512 floats and ceil(I / 16) zeroed tickets.
+KML_API int kml_gemm_skinny_glu_splits(int I, int K) {
+  if (I < 8 || K < 8) return 0;
+  return skinny_plan(I, K, 0).S;
+}
+
+// y[M <= 16][I] = silu(x · w[:I]ᵀ) * (x · w[I:2I]ᵀ); w [2 I, K] row-major, rows ldw apart.
+// splits: 0 = the default plan, > 0 = that many K splits (the tuning sweep)
+KML_API int kml_gemm_skinny_glu(const bf16_t* x, int ldx, const bf16_t* w, int ldw, bf16_t* y, int ldy, int M, int I,
+                                int K, int splits, float* ws, unsigned* cnt, hipStream_t s) {
+  if (!x || !w || !y || M < 1 || M > 16 || I < 8 || I % 8 || K < 8 || K % 8 || ldx % 8 || ldw % 8 || ldx < K ||
+      ldw < K || ldy < I || splits < 0)
+    return (int)hipErrorInvalidValue;
+  const SkinnyPlan p = skinny_plan(I, K, splits);
+  if (p.S > 1 && (!ws || !cnt)) return (int)hipErrorInvalidValue;
+  if (p.S > 65535) return (int)hipErrorInvalidValue;
+  const dim3 grid((unsigned)p.groups, (unsigned)p.S);
+  if (p.big)
+    hipLaunchKernelGGL((k_gemm_skinny_glu<4, 2>), grid, dim3(256), 0, s, x, ldx, w, ldw, y, ldy, M, I, K, p.cps, ws,
+                       cnt);
+  else
+    hipLaunchKernelGGL((k_gemm_skinny_glu<16, 2>), grid, dim3(1024), 0, s, x, ldx, w, ldw, y, ldy, M, I, K, p.cps, ws,
+                       cnt);
   KML_LAUNCH_CHECK();
 }
 

@@ -11,7 +11,6 @@
 namespace {
 
 constexpr int MAXV = 8;   // RMSNorm: up to 8 x (64 lanes x 4) = 2048 columns held in registers
-constexpr float LOG2E_F = 1.4426950408889634f;
 
 __device__ __forceinline__ void unpack4(const uint2 v, float* f) {
   f[0] = lo_bf(v.x); f[1] = hi_bf(v.x); f[2] = lo_bf(v.y); f[3] = hi_bf(v.y);
@@ -253,23 +252,14 @@ __global__ __launch_bounds__(256) void k_rope(bf16_t* __restrict__ qkv, int ld, 
     unpack8(lo, a);
     unpack8(hi, b);
 #pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const float s = sn[k] * sgn;
-      oa[k] = a[k] * cs[k] - b[k] * s;
-      ob[k] = b[k] * cs[k] + a[k] * s;
-    }
+    for (int k = 0; k < 8; ++k) kml_rope_pair(a[k], b[k], cs[k], sn[k] * sgn, oa[k], ob[k]);
     *reinterpret_cast<uint4*>(p) = pack8(oa);
     *reinterpret_cast<uint4*>(p + 32) = pack8(ob);
   }
 }
 
 // ------------------------------------------------------------------------------ SwiGLU
-// sigmoid through one v_exp_f32 and one rcp: exp2(-g log2 e) is +inf for g << 0 (rcp: 0) and 0
-// for g >> 0 (sigmoid 1), so every finite g gives finite values forward and backward.
-__device__ __forceinline__ float sigmoidf_fast(float g) {
-  return __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-g * LOG2E_F));
-}
-
+// (sigmoidf_fast: kml_common.h, shared with the decode step's gated GEMM)
 // gu [T, ldg]: gate in columns [0, I), up in [I, 2I); h [T, I] = silu(gate) * up
 __global__ __launch_bounds__(256) void k_swiglu_fwd(const bf16_t* __restrict__ gu, int ldg, bf16_t* __restrict__ h,
                                                     long long T, int I) {

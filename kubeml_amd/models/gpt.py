@@ -35,7 +35,7 @@ import torch
 import torch.nn as tnn
 from torch.autograd import Function
 
-from ..nn.decode import KVCache, filter_logits, lookup_draft_reference
+from ..nn.decode import DecodeMixin, KVCache, advance_cpu as _advance_cpu, lookup_draft_reference
 from ..nn.flat import grad_storage_of, shadow_of
 from ..nn.modules import Linear, cross_entropy
 from ..nn.transformer import Dropout, LayerNorm, RNGState, SelfAttention, _bf, gather_rows
@@ -189,7 +189,7 @@ class GPT2Model(tnn.Module):
         return x
 
 
-class GPT2LMHeadModel(tnn.Module):
+class GPT2LMHeadModel(DecodeMixin, tnn.Module):
     def __init__(self, vocab=50257, hidden=768, layers=12, heads=12, inter=3072, max_pos=1024, eps=1e-5,
                  dropout=0.1, seed: int = 0, activation: str = "gelu"):
         super().__init__()
@@ -289,9 +289,16 @@ class GPT2LMHeadModel(tnn.Module):
                              classes=self.vocab)
 
     # ------------------------------------------------------------------ KV-cache decoding
-    # Inference only (no autograd, no dropout whatever the module's mode).  GPU: the prompt runs
-    # the training kernels once, every later token one captured step of the decode kernels
-    # (csrc/kernels/decode.hip).  CPU: the same steps in stock torch on a cache of plain tensors.
+    # generate / prefill / decode_step / prefill_logits / decode_logits and the captured replay of
+    # _step are nn.decode.DecodeMixin's; this model supplies the cache, _prefill and _step.
+
+    @property
+    def _decode_table(self):
+        return self.transformer.wte.weight
+
+    @property
+    def _decode_max_pos(self):
+        return self.transformer.max_pos
 
     def _closers(self):
         tr = self.transformer
@@ -381,134 +388,6 @@ class GPT2LMHeadModel(tnn.Module):
         if advance:
             self._pick(cache, logits)
         return logits
-
-    def _pick(self, cache, logits):
-        """The GPU step's last launch: the plain sampler, or the filtered one when the cache has
-        a repetition penalty, top-k or top-p on."""
-        from ..ops import decode as D
-        if cache.filtered:
-            D.decode_sample(logits, self.vocab, cache.ctl, cache.fpar, cache.ipar, cache.next_ids, cache.tokens,
-                            cache.lens, cache.finished, sample=cache.sample, info=cache.info)
-        else:
-            D.decode_advance(logits, self.vocab, cache.ctl, cache.temp, cache.next_ids, cache.tokens, cache.lens,
-                             cache.finished, sample=cache.sample)
-
-    def _replay(self, cache, advance):
-        """The GPU step as one captured graph per (cache, advance, sampling, filtered); captured
-        on first use after an eager warm-up whose effect on the decode state is rolled back.  The
-        filter parameters live in device memory: other values replay the same graph."""
-        key = (bool(advance), bool(cache.sample), bool(cache.filtered))
-        ent = cache._graphs.get(key)
-        if ent is None:
-            from ..engine.step import capture_graph
-            state = [cache.lens, cache.tokens, cache.next_ids, cache.finished, cache.ctl]
-            keep = [t.clone() for t in state]
-            cur = torch.cuda.current_stream()
-            side = torch.cuda.Stream()
-            side.wait_stream(cur)
-            with torch.cuda.stream(side):
-                self._step(cache, advance)   # re-appends the same K / V row: idempotent
-            cur.wait_stream(side)
-            for t, k in zip(state, keep):
-                t.copy_(k)
-            torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with capture_graph(g, capture_error_mode="thread_local"):
-                logits = self._step(cache, advance)
-            ent = cache._graphs[key] = (g, logits)
-        ent[0].replay()
-        return ent[1]
-
-    def decode_step(self, cache):
-        """Feed ``cache.next_ids``, append its keys / values, pick the next token (greedy or
-        Gumbel-max, behind the cache's repetition penalty / top-k / top-p if any is on) and
-        advance ``lens``.  Returns the logits."""
-        if cache.lens.is_cuda:
-            return self._replay(cache, True)
-        return self._step(cache, True)
-
-    def prefill(self, ids, attention_mask, cache):
-        """Run the right-padded prompt, fill the cache and pick each sequence's first new token
-        (``cache.next_ids``, ``cache.tokens[b, prompt_len[b]]``).  Returns the prompt's last logits."""
-        logits = self._prefill(ids, attention_mask, cache)
-        if ids.is_cuda:
-            self._pick(cache, logits)
-        else:
-            _advance_cpu(cache, logits, cache.gen)
-        return logits
-
-    def prefill_logits(self, ids, attention_mask, cache):
-        """Teacher-forced :meth:`prefill`: fills the cache, samples nothing.  ``[B, vocab]``."""
-        return self._prefill(ids, attention_mask, cache)[:, :self.vocab]
-
-    @torch.no_grad()
-    def decode_logits(self, cache, ids):
-        """Teacher-forced :meth:`decode_step`: appends the GIVEN token ``ids[b]`` at the next
-        position of every sequence and returns its logits ``[B, vocab]`` (a new tensor)."""
-        cache.lens.add_(1).clamp_(max=cache.Lcap - 1)
-        cache.next_ids.copy_(ids.reshape(-1))
-        logits = self._replay(cache, False) if cache.lens.is_cuda else self._step(cache, False)
-        return logits[:, :self.vocab].clone()
-
-    @torch.no_grad()
-    def generate(self, ids, attention_mask=None, max_new_tokens=32, temperature=0.0, eos_token_id=None, seed=0,
-                 top_k=0, top_p=1.0, repetition_penalty=1.0, prompt_lookup_num_tokens=0, max_matching_ngram_size=2):
-        """Continue each right-padded prompt by ``max_new_tokens`` tokens: greedy at
-        ``temperature == 0``, else Gumbel-max sampling reproducible from ``seed``.  HF's processor
-        chain runs on the device ahead of the pick: ``repetition_penalty`` (1: off) over the prompt
-        and everything generated, ``top_k`` (0: off; ties at the k-th value stay) and ``top_p`` (1:
-        off; whole classes of equal value).  A sequence that
-        draws ``eos_token_id`` keeps emitting it.  Returns int64 ``[B, Lprompt_max +
-        max_new_tokens]``: row b is its prompt, its new tokens, then ``eos_token_id`` (0 without
-        one) up to the common width.
-
-        ``prompt_lookup_num_tokens = k >= 1`` turns on prompt-lookup speculative decoding (HF's
-        option of that name): an n-gram lookup in each sequence's own history (n-grams of up to
-        ``max_matching_ngram_size`` tokens) drafts ``k`` tokens and one round of ``k + 1`` rows per
-        sequence verifies them (:meth:`draft_lookup`, :meth:`verify_step`), so a round emits 1 to
-        ``k + 1`` tokens per sequence.  The result is, element for element, what the same call
-        returns with ``k = 0``, greedy or sampled; ``last_generate_stats`` then holds ``rounds``,
-        ``accepted`` (draft tokens accepted) and ``tokens`` (tokens the rounds committed), both
-        summed over the sequences.  Limits: ``B <= 4``, ``B * (k + 1) <= 16``, no ``top_k`` /
-        ``top_p`` / ``repetition_penalty``."""
-        tr = self.transformer
-        B, L = ids.shape
-        if max_new_tokens < 1:
-            raise ValueError("max_new_tokens must be at least 1")
-        if B > 16:
-            raise ValueError(f"generate: batch {B} > 16 (the decode GEMMs take at most 16 rows)")
-        plen = torch.full((B,), L, dtype=torch.int64) if attention_mask is None else attention_mask.long().sum(1).cpu()
-        if int(plen.max()) + max_new_tokens > tr.max_pos:
-            raise ValueError(f"generate: prompt {int(plen.max())} + {max_new_tokens} new tokens exceeds max_pos "
-                             f"{tr.max_pos}")
-        k = _draft_count(prompt_lookup_num_tokens, max_matching_ngram_size)
-        if k:
-            return self._generate_lookup(ids, attention_mask, plen, max_new_tokens, temperature, eos_token_id, seed,
-                                         top_k, top_p, repetition_penalty, k, int(max_matching_ngram_size))
-        Lcap = -(-(L + max_new_tokens) // 64) * 64
-        sample = temperature > 0
-        caches = self.__dict__.setdefault("_kml_decode_caches", {})
-        # the captured step holds the addresses of the bf16 shadows: a model moved or flattened
-        # again gets a new cache (and capture)
-        stamp = shadow_of(tr.wte.weight).data_ptr() if ids.is_cuda else 0
-        key = (B, Lcap, sample, ids.device, tr.wte.weight.dtype, stamp)
-        cache = caches.get(key)
-        if cache is None:
-            cache = caches[key] = self.new_cache(B, Lcap, ids.device)
-        cache.reset(seed=seed, temperature=temperature, eos_token_id=eos_token_id, top_k=top_k, top_p=top_p,
-                    repetition_penalty=repetition_penalty)
-        if ids.is_cuda:
-            for p in self.parameters():   # bf16 shadows current before the captured step reads them
-                shadow_of(p)
-        self.prefill(ids, attention_mask, cache)
-        for _ in range(max_new_tokens - 1):
-            self.decode_step(cache)
-        W = L + max_new_tokens
-        out = cache.tokens[:, :W].clone()
-        fill = 0 if eos_token_id is None else int(eos_token_id)
-        end = (plen + max_new_tokens).to(out.device)
-        out.masked_fill_(torch.arange(W, device=out.device)[None] >= end[:, None], fill)
-        return out
 
     # ------------------------------------------------------------------ speculative decoding
     # A verify round feeds q = k + 1 rows per sequence — next_ids[b] and k draft tokens at positions
@@ -675,17 +554,6 @@ class GPT2LMHeadModel(tnn.Module):
         return out
 
 
-def _draft_count(k, max_ngram):
-    """``prompt_lookup_num_tokens`` as an int (None: 0), both options checked."""
-    k = 0 if k is None else k
-    if isinstance(k, bool) or not isinstance(k, (int, float)) or int(k) != k or k < 0:
-        raise ValueError(f"prompt_lookup_num_tokens must be an integer >= 0, got {k!r}")
-    if isinstance(max_ngram, bool) or not isinstance(max_ngram, (int, float)) or int(max_ngram) != max_ngram \
-            or max_ngram < 1:
-        raise ValueError(f"max_matching_ngram_size must be an integer >= 1, got {max_ngram!r}")
-    return int(k)
-
-
 def _verify_commit_cpu(cache):
     """Stock-torch twin of the commit of ``kml_verify_pick`` on a CPU cache whose ``pick`` holds
     the rows' choices: per sequence, pick j lands at ``tokens[b, lens[b] + j + 1]`` while that index
@@ -726,34 +594,6 @@ def _verify_commit_cpu(cache):
     cache.stats[0] += acc
     cache.stats[1] += com
     cache.stats[2] = rem
-
-
-def _advance_cpu(cache, logits, gen):
-    """Stock-torch twin of ``kml_decode_advance`` / ``kml_decode_sample`` on a CPU cache."""
-    eos = int(cache.ctl[2])
-    keep = None
-    if cache.filtered:
-        T, k, p, pen = cache.filters
-        logits, keep = filter_logits(logits, cache.tokens, cache.lens, T, k, p, pen)
-    if cache.sample:
-        u = torch.rand(logits.shape, generator=gen, dtype=torch.float64).clamp_(1e-300, 1.0 - 1e-16)
-        key = logits.double() / float(cache.temp[0]) - torch.log(-torch.log(u))
-        if keep is not None:
-            key = key.masked_fill(~keep, float("-inf"))
-        tok = key.argmax(-1)
-    elif keep is not None:   # the argmax of the penalised row; NaN never wins, an all-NaN row gives 0
-        tok = logits.masked_fill(torch.isnan(logits), float("-inf")).argmax(-1)
-    else:
-        tok = logits.argmax(-1)
-    if eos >= 0:
-        tok = torch.where(cache.finished.bool(), torch.full_like(tok, eos), tok)
-        cache.finished |= (tok == eos).to(torch.int32)
-    cache.next_ids.copy_(tok)
-    nxt = cache.lens.long() + 1
-    ok = nxt < cache.Lcap
-    cache.tokens[torch.arange(cache.B)[ok], nxt[ok]] = tok[ok]
-    cache.lens.copy_(nxt.clamp(max=cache.Lcap - 1).to(torch.int32))
-    cache.ctl[1] += 1
 
 
 def gpt2_small(**kw) -> GPT2LMHeadModel:

@@ -15,8 +15,18 @@
 
 ``state_dict`` / ``load_state_dict`` split and concatenate the fused ``qkv`` / ``gate_up``
 parameters, so HF checkpoints of the family load directly.  Build from a checkpoint's
-``config.json`` with :meth:`LlamaForCausalLM.from_hf_config`.  Training only: there is no
-``generate`` (the decode kernels need RoPE at the cache position and an ``Hkv``-head cache).
+``config.json`` with :meth:`LlamaForCausalLM.from_hf_config`.
+
+Inference: ``generate`` / ``prefill`` / ``decode_step`` / ``prefill_logits`` / ``decode_logits``
+(:class:`~kubeml_amd.nn.decode.DecodeMixin`, GPT-2's) on a :class:`~kubeml_amd.nn.KVCache` of
+``Hkv`` heads.  The prompt runs the training kernels once and appends its rotated keys; every later
+token is one captured step of eight launches a layer (csrc/kernels/decode.hip): ``qkv`` skinny GEMM,
+``kml_kv_append_rope`` (Q rotated in place, K rotated into and V copied to the cache at row
+``lens[b]``), ``kml_attn_decode_gqa`` (a chunk of a K/V head loaded once for its group of query
+heads), ``o_proj``, add + RMSNorm, ``kml_gemm_skinny_glu`` (gate and up GEMM with the SwiGLU in the
+epilogue), ``down_proj``, add + RMSNorm.  Not implemented: speculative decoding
+(``prompt_lookup_num_tokens > 0`` raises ``ValueError``), head dim 128, ``rope_scaling``, paged
+caches.
 """
 from __future__ import annotations
 
@@ -27,9 +37,11 @@ import torch
 import torch.nn as tnn
 from torch.autograd import Function
 
+from ..nn.decode import DecodeMixin, KVCache, advance_cpu
 from ..nn.flat import grad_storage_of, shadow_of
-from ..nn.modules import Linear, cross_entropy
-from ..nn.transformer import RMSNorm, _AttnFn, _bf, attention_reference, rope, rope_table, swiglu
+from ..nn.modules import Linear, _pad_nograd, cross_entropy
+from ..nn.transformer import (RMSNorm, _AttnFn, _bf, attention_reference, gather_rows, rope, rope_reference,
+                              rope_table, swiglu)
 
 
 class _TokEmbFn(Function):
@@ -121,6 +133,21 @@ class LlamaMLP(tnn.Module):
     def forward(self, x):
         return self.down_proj(swiglu(self.gate_up(x)))
 
+    def forward_small(self, x):
+        """Inference-only forward for M <= 16 rows (a decode step): the gate / up GEMM with the
+        SwiGLU in its epilogue (``kml_gemm_skinny_glu``), then ``down_proj.forward_small``.  On the
+        CPU the plain forward."""
+        if not x.is_cuda:
+            return self.forward(x)
+        with torch.no_grad():
+            from ..ops import decode as D
+            gu = self.gate_up
+            x = _bf(x)
+            if x.shape[1] != gu.in_pad:
+                x = _pad_nograd(x, gu.in_pad)
+            h = D.gemm_skinny_glu(x.contiguous(), shadow_of(gu.weight).view(gu.out_pad, gu.in_pad))
+            return self.down_proj.forward_small(h)
+
 
 class LlamaDecoderLayer(tnn.Module):
     """``h += attn(input_layernorm(h))``, ``h += mlp(post_attention_layernorm(h))``.  The layer
@@ -176,7 +203,7 @@ class LlamaModel(tnn.Module):
         return x
 
 
-class LlamaForCausalLM(tnn.Module):
+class LlamaForCausalLM(DecodeMixin, tnn.Module):
     def __init__(self, vocab=32000, hidden=576, layers=30, heads=9, kv_heads=3, inter=1536, max_pos=2048, eps=1e-5,
                  rope_theta=10000.0, tie_word_embeddings=False, seed: int = 0):
         super().__init__()
@@ -260,6 +287,113 @@ class LlamaForCausalLM(tnn.Module):
         logits = self.lm_head(z, keep_pad=True)   # vocab-padded logits used in place
         return cross_entropy(logits, tgt.reshape(-1), ignore_index=-100, return_correct=return_correct,
                              classes=self.vocab)
+
+    # ------------------------------------------------------------------ KV-cache decoding
+    # generate / prefill / decode_step / prefill_logits / decode_logits and the captured replay of
+    # _step are nn.decode.DecodeMixin's; this model supplies the cache, _prefill and _step.
+
+    @property
+    def _decode_table(self):
+        return self.model.embed_tokens.weight
+
+    @property
+    def _decode_max_pos(self):
+        return self.model.max_pos
+
+    def _closers(self):
+        m = self.model
+        return list(zip(m.layers, [lay.input_layernorm for lay in m.layers[1:]] + [m.norm]))
+
+    def new_cache(self, B, Lcap, device=None):
+        m = self.model
+        at = m.layers[0].self_attn
+        p = m.embed_tokens.weight
+        return KVCache(len(m.layers), B, at.heads, Lcap, device or p.device, dtype=p.dtype, kv_heads=at.kv_heads)
+
+    @torch.no_grad()
+    def _prefill(self, ids, attention_mask, cache):
+        """Causal forward over the right-padded prompt; appends every layer's rotated K and its V;
+        leaves ``lens[b] = prompt_len[b] - 1``; returns the logits of each sequence's last prompt
+        token."""
+        m = self.model
+        B, L = ids.shape
+        if B != cache.B or L > cache.Lcap or L > m.max_pos:
+            raise ValueError(f"prompt [{B}, {L}] does not fit the cache ({cache.B} x {cache.Lcap}) / max_pos")
+        if attention_mask is None:
+            plen = torch.full((B,), L, dtype=torch.int64, device=ids.device)
+            bias = None
+        else:
+            plen = attention_mask.long().sum(1)
+            pos = torch.arange(L, device=ids.device)[None]
+            if int(plen.min()) < 1 or not bool(((pos < plen[:, None]) == attention_mask.bool()).all()):
+                raise ValueError("prefill: the prompt must be right-padded with at least one token per sequence")
+            bias = ((1.0 - attention_mask.float()) * -10000.0).reshape(B, L).contiguous()
+        gpu = ids.is_cuda
+        at0 = m.layers[0].self_attn
+        H, Hkv = at0.heads, at0.kv_heads
+        if gpu:
+            from ..ops import decode as D
+            from ..ops import transformer as T
+            e = T.gather_rows(shadow_of(m.embed_tokens.weight), ids.reshape(-1).contiguous())
+        else:
+            e = m.embed_tokens(ids).reshape(B * L, -1)
+            if bias is not None:
+                bias = bias.to(e.dtype)
+        x, s = m.layers[0].input_layernorm.add_norm(e)
+        for i, (lay, norm) in enumerate(self._closers()):
+            at = lay.self_attn
+            qkv = rope(at.qkv(x), m.rope_table, L, H, Hkv)   # the flash kernel reads rotated Q and K
+            if gpu:
+                D.kv_append_rope(qkv, cache.k[i], cache.v[i], L, H, m.rope_table, rotate=False)   # append only
+                ctx = _AttnFn.apply(qkv, B, H, L, bias, None, True, Hkv)
+            else:
+                cache.append_cpu(i, qkv, L, decode=False)
+                ctx = attention_reference(qkv, B, H, L, bias, causal=True, kv_heads=Hkv)
+            x2, s = lay.post_attention_layernorm.add_norm(at.o_proj(ctx), residual=s)
+            x, s = norm.add_norm(lay.mlp(x2), residual=s)
+        rows = torch.arange(B, device=ids.device) * L + plen - 1
+        z = gather_rows(x, rows)
+        cache.lens.copy_((plen - 1).to(torch.int32))
+        cache.tokens.zero_()
+        cache.tokens[:, :L] = ids * (torch.arange(L, device=ids.device)[None] < plen[:, None])
+        cache.finished.zero_()
+        return self.lm_head(z, keep_pad=True)
+
+    @torch.no_grad()
+    def _step(self, cache, advance):
+        """One decode step from ``cache.next_ids`` at position ``lens[b]``: returns the logits
+        ``[B, vocab (padded to 8 on the GPU)]``; ``advance`` also picks the next token."""
+        m = self.model
+        at0 = m.layers[0].self_attn
+        H, Hkv = at0.heads, at0.kv_heads
+        if not cache.lens.is_cuda:
+            pos = cache.lens.long().clamp(0, m.max_pos - 1)
+            x, s = m.layers[0].input_layernorm.add_norm(m.embed_tokens(cache.next_ids))
+            for i, (lay, norm) in enumerate(self._closers()):
+                at = lay.self_attn
+                qkv = rope_reference(at.qkv(x), m.rope_table, 1, H, Hkv, pos=pos)
+                cache.append_cpu(i, qkv, 1, decode=True)
+                x2, s = lay.post_attention_layernorm.add_norm(at.o_proj(cache.attend_cpu(i, qkv)), residual=s)
+                x, s = norm.add_norm(lay.mlp(x2), residual=s)
+            logits = self.lm_head(x)
+            if advance:
+                advance_cpu(cache, logits, cache.gen)
+            return logits
+        from ..ops import decode as D
+        from ..ops import transformer as T
+        e = T.gather_rows(shadow_of(m.embed_tokens.weight), cache.next_ids)
+        x, s = m.layers[0].input_layernorm.add_norm(e)
+        for i, (lay, norm) in enumerate(self._closers()):
+            at = lay.self_attn
+            qkv = at.qkv.forward_small(x)
+            D.kv_append_rope(qkv, cache.k[i], cache.v[i], 1, H, m.rope_table, lens=cache.lens)
+            ctx = D.attn_decode_gqa(qkv, cache.k[i], cache.v[i], cache.lens, H, ws=cache.ws)
+            x2, s = lay.post_attention_layernorm.add_norm(at.o_proj.forward_small(ctx), residual=s)
+            x, s = norm.add_norm(lay.mlp.forward_small(x2), residual=s)
+        logits = self.lm_head.forward_small(x, keep_pad=True)
+        if advance:
+            self._pick(cache, logits)
+        return logits
 
 
 def llama_tiny(**kw) -> LlamaForCausalLM:

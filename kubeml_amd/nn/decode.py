@@ -1,5 +1,6 @@
 """Decode-time state of a decoder LM: the per-layer key / value cache and the per-sequence
-bookkeeping that one captured decode step reads and advances on the device."""
+bookkeeping that one captured decode step reads and advances on the device; and
+:class:`DecodeMixin`, the model-independent half of ``generate`` that the decoder LMs share."""
 from __future__ import annotations
 
 import torch
@@ -91,7 +92,9 @@ class KVCache:
     tokens (rounded up to a multiple of 64), head dim 64.
 
     * ``k[i]``, ``v[i]``: ``[B, H, Lcap, 64]``, head-major — one (b, h) key stream is contiguous
-      128-byte rows.  bf16 and uninitialised on the GPU (rows past ``lens[b]`` are never read);
+      128-byte rows.  ``kv_heads = Hkv`` (grouped-query models; None: ``H``) makes them ``[B, Hkv,
+      Lcap, 64]``: query head h reads K/V head ``h // (H // Hkv)``; the workspace stays sized for
+      the ``H`` query heads.  bf16 and uninitialised on the GPU (rows past ``lens[b]`` are never read);
       zeros of ``dtype`` on the CPU.
     * ``lens`` int32 ``[B]``: index of the newest token of each sequence (its key is row
       ``lens[b]`` once the step has appended it).
@@ -110,14 +113,17 @@ class KVCache:
       partials of ``k + 1`` queries per (sequence, head) (GPU only).
     """
 
-    def __init__(self, layers, B, H, Lcap, device, dtype=None):
+    def __init__(self, layers, B, H, Lcap, device, dtype=None, kv_heads=None):
         device = torch.device(device)
         self.layers, self.B, self.H = int(layers), int(B), int(H)
+        self.Hkv = self.H if kv_heads is None else int(kv_heads)
+        if self.Hkv < 1 or self.H % self.Hkv:
+            raise ValueError(f"KVCache: kv_heads {kv_heads} must divide the {self.H} heads")
         self.Lcap = -(-int(Lcap) // 64) * 64
         self.device = device
         gpu = device.type == "cuda"
         self.dtype = torch.bfloat16 if gpu else (dtype or torch.float32)
-        shape = (self.B, self.H, self.Lcap, 64)
+        shape = (self.B, self.Hkv, self.Lcap, 64)
         make = torch.empty if gpu else torch.zeros
         self.k = [make(shape, dtype=self.dtype, device=device) for _ in range(self.layers)]
         self.v = [make(shape, dtype=self.dtype, device=device) for _ in range(self.layers)]
@@ -133,7 +139,8 @@ class KVCache:
         self.ws = None
         if gpu:
             from ..ops import decode as D
-            self.ws = D.attn_decode_workspace(self.B, self.H, self.Lcap, device)
+            self.ws = (D.attn_decode_workspace if kv_heads is None else D.attn_decode_gqa_workspace)(
+                self.B, self.H, self.Lcap, device)
         self.sample = False   # Gumbel-max sampling at temp[0] instead of the argmax
         self.filtered = False   # a repetition penalty, top-k or top-p is on: the filtered sampler picks
         self.filters = (1.0, 0, 1.0, 1.0)   # host copy: temperature, top_k, top_p, penalty
@@ -203,12 +210,12 @@ class KVCache:
 
     # ------------------------------------------------------------------ CPU path (plain tensors)
     def append_cpu(self, i, qkv, Lq, decode):
-        """K / V thirds of a ``[B*Lq, 3*H*64]`` buffer into layer i: rows 0..Lq-1 (prefill) or
-        rows ``lens[b] + t`` (decode: Lq = 1 in a plain step, the rows of a verify round
-        otherwise); rows at or past Lcap are dropped."""
-        B, H, D = self.B, self.H, self.H * 64
-        k = qkv[:, D:2 * D].reshape(B, Lq, H, 64).permute(0, 2, 1, 3)
-        v = qkv[:, 2 * D:].reshape(B, Lq, H, 64).permute(0, 2, 1, 3)
+        """K / V parts of a ``[B*Lq, (H + 2*Hkv)*64]`` buffer (thirds when ``Hkv == H``) into layer
+        i: rows 0..Lq-1 (prefill) or rows ``lens[b] + t`` (decode: Lq = 1 in a plain step, the rows
+        of a verify round otherwise); rows at or past Lcap are dropped."""
+        B, H, D, E = self.B, self.Hkv, self.H * 64, self.Hkv * 64
+        k = qkv[:, D:D + E].reshape(B, Lq, H, 64).permute(0, 2, 1, 3)
+        v = qkv[:, D + E:].reshape(B, Lq, H, 64).permute(0, 2, 1, 3)
         if not decode:
             n = min(Lq, self.Lcap)
             self.k[i][:, :, :n] = k[:, :, :n]
@@ -222,12 +229,16 @@ class KVCache:
                     self.v[i][b, :, r] = v[b, :, t]
 
     def attend_cpu(self, i, qkv, Lq=1):
-        """softmax(q Kᵀ / 8) V of layer i; q = the first third of qkv ``[B*Lq, 3*H*64]``: row
-        ``b*Lq + t`` sees cache rows ``0 .. lens[b] + t``.  The queries of a sequence are taken one
-        at a time, each with the shapes of the one-query call, so row t has the bits of a plain
-        step at that length."""
+        """softmax(q Kᵀ / 8) V of layer i; q = the first ``H*64`` columns of qkv ``[B*Lq, (H +
+        2*Hkv)*64]``: row ``b*Lq + t`` sees cache rows ``0 .. lens[b] + t``.  The queries of a
+        sequence are taken one at a time, each with the shapes of the one-query call, so row t has
+        the bits of a plain step at that length.  With ``Hkv < H`` every K/V head serves its group
+        of ``H // Hkv`` query heads."""
         B, H = self.B, self.H
-        kt = self.k[i].transpose(-1, -2)
+        kc, vc = self.k[i], self.v[i]
+        if self.Hkv != H:
+            kc, vc = (t.repeat_interleave(H // self.Hkv, 1) for t in (kc, vc))
+        kt = kc.transpose(-1, -2)
         cols = torch.arange(self.Lcap)[None, :]
         q = qkv[:, :H * 64].reshape(B, Lq, H, 1, 64)
         out = []
@@ -235,7 +246,7 @@ class KVCache:
             s = (q[:, t] @ kt) / 8.0                                           # [B, H, 1, Lcap]
             past = cols > (self.lens[:, None].long() + t).clamp(max=self.Lcap - 1)   # [B, Lcap]
             s = s.masked_fill(past[:, None, None, :], float("-inf"))
-            out.append((s.softmax(-1) @ self.v[i]).reshape(B, H * 64))
+            out.append((s.softmax(-1) @ vc).reshape(B, H * 64))
         return out[0] if Lq == 1 else torch.stack(out, 1).reshape(B * Lq, H * 64)
 
     def uniforms_cpu(self, t, shape):
@@ -252,3 +263,193 @@ class KVCache:
         newest = max(self.ublocks, default=0)
         for n in [n for n in self.ublocks if n < below and n != newest]:
             del self.ublocks[n]
+
+
+def draft_count(k, max_ngram):
+    """``prompt_lookup_num_tokens`` as an int (None: 0), both options checked."""
+    k = 0 if k is None else k
+    if isinstance(k, bool) or not isinstance(k, (int, float)) or int(k) != k or k < 0:
+        raise ValueError(f"prompt_lookup_num_tokens must be an integer >= 0, got {k!r}")
+    if isinstance(max_ngram, bool) or not isinstance(max_ngram, (int, float)) or int(max_ngram) != max_ngram \
+            or max_ngram < 1:
+        raise ValueError(f"max_matching_ngram_size must be an integer >= 1, got {max_ngram!r}")
+    return int(k)
+
+
+def advance_cpu(cache, logits, gen):
+    """Stock-torch twin of ``kml_decode_advance`` / ``kml_decode_sample`` on a CPU cache."""
+    eos = int(cache.ctl[2])
+    keep = None
+    if cache.filtered:
+        T, k, p, pen = cache.filters
+        logits, keep = filter_logits(logits, cache.tokens, cache.lens, T, k, p, pen)
+    if cache.sample:
+        u = torch.rand(logits.shape, generator=gen, dtype=torch.float64).clamp_(1e-300, 1.0 - 1e-16)
+        key = logits.double() / float(cache.temp[0]) - torch.log(-torch.log(u))
+        if keep is not None:
+            key = key.masked_fill(~keep, float("-inf"))
+        tok = key.argmax(-1)
+    elif keep is not None:   # the argmax of the penalised row; NaN never wins, an all-NaN row gives 0
+        tok = logits.masked_fill(torch.isnan(logits), float("-inf")).argmax(-1)
+    else:
+        tok = logits.argmax(-1)
+    if eos >= 0:
+        tok = torch.where(cache.finished.bool(), torch.full_like(tok, eos), tok)
+        cache.finished |= (tok == eos).to(torch.int32)
+    cache.next_ids.copy_(tok)
+    nxt = cache.lens.long() + 1
+    ok = nxt < cache.Lcap
+    cache.tokens[torch.arange(cache.B)[ok], nxt[ok]] = tok[ok]
+    cache.lens.copy_(nxt.clamp(max=cache.Lcap - 1).to(torch.int32))
+    cache.ctl[1] += 1
+
+
+class DecodeMixin:
+    """The model-independent half of KV-cache decoding, shared by the decoder LMs.  A model supplies
+
+    * ``vocab``, ``_decode_max_pos`` (positions it can address) and ``_decode_table`` (its token
+      table parameter: the device, dtype and shadow address a captured step is bound to);
+    * ``new_cache(B, Lcap, device)``;
+    * ``_prefill(ids, attention_mask, cache)``: the prompt through the training kernels, every
+      layer's K / V appended, ``lens[b] = prompt_len[b] - 1``, returns the last prompt logits;
+    * ``_step(cache, advance)``: one step from ``cache.next_ids`` at position ``lens[b]``; on the GPU
+      it ends with :meth:`_pick` when ``advance``, on the CPU with :func:`advance_cpu`;
+    * optionally ``_generate_lookup`` (prompt-lookup speculative decoding).
+
+    Inference only (no autograd, no dropout whatever the module's mode).  GPU: the prompt runs the
+    training kernels once, every later token one captured step of the decode kernels
+    (csrc/kernels/decode.hip).  CPU: the same steps in stock torch on a cache of plain tensors."""
+
+    def _pick(self, cache, logits):
+        """The GPU step's last launch: the plain sampler, or the filtered one when the cache has
+        a repetition penalty, top-k or top-p on."""
+        from ..ops import decode as D
+        if cache.filtered:
+            D.decode_sample(logits, self.vocab, cache.ctl, cache.fpar, cache.ipar, cache.next_ids, cache.tokens,
+                            cache.lens, cache.finished, sample=cache.sample, info=cache.info)
+        else:
+            D.decode_advance(logits, self.vocab, cache.ctl, cache.temp, cache.next_ids, cache.tokens, cache.lens,
+                             cache.finished, sample=cache.sample)
+
+    def _replay(self, cache, advance):
+        """The GPU step as one captured graph per (cache, advance, sampling, filtered); captured
+        on first use after an eager warm-up whose effect on the decode state is rolled back.  The
+        filter parameters live in device memory: other values replay the same graph."""
+        key = (bool(advance), bool(cache.sample), bool(cache.filtered))
+        ent = cache._graphs.get(key)
+        if ent is None:
+            from ..engine.step import capture_graph
+            state = [cache.lens, cache.tokens, cache.next_ids, cache.finished, cache.ctl]
+            keep = [t.clone() for t in state]
+            cur = torch.cuda.current_stream()
+            side = torch.cuda.Stream()
+            side.wait_stream(cur)
+            with torch.cuda.stream(side):
+                self._step(cache, advance)   # re-appends the same K / V row: idempotent
+            cur.wait_stream(side)
+            for t, k in zip(state, keep):
+                t.copy_(k)
+            torch.cuda.synchronize()
+            g = torch.cuda.CUDAGraph()
+            with capture_graph(g, capture_error_mode="thread_local"):
+                logits = self._step(cache, advance)
+            ent = cache._graphs[key] = (g, logits)
+        ent[0].replay()
+        return ent[1]
+
+    def decode_step(self, cache):
+        """Feed ``cache.next_ids``, append its keys / values, pick the next token (greedy or
+        Gumbel-max, behind the cache's repetition penalty / top-k / top-p if any is on) and
+        advance ``lens``.  Returns the logits."""
+        if cache.lens.is_cuda:
+            return self._replay(cache, True)
+        return self._step(cache, True)
+
+    def prefill(self, ids, attention_mask, cache):
+        """Run the right-padded prompt, fill the cache and pick each sequence's first new token
+        (``cache.next_ids``, ``cache.tokens[b, prompt_len[b]]``).  Returns the prompt's last logits."""
+        logits = self._prefill(ids, attention_mask, cache)
+        if ids.is_cuda:
+            self._pick(cache, logits)
+        else:
+            advance_cpu(cache, logits, cache.gen)
+        return logits
+
+    def prefill_logits(self, ids, attention_mask, cache):
+        """Teacher-forced :meth:`prefill`: fills the cache, samples nothing.  ``[B, vocab]``."""
+        return self._prefill(ids, attention_mask, cache)[:, :self.vocab]
+
+    @torch.no_grad()
+    def decode_logits(self, cache, ids):
+        """Teacher-forced :meth:`decode_step`: appends the GIVEN token ``ids[b]`` at the next
+        position of every sequence and returns its logits ``[B, vocab]`` (a new tensor)."""
+        cache.lens.add_(1).clamp_(max=cache.Lcap - 1)
+        cache.next_ids.copy_(ids.reshape(-1))
+        logits = self._replay(cache, False) if cache.lens.is_cuda else self._step(cache, False)
+        return logits[:, :self.vocab].clone()
+
+    def _generate_lookup(self, *args):
+        raise ValueError(f"generate: prompt_lookup_num_tokens > 0 (speculative decoding) is not implemented for "
+                         f"{type(self).__name__}")
+
+    @torch.no_grad()
+    def generate(self, ids, attention_mask=None, max_new_tokens=32, temperature=0.0, eos_token_id=None, seed=0,
+                 top_k=0, top_p=1.0, repetition_penalty=1.0, prompt_lookup_num_tokens=0, max_matching_ngram_size=2):
+        """Continue each right-padded prompt by ``max_new_tokens`` tokens: greedy at
+        ``temperature == 0``, else Gumbel-max sampling reproducible from ``seed``.  HF's processor
+        chain runs on the device ahead of the pick: ``repetition_penalty`` (1: off) over the prompt
+        and everything generated, ``top_k`` (0: off; ties at the k-th value stay) and ``top_p`` (1:
+        off; whole classes of equal value).  A sequence that
+        draws ``eos_token_id`` keeps emitting it.  Returns int64 ``[B, Lprompt_max +
+        max_new_tokens]``: row b is its prompt, its new tokens, then ``eos_token_id`` (0 without
+        one) up to the common width.
+
+        ``prompt_lookup_num_tokens = k >= 1`` turns on prompt-lookup speculative decoding (HF's
+        option of that name) on the models that implement it (GPT-2; the others raise
+        ``ValueError``): an n-gram lookup in each sequence's own history (n-grams of up to
+        ``max_matching_ngram_size`` tokens) drafts ``k`` tokens and one round of ``k + 1`` rows per
+        sequence verifies them (``draft_lookup``, ``verify_step``), so a round emits 1 to
+        ``k + 1`` tokens per sequence.  The result is, element for element, what the same call
+        returns with ``k = 0``, greedy or sampled; ``last_generate_stats`` then holds ``rounds``,
+        ``accepted`` (draft tokens accepted) and ``tokens`` (tokens the rounds committed), both
+        summed over the sequences.  Limits: ``B <= 4``, ``B * (k + 1) <= 16``, no ``top_k`` /
+        ``top_p`` / ``repetition_penalty``."""
+        from .flat import shadow_of
+        table, max_pos = self._decode_table, self._decode_max_pos
+        B, L = ids.shape
+        if max_new_tokens < 1:
+            raise ValueError("max_new_tokens must be at least 1")
+        if B > 16:
+            raise ValueError(f"generate: batch {B} > 16 (the decode GEMMs take at most 16 rows)")
+        plen = torch.full((B,), L, dtype=torch.int64) if attention_mask is None else attention_mask.long().sum(1).cpu()
+        if int(plen.max()) + max_new_tokens > max_pos:
+            raise ValueError(f"generate: prompt {int(plen.max())} + {max_new_tokens} new tokens exceeds max_pos "
+                             f"{max_pos}")
+        k = draft_count(prompt_lookup_num_tokens, max_matching_ngram_size)
+        if k:
+            return self._generate_lookup(ids, attention_mask, plen, max_new_tokens, temperature, eos_token_id, seed,
+                                         top_k, top_p, repetition_penalty, k, int(max_matching_ngram_size))
+        Lcap = -(-(L + max_new_tokens) // 64) * 64
+        sample = temperature > 0
+        caches = self.__dict__.setdefault("_kml_decode_caches", {})
+        # the captured step holds the addresses of the bf16 shadows: a model moved or flattened
+        # again gets a new cache (and capture)
+        stamp = shadow_of(table).data_ptr() if ids.is_cuda else 0
+        key = (B, Lcap, sample, ids.device, table.dtype, stamp)
+        cache = caches.get(key)
+        if cache is None:
+            cache = caches[key] = self.new_cache(B, Lcap, ids.device)
+        cache.reset(seed=seed, temperature=temperature, eos_token_id=eos_token_id, top_k=top_k, top_p=top_p,
+                    repetition_penalty=repetition_penalty)
+        if ids.is_cuda:
+            for p in self.parameters():   # bf16 shadows current before the captured step reads them
+                shadow_of(p)
+        self.prefill(ids, attention_mask, cache)
+        for _ in range(max_new_tokens - 1):
+            self.decode_step(cache)
+        W = L + max_new_tokens
+        out = cache.tokens[:, :W].clone()
+        fill = 0 if eos_token_id is None else int(eos_token_id)
+        end = (plen + max_new_tokens).to(out.device)
+        out.masked_fill_(torch.arange(W, device=out.device)[None] >= end[:, None], fill)
+        return out

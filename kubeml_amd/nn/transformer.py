@@ -437,12 +437,14 @@ def rope_table(max_pos, theta=10000.0, device=None):
     return t if device is None else t.to(device)
 
 
-def rope_reference(qkv, table, L, H, kv_heads):
+def rope_reference(qkv, table, L, H, kv_heads, pos=None):
     """Stock-torch rotary embedding of a fused ``[B*L, (H + 2 Hkv)*64]`` buffer (HF ``rotate_half``:
-    element i < 32 of a head pairs with i + 32); table: :func:`rope_table`."""
+    element i < 32 of a head pairs with i + 32); table: :func:`rope_table`.  ``pos``: the position
+    of every row (a decode step's rows sit at their sequences' lengths) instead of ``row % L``."""
     T_ = qkv.shape[0]
     n = (H + kv_heads) * 64
-    pos = torch.arange(T_, device=qkv.device) % L
+    if pos is None:
+        pos = torch.arange(T_, device=qkv.device) % L
     tb = table.to(qkv.dtype)[pos]
     c, s = tb[:, None, :32], tb[:, None, 32:]
     x = qkv[:, :n].reshape(T_, H + kv_heads, 64)

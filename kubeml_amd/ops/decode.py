@@ -2,7 +2,9 @@
 attention over the cache, the skinny (M <= 16) GEMM, the embedding at the device lengths and
 the next-token choice (plain, or behind a repetition penalty, top-k and top-p); and the verify
 round of speculative decoding: multi-row embedding and append, multi-query attention, the n-gram
-drafter, pick and commit.
+drafter, pick and commit; and what a Llama-style decoder needs instead: the append that rotates Q and
+K (RoPE at the cache position) into a cache of ``Hkv`` heads, grouped-query attention over that
+cache, and the skinny GEMM with the SwiGLU gate in its epilogue.
 
 Everything a step needs that changes per token — sequence lengths, seed / step, temperature,
 eos, the sampling filters — is read from device memory, so one captured step replays for every token.  All launches
@@ -137,6 +139,108 @@ def gemm_skinny(x, w, bias=None, act=None, out=None, splits=None):
     HIP.call("kml_gemm_skinny", "p i p i p p i i i i i i p p s", _p(x), x.stride(0), _p(w), w.stride(0), _p(bias),
              _p(out), out.stride(0), M, N, K, _SKINNY_ACT[act], 0 if splits is None else S, _p(ws), _p(cnt),
              _s())
+    return out
+
+
+# ------------------------------------------------------------------ Llama-style decoders
+def _chk_gqa(kc, vc, H):
+    B, Hkv, Lcap = _chk_cache(kc, vc)
+    if int(H) != H or H < Hkv or H % Hkv:
+        raise ValueError(f"{H} query heads over a cache of {Hkv} K/V heads: H must be a multiple of Hkv")
+    return B, int(H), Hkv, Lcap
+
+
+def kv_append_rope(qkv, kc, vc, Lq, H, table, lens=None, rotate=True):
+    """The append of a grouped-query model with rotary embedding, one launch.  ``qkv``: the fused
+    ``[B*Lq, (H + 2*Hkv)*64]`` projection (H query | Hkv key | Hkv value heads); ``kc, vc [B, Hkv,
+    Lcap, 64]``; ``table``: fp32 ``[max_pos, 64]`` from :func:`kubeml_amd.nn.transformer.rope_table`.
+    Row t of sequence b goes to cache row ``r = t`` (``lens`` None: prefill) or ``r = lens[b] + t``
+    (``Lq <= 16``).  The Q heads are rotated in place and the K heads on their way into the cache, at
+    position ``r`` clamped to the table, with the bits of ``kml_rope``; V is copied.  Rows outside
+    ``[0, Lcap)`` are dropped.  ``rotate=False`` only appends (a buffer ``rope_`` has rotated)."""
+    B, H, Hkv, Lcap = _chk_gqa(kc, vc, H)
+    _chk_view(qkv, "qkv")
+    if qkv.shape[0] != B * Lq or qkv.shape[1] != (H + 2 * Hkv) * 64:
+        raise ValueError(f"qkv: expected [{B * Lq}, {(H + 2 * Hkv) * 64}], got {tuple(qkv.shape)}")
+    if lens is not None:
+        if not 1 <= Lq <= 16:
+            raise ValueError("kv_append_rope: decode mode appends 1..16 rows per sequence")
+        _chk_lens(lens, B)
+    elif Lq > Lcap:
+        raise ValueError(f"kv_append_rope: {Lq} prompt rows do not fit a cache of {Lcap}")
+    _chk(table, F32, "table", ndim=2)
+    if table.shape[1] != 64 or not table.is_contiguous():
+        raise ValueError(f"table: expected a contiguous [max_pos, 64] fp32 tensor, got {tuple(table.shape)}")
+    HIP.call("kml_kv_append_rope", "p i p p p p i i i i i i i i s", _p(qkv), qkv.stride(0), _p(kc), _p(vc), _p(lens),
+             _p(table), B, H, Hkv, Lq, Lcap, table.shape[0], int(lens is not None), int(bool(rotate)), _s())
+
+
+def attn_decode_gqa_workspace(B, H, Lcap, device):
+    """fp32 workspace for the chunk partials of ``H`` query heads (whatever the cache's ``Hkv``)."""
+    return torch.empty(int(HIP.raw("kml_attn_decode_gqa_ws_floats", B, H, Lcap)), dtype=F32, device=device)
+
+
+def attn_decode_gqa(q, kc, vc, lens, H, ws=None, out=None, scale=None, heads_per_block=None):
+    """:func:`attn_decode` for ``H`` query heads over a cache of ``Hkv`` K/V heads ``kc, vc [B, Hkv,
+    Lcap, 64]``: query head h reads K/V head ``h // (H // Hkv)``.  Each chunk of a K/V head is loaded
+    once for its whole group of query heads.  Head h of the result is bit-identical to
+    :func:`attn_decode` on the cache with its heads repeat-interleaved ``H // Hkv`` times.
+    q: ``[B, >= H*64]`` bf16 view.  Returns ``[B, H*64]`` bf16.  ``heads_per_block``: 1 or 4 query
+    heads of a group per block instead of the kernel's choice by grid size (same bits; tuning only)."""
+    B, H, Hkv, Lcap = _chk_gqa(kc, vc, H)
+    if heads_per_block not in (None, 1, 4):
+        raise ValueError("heads_per_block must be 1 or 4")
+    _chk_view(q, "q")
+    if q.shape[0] != B or q.shape[1] < H * 64:
+        raise ValueError(f"q: expected a [{B}, >= {H * 64}] view, got {tuple(q.shape)}")
+    _chk_lens(lens, B)
+    need = int(HIP.raw("kml_attn_decode_gqa_ws_floats", B, H, Lcap))
+    if ws is None:
+        ws = torch.empty(need, dtype=F32, device=q.device)
+    _chk(ws, F32, "ws")
+    if ws.numel() < need:
+        raise ValueError(f"ws: {ws.numel()} floats, {H} query heads on this cache need {need}")
+    if out is None:
+        out = torch.empty((B, H * 64), dtype=BF16, device=q.device)
+    _chk_view(out, "out")
+    if out.shape != (B, H * 64):
+        raise ValueError(f"out: expected [{B}, {H * 64}], got {tuple(out.shape)}")
+    scale = 1.0 / math.sqrt(64) if scale is None else scale
+    cnt = _COUNTERS.take(q.device, B * H)
+    HIP.call("kml_attn_decode_gqa", "p i p p p p p p i i i i i f i s", _p(q), q.stride(0), _p(kc), _p(vc), _p(lens),
+             _p(ws), _p(cnt), _p(out), out.stride(0), B, H, Hkv, Lcap, float(scale), int(heads_per_block or 0), _s())
+    return out
+
+
+def gemm_skinny_glu(x, w, out=None, splits=None):
+    """h[M, I] = silu(x @ w[:I]ᵀ) * (x @ w[I:]ᵀ) for M <= 16 and the fused ``gate_up`` weight
+    ``w [2*I, K]`` (gate rows first): one launch, every weight byte read once, the gate applied in
+    fp32 to the fp32 sums and the product rounded once to bf16.  x, w and out may be row-major views
+    with a row stride that is a multiple of 8.  Row m of the result does not depend on M or on the
+    other rows.  ``splits``: another K split than the kernel's plan for (I, K) (the tuning sweep)."""
+    _chk_view(x, "x")
+    _chk_view(w, "w")
+    M, K = x.shape
+    if not 1 <= M <= 16:
+        raise ValueError(f"gemm_skinny_glu: M = {M} rows; the skinny kernel takes 1..16")
+    if w.shape[1] != K or K % 8 or K < 8 or w.shape[0] % 16 or w.shape[0] < 16:
+        raise ValueError(f"gemm_skinny_glu: x {tuple(x.shape)} vs w {tuple(w.shape)} (w [2 I, K], I and K "
+                         "multiples of 8)")
+    I = w.shape[0] // 2
+    if out is None:
+        out = torch.empty((M, I), dtype=BF16, device=x.device)
+    if out.dtype != BF16 or not out.is_cuda or out.dim() != 2 or out.stride(1) != 1 or out.shape != (M, I):
+        raise ValueError(f"out: expected a row-major bf16 [{M}, {I}] GPU view")
+    S = int(HIP.raw("kml_gemm_skinny_glu_splits", I, K)) if splits is None else int(splits)
+    if S < 1:
+        raise ValueError(f"gemm_skinny_glu: no plan for I = {I}, K = {K}" if splits is None else "splits must be >= 1")
+    ws = cnt = None
+    if S > 1:
+        groups = -(-I // 16)
+        ws = torch.empty(groups * S * 512, dtype=F32, device=x.device)
+        cnt = _COUNTERS.take(x.device, groups)
+    HIP.call("kml_gemm_skinny_glu", "p i p i p i i i i i p p s", _p(x), x.stride(0), _p(w), w.stride(0), _p(out),
+             out.stride(0), M, I, K, 0 if splits is None else S, _p(ws), _p(cnt), _s())
     return out
 
 
