@@ -79,9 +79,10 @@ __device__ __forceinline__ float sigmoidf_fast(float g) {
   return __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-g * 1.4426950408889634f));
 }
 
-// One pair of the rotary embedding (HF rotate_half: a = element i < 32 of a head, b = element
-// i + 32): (a, b) -> (a c - b s, b c + a s).  One definition for kml_rope and the decode append,
-// so a key rotated by either has the same bits.
+// One pair of the rotary embedding (HF rotate_half: a = element i of a head's first half, b =
+// element i of its second half — i + 32 at head dim 64, i + 64 at 128): (a, b) -> (a c - b s,
+// b c + a s).  One definition for kml_rope, kml_rope128 and the decode append, so a key rotated
+// by any of them has the same bits.
 __device__ __forceinline__ void kml_rope_pair(float a, float b, float c, float s, float& oa, float& ob) {
   oa = a * c - b * s;
   ob = b * c + a * s;

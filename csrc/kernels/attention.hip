@@ -41,33 +41,13 @@
 // conflict-free for both the row-fragment (ds_read_b128) and transpose reads.
 // Layout: token-major activations [B*L, ld] with head h at column offset 64 h, so the
 // fused QKV projection output / dQKV gradient buffers are used in place.
-#include "kml_common.h"
+#include "kml_attn.h"
 
 #include <cstdio>
 #include <cstdlib>
 #include <type_traits>
 
 namespace {
-
-typedef __attribute__((ext_vector_type(4))) short v4s_t;
-constexpr float LOG2E = 1.4426950408889634f;
-
-struct AttnArgs {
-  const bf16_t* q; const bf16_t* k; const bf16_t* v; const bf16_t* o; const bf16_t* dout;
-  bf16_t* out; bf16_t* dq; bf16_t* dk; bf16_t* dv;
-  float* lse;          // [B*H][L] base-2 log-sum-exp of scaled scores
-  float* dsum;         // [B*H][L] D = rowsum(dO * O)
-  const float* bias;   // [B][L] additive key bias (natural-log units) or null
-  int ldq, ldk, ldv, ldo, lddo, ldout, lddq, lddk, lddv;
-  int B, H, L;
-  float scale;         // softmax scale (1/sqrt(64))
-  const float* ctr;    // [seed, step] (device) for attention dropout, or null
-  unsigned salt;
-  float pdrop;         // dropout probability (0: off)
-  int xcd;             // XCD-aware block order (attn_blk); 0: plain grid order (A/B switch)
-  unsigned char* keep; // dropout keep bits written by the forward, read by the backward (Drop), or null
-  int G;               // grouped-query attention: query heads per K/V head (H = Hkv * G); 1: one K/V head each
-};
 
 __device__ __forceinline__ unsigned ahash(unsigned a, unsigned b, unsigned c) {
   unsigned h = a * 0x9E3779B1u ^ (b + 0x7F4A7C15u) * 0x85EBCA77u ^ c * 0xC2B2AE3Du;
@@ -137,34 +117,6 @@ __device__ __forceinline__ float fmask(float x, int m) { return __int_as_float(_
 
 __device__ __forceinline__ int swz(int r, int c) { return r * 128 + ((c ^ (r & 7)) << 4); }
 
-// XCD-aware block order.  Blocks are dealt round-robin over the 8 XCDs (b and b + 8 share
-// one), so with the plain (tile, b*h) grid the 8 tiles of one head land on 8 different L2s
-// and each XCD fetches that head's K/V (or Q/dO) again.  Renumbered so each XCD runs a
-// contiguous range of ids, tile fastest: the tiles of one head share one L2.
-//
-// GROUP (grouped-query forward / dQ, grid.y = B * H): the G query heads of a K/V head read the
-// same K/V tiles.  Their ids stay inside one XCD's contiguous range (bh = kvbh * G + hg), and
-// within the group the head runs fastest and the tile next: id = (kvbh * gx + xt) * G + hg, so the
-// G blocks of one (K/V head, tile) are dispatched back to back on that XCD and walk the same K/V
-// lines of its L2 together (causal: they also carry the same amount of work).
-template <bool GROUP = false>
-__device__ __forceinline__ void attn_blk(const AttnArgs& a, int& xt, int& bh) {
-  const int gx = (int)gridDim.x, nwg = gx * (int)gridDim.y;
-  const int lin = (int)blockIdx.y * gx + (int)blockIdx.x;
-  if (!a.xcd) { xt = (int)blockIdx.x; bh = (int)blockIdx.y; return; }
-  const int q = nwg >> 3, r = nwg & 7, x = lin & 7, k = lin >> 3;
-  const int id = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + k;
-  if constexpr (GROUP) {
-    const int t = id / a.G, hg = id - t * a.G;
-    const int kvbh = t / gx;
-    xt = t - kvbh * gx;
-    bh = kvbh * a.G + hg;
-  } else {
-    bh = id / gx;
-    xt = id - bh * gx;
-  }
-}
-
 struct TileRegs { uint4 v[2]; };
 
 __device__ __forceinline__ void tile_load(TileRegs& R, const bf16_t* base, int ld, int row0, int L, int tid) {
@@ -199,34 +151,6 @@ __device__ __forceinline__ bf16x8_t frag_tr(const char* lds, int col0, int ks, i
   v4s_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4s_t*)(p1));
   bf16x8_t f = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
   return f;
-}
-
-// bf16 operand from 8 accumulator values of tiles 2ks, 2ks+1 (the permuted k order)
-// (v_cvt_pk_bf16_f32: round-to-nearest-even, NaN stays NaN — one instruction per pair)
-typedef __bf16 bf16x2_hw __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned cvt2(float a, float b) {
-  return __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2_t{a, b}), bf16x2_hw));
-}
-__device__ __forceinline__ bf16x8_t pack_p(const f32x4_t& t0, const f32x4_t& t1) {
-  typedef __attribute__((ext_vector_type(4))) unsigned u32x4_t;
-  const u32x4_t u = {cvt2(t0[0], t0[1]), cvt2(t0[2], t0[3]), cvt2(t1[0], t1[1]), cvt2(t1[2], t1[3])};
-  return __builtin_bit_cast(bf16x8_t, u);
-}
-__device__ __forceinline__ float fexp2(float x) { return __builtin_amdgcn_exp2f(x); }  // v_exp_f32
-
-__device__ __forceinline__ bf16x8_t load_frag_g(const bf16_t* row_ptr, int ks, int g, bool ok) {
-  if (!ok) { bf16x8_t z = {0, 0, 0, 0, 0, 0, 0, 0}; return z; }
-  return *reinterpret_cast<const bf16x8_t*>(row_ptr + 32 * ks + 8 * g);
-}
-
-#define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16((a), (b), (c), 0, 0, 0)
-
-__device__ __forceinline__ void store4(bf16_t* p, const f32x4_t& v, float s) {
-  uint2 w;
-  w.x = pack_bf2(v[0] * s, v[1] * s);
-  w.y = pack_bf2(v[2] * s, v[3] * s);
-  *reinterpret_cast<uint2*>(p) = w;
 }
 
 // ------------------------------------------------------------------------------ forward
@@ -698,8 +622,6 @@ template <int OCC, int DM, bool BIAS, bool CAUSAL>
 __global__ __launch_bounds__(256, OCC) void k_attn_gqa_bwd_dkv(AttnArgs a) {
   attn_bwd_dkv_body<DM, BIAS, CAUSAL, true>(a);
 }
-
-bool aligned16(const void* p) { return (((unsigned long long)p) & 15ull) == 0; }
 
 }  // namespace
 

@@ -231,21 +231,25 @@ int rms_bwd_blocks(long long M, int* rpb) {
 // pairs with i + 32; (a, b) -> (a c - b s, b c + a s), c / s = cos / sin(pos theta^(-i/32)) read
 // from the fp32 table [max_pos][cos(32) | sin(32)]; pos = row % L.  Backward: s -> -s, the
 // transpose rotation, on dQ / dK.  A thread owns 8 pairs: 16 bytes from each half of a head.
+// HALF: half the head width — 32 as described, or 64 for head dim 128 (pairs i and i + 64, table
+// rows cos(64) | sin(64), f_i = theta^(-i/64)).
+template <int HALF>
 __global__ __launch_bounds__(256) void k_rope(bf16_t* __restrict__ qkv, int ld, const float* __restrict__ table,
                                               long long T, int L, int heads, float sgn) {
-  const long long n = T * heads * 4;
+  constexpr int CH = HALF / 8;   // 8-pair chunks of a head
+  const long long n = T * heads * CH;
   for (long long i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-    const int c = (int)(i & 3);
-    const long long rh = i >> 2;
+    const int c = (int)(i % CH);
+    const long long rh = i / CH;
     const long long row = rh / heads;
     const int head = (int)(rh - row * heads);
     const int pos = (int)(row % L);
-    bf16_t* p = qkv + row * ld + head * 64 + c * 8;
-    const float* tb = table + (long long)pos * 64 + c * 8;
+    bf16_t* p = qkv + row * ld + head * (2 * HALF) + c * 8;
+    const float* tb = table + (long long)pos * (2 * HALF) + c * 8;
     const uint4 lo = *reinterpret_cast<const uint4*>(p);
-    const uint4 hi = *reinterpret_cast<const uint4*>(p + 32);
+    const uint4 hi = *reinterpret_cast<const uint4*>(p + HALF);
     const float4 c0 = *reinterpret_cast<const float4*>(tb), c1 = *reinterpret_cast<const float4*>(tb + 4);
-    const float4 s0 = *reinterpret_cast<const float4*>(tb + 32), s1 = *reinterpret_cast<const float4*>(tb + 36);
+    const float4 s0 = *reinterpret_cast<const float4*>(tb + HALF), s1 = *reinterpret_cast<const float4*>(tb + HALF + 4);
     const float cs[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w};
     const float sn[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
     float a[8], b[8], oa[8], ob[8];
@@ -254,7 +258,7 @@ __global__ __launch_bounds__(256) void k_rope(bf16_t* __restrict__ qkv, int ld, 
 #pragma unroll
     for (int k = 0; k < 8; ++k) kml_rope_pair(a[k], b[k], cs[k], sn[k] * sgn, oa[k], ob[k]);
     *reinterpret_cast<uint4*>(p) = pack8(oa);
-    *reinterpret_cast<uint4*>(p + 32) = pack8(ob);
+    *reinterpret_cast<uint4*>(p + HALF) = pack8(ob);
   }
 }
 
@@ -302,6 +306,18 @@ __global__ __launch_bounds__(256) void k_swiglu_bwd(const bf16_t* __restrict__ d
 
 bool al16(const void* p) { return (((unsigned long long)p) & 15ull) == 0; }
 
+template <int HALF>
+int rope_launch(bf16_t* qkv, int ld, const float* table, long long T, int L, int H, int Hkv, int max_pos,
+                int backward, hipStream_t s) {
+  if (T <= 0 || L <= 0 || T % L || L > max_pos || H <= 0 || Hkv <= 0 || ld % 8 ||
+      ld < (H + 2 * Hkv) * 2 * HALF || !al16(qkv) || !al16(table))
+    return (int)hipErrorInvalidValue;
+  const int heads = H + Hkv;
+  hipLaunchKernelGGL(k_rope<HALF>, dim3(kml_stream_grid(T * heads * (HALF / 8), 256)), dim3(256), 0, s, qkv, ld,
+                     table, T, L, heads, backward ? -1.f : 1.f);
+  KML_LAUNCH_CHECK();
+}
+
 }  // namespace
 
 // y = RMSNorm(x [+ res]) * gamma over rows of N bf16; sum_out (optional) = x + res; rstd fp32 [M]
@@ -347,13 +363,13 @@ KML_API int kml_rmsnorm_bwd(const bf16_t* dy, const bf16_t* sin_, const float* r
 // fp32 [max_pos][64] = cos(32) | sin(32); backward != 0: the transpose rotation (for dQ / dK)
 KML_API int kml_rope(bf16_t* qkv, int ld, const float* table, long long T, int L, int H, int Hkv, int max_pos,
                      int backward, hipStream_t s) {
-  if (T <= 0 || L <= 0 || T % L || L > max_pos || H <= 0 || Hkv <= 0 || ld % 8 || ld < (H + 2 * Hkv) * 64 ||
-      !al16(qkv) || !al16(table))
-    return (int)hipErrorInvalidValue;
-  const int heads = H + Hkv;
-  hipLaunchKernelGGL(k_rope, dim3(kml_stream_grid(T * heads * 4, 256)), dim3(256), 0, s, qkv, ld, table, T, L, heads,
-                     backward ? -1.f : 1.f);
-  KML_LAUNCH_CHECK();
+  return rope_launch<32>(qkv, ld, table, T, L, H, Hkv, max_pos, backward, s);
+}
+
+// the same on heads of 128 columns: pairs i and i + 64, table fp32 [max_pos][128] = cos(64) | sin(64)
+KML_API int kml_rope128(bf16_t* qkv, int ld, const float* table, long long T, int L, int H, int Hkv, int max_pos,
+                        int backward, hipStream_t s) {
+  return rope_launch<64>(qkv, ld, table, T, L, H, Hkv, max_pos, backward, s);
 }
 
 // h [T, I] = silu(gu[:, :I]) * gu[:, I:2I]; gu rows ldg apart

@@ -1,12 +1,13 @@
 """Llama-style decoder-only language model (HuggingFace ``LlamaForCausalLM`` architecture and
 ``state_dict`` names: ``model.embed_tokens.weight``, ``model.layers.{i}.self_attn.q_proj.weight``,
-..., ``lm_head.weight``) on the MI355X layers, head dim 64:
+..., ``lm_head.weight``) on the MI355X layers, head dim 64 or 128:
 
 * RMSNorm with the pre-norm residual stream carried inside its launches — a chain of
   :meth:`RMSNorm.add_norm`, as ``GPT2Model`` chains ``LayerNorm.add_norm`` (csrc/kernels/llama.hip);
-* one fused ``qkv`` projection ``[(H + 2 Hkv) * 64, hidden]`` without bias (head dim 64, whatever
-  ``hidden / heads`` is), rotary position embedding in place on its output (``kml_rope``),
-  grouped-query causal flash attention (``kml_attn_gqa_fwd / _bwd``: ``Hkv`` K/V heads shared by
+* one fused ``qkv`` projection ``[(H + 2 Hkv) * d, hidden]`` without bias (head dim d = 64 or 128,
+  whatever ``hidden / heads`` is), rotary position embedding in place on its output (``kml_rope``
+  / ``kml_rope128``), grouped-query causal flash attention (``kml_attn_gqa_fwd / _bwd``, at head dim
+  128 ``kml_attn128_fwd / _bwd`` of csrc/kernels/attention_d128.hip: ``Hkv`` K/V heads shared by
   groups of ``H / Hkv`` query heads);
 * gated SiLU MLP: one fused ``gate_up`` projection ``[2 I, hidden]``, ``kml_swiglu_fwd / _bwd``,
   ``down_proj``;
@@ -25,8 +26,9 @@ token is one captured step of eight launches a layer (csrc/kernels/decode.hip): 
 ``lens[b]``), ``kml_attn_decode_gqa`` (a chunk of a K/V head loaded once for its group of query
 heads), ``o_proj``, add + RMSNorm, ``kml_gemm_skinny_glu`` (gate and up GEMM with the SwiGLU in the
 epilogue), ``down_proj``, add + RMSNorm.  Not implemented: speculative decoding
-(``prompt_lookup_num_tokens > 0`` raises ``ValueError``), head dim 128, ``rope_scaling``, paged
-caches.
+(``prompt_lookup_num_tokens > 0`` raises ``ValueError``), KV-cache decoding at head dim 128 (such
+a model trains and evaluates full sequences; ``new_cache`` / ``prefill`` / ``decode_step`` /
+``generate`` raise ``NotImplementedError``), ``rope_scaling``, paged caches.
 """
 from __future__ import annotations
 
@@ -68,20 +70,22 @@ class LlamaAttention(tnn.Module):
     grouped-query causal attention + ``o_proj``; HF's ``q_proj`` / ``k_proj`` / ``v_proj`` through
     the state-dict hooks."""
 
-    def __init__(self, hidden, heads, kv_heads):
+    def __init__(self, hidden, heads, kv_heads, head_dim=64):
         super().__init__()
         if kv_heads < 1 or heads % kv_heads:
             raise ValueError(f"kv_heads {kv_heads} must divide heads {heads}")
-        self.hidden, self.heads, self.kv_heads = hidden, heads, kv_heads
-        self.qkv = Linear(hidden, (heads + 2 * kv_heads) * 64, bias=False)
-        self.o_proj = Linear(heads * 64, hidden, bias=False)   # head dim is 64 whatever hidden / heads is
+        if head_dim not in (64, 128):
+            raise ValueError(f"head_dim {head_dim}: the attention kernels are written for 64 and 128")
+        self.hidden, self.heads, self.kv_heads, self.head_dim = hidden, heads, kv_heads, head_dim
+        self.qkv = Linear(hidden, (heads + 2 * kv_heads) * head_dim, bias=False)
+        self.o_proj = Linear(heads * head_dim, hidden, bias=False)   # whatever hidden / heads is
         self._register_state_dict_hook(LlamaAttention._sd_hook)
         self._register_load_state_dict_pre_hook(LlamaAttention._load_hook, with_module=True)
 
     @staticmethod
     def _sd_hook(mod, sd, prefix, local_metadata):
         w = sd.pop(prefix + "qkv.weight")
-        D, E = mod.heads * 64, mod.kv_heads * 64
+        D, E = mod.heads * mod.head_dim, mod.kv_heads * mod.head_dim
         sd[prefix + "q_proj.weight"], sd[prefix + "k_proj.weight"], sd[prefix + "v_proj.weight"] = \
             w[:D], w[D:D + E], w[D + E:]
         sd[prefix + "o_proj.weight"] = sd.pop(prefix + "o_proj.weight")   # HF order: q, k, v, o
@@ -94,12 +98,12 @@ class LlamaAttention(tnn.Module):
             sd[prefix + "qkv.weight"] = torch.cat([sd.pop(n) for n in names], 0)
 
     def forward(self, x, B, L, table, bias=None):
-        H, Hkv = self.heads, self.kv_heads
-        qkv = rope(self.qkv(x), table, L, H, Hkv)
+        H, Hkv, d = self.heads, self.kv_heads, self.head_dim
+        qkv = rope(self.qkv(x), table, L, H, Hkv, head_dim=d)
         if not x.is_cuda:
-            ctx = attention_reference(qkv, B, H, L, bias, causal=True, kv_heads=Hkv)
+            ctx = attention_reference(qkv, B, H, L, bias, causal=True, kv_heads=Hkv, head_dim=d)
         else:
-            ctx = _AttnFn.apply(qkv, B, H, L, bias, None, True, Hkv)
+            ctx = _AttnFn.apply(qkv, B, H, L, bias, None, True, Hkv, d)
         return self.o_proj(ctx)
 
 
@@ -154,9 +158,9 @@ class LlamaDecoderLayer(tnn.Module):
     receives ``input_layernorm(h)`` already computed (by the previous layer's closing add-and-
     normalise) and returns its MLP branch and the stream; the caller's next ``add_norm`` closes it."""
 
-    def __init__(self, hidden, heads, kv_heads, inter, eps):
+    def __init__(self, hidden, heads, kv_heads, inter, eps, head_dim=64):
         super().__init__()
-        self.self_attn = LlamaAttention(hidden, heads, kv_heads)
+        self.self_attn = LlamaAttention(hidden, heads, kv_heads, head_dim)
         self.mlp = LlamaMLP(hidden, inter)
         self.input_layernorm = RMSNorm(hidden, eps)
         self.post_attention_layernorm = RMSNorm(hidden, eps)
@@ -168,14 +172,15 @@ class LlamaDecoderLayer(tnn.Module):
 
 
 class LlamaModel(tnn.Module):
-    def __init__(self, vocab, hidden, layers, heads, kv_heads, inter, max_pos, eps, rope_theta):
+    def __init__(self, vocab, hidden, layers, heads, kv_heads, inter, max_pos, eps, rope_theta, head_dim=64):
         super().__init__()
         self.embed_tokens = tnn.Embedding(vocab, hidden)
-        self.layers = tnn.ModuleList([LlamaDecoderLayer(hidden, heads, kv_heads, inter, eps) for _ in range(layers)])
+        self.layers = tnn.ModuleList([LlamaDecoderLayer(hidden, heads, kv_heads, inter, eps, head_dim)
+                                      for _ in range(layers)])
         self.norm = RMSNorm(hidden, eps)
         self.max_pos = max_pos
         # cos | sin of every position: built in fp64, rounded to fp32 once; a buffer, not a parameter
-        self.register_buffer("rope_table", rope_table(max_pos, rope_theta), persistent=False)
+        self.register_buffer("rope_table", rope_table(max_pos, rope_theta, head_dim=head_dim), persistent=False)
         # storage rows padded to 8 so a tied lm_head Linear can share the token table
         vp = -(-vocab // 8) * 8
         self.embed_tokens.weight._kml_storage_shape = (vp, hidden)
@@ -205,12 +210,13 @@ class LlamaModel(tnn.Module):
 
 class LlamaForCausalLM(DecodeMixin, tnn.Module):
     def __init__(self, vocab=32000, hidden=576, layers=30, heads=9, kv_heads=3, inter=1536, max_pos=2048, eps=1e-5,
-                 rope_theta=10000.0, tie_word_embeddings=False, seed: int = 0):
+                 rope_theta=10000.0, tie_word_embeddings=False, seed: int = 0, head_dim: int = 64):
         super().__init__()
         self.vocab = vocab
         self.tie_word_embeddings = bool(tie_word_embeddings)
         self.seed = seed
-        self.model = LlamaModel(vocab, hidden, layers, heads, kv_heads, inter, max_pos, eps, rope_theta)
+        self.head_dim = head_dim
+        self.model = LlamaModel(vocab, hidden, layers, heads, kv_heads, inter, max_pos, eps, rope_theta, head_dim)
         self.lm_head = Linear(hidden, vocab, bias=False)
         if self.tie_word_embeddings:   # lm_head.weight IS the token table
             self.lm_head.weight = self.model.embed_tokens.weight
@@ -222,9 +228,11 @@ class LlamaForCausalLM(DecodeMixin, tnn.Module):
         """Build the model a HuggingFace Llama ``config`` describes: a ``LlamaConfig``, a dict, or
         the path of a ``config.json``.  Maps the sizes, ``rms_norm_eps``, ``rope_theta`` and
         ``tie_word_embeddings``.  Raises ``ValueError`` for what this model does not implement:
-        a head dim other than 64, ``hidden_act`` other than ``silu``, a ``rope_scaling``,
+        a head dim (``head_dim``, or ``hidden_size // num_attention_heads`` without one) other than
+        64 or 128, ``hidden_act`` other than ``silu``, a ``rope_scaling``,
         ``attention_bias`` / ``mlp_bias``, a non-zero ``attention_dropout``.  ``overrides`` replace
-        constructor arguments.  Follow with ``load_state_dict(hf_model.state_dict())``."""
+        constructor arguments.  Follow with ``load_state_dict(hf_model.state_dict())``.  A head-dim-128
+        model trains and evaluates full sequences; its KV-cache decoding is not implemented yet."""
         if isinstance(config, (str, os.PathLike)):
             with open(config) as f:
                 config = json.load(f)
@@ -235,9 +243,9 @@ class LlamaForCausalLM(DecodeMixin, tnn.Module):
         c = config
         hidden, heads = c.get("hidden_size", 4096), c.get("num_attention_heads", 32)
         head_dim = c.get("head_dim") or hidden // heads
-        if head_dim != 64:
-            raise ValueError(f"from_hf_config: head dim {head_dim} (hidden {hidden}, {heads} heads); only 64 is "
-                             "implemented")
+        if head_dim not in (64, 128):
+            raise ValueError(f"from_hf_config: head dim {head_dim} (hidden {hidden}, {heads} heads); only 64 and "
+                             "128 are implemented")
         if c.get("hidden_act", "silu") != "silu":
             raise ValueError(f"from_hf_config: hidden_act {c.get('hidden_act')!r} (supported: 'silu')")
         if c.get("rope_scaling") is not None:
@@ -251,7 +259,8 @@ class LlamaForCausalLM(DecodeMixin, tnn.Module):
         kw = dict(vocab=c.get("vocab_size", 32000), hidden=hidden, layers=c.get("num_hidden_layers", 32), heads=heads,
                   kv_heads=heads if kvh is None else kvh, inter=c.get("intermediate_size", 11008),
                   max_pos=c.get("max_position_embeddings", 2048), eps=c.get("rms_norm_eps", 1e-6),
-                  rope_theta=c.get("rope_theta", 10000.0), tie_word_embeddings=c.get("tie_word_embeddings", False))
+                  rope_theta=c.get("rope_theta", 10000.0), tie_word_embeddings=c.get("tie_word_embeddings", False),
+                  head_dim=head_dim)
         kw.update(overrides)
         return cls(**kw)
 
@@ -304,7 +313,25 @@ class LlamaForCausalLM(DecodeMixin, tnn.Module):
         m = self.model
         return list(zip(m.layers, [lay.input_layernorm for lay in m.layers[1:]] + [m.norm]))
 
+    def _decode_check(self):
+        if self.head_dim != 64:
+            raise NotImplementedError(f"KV-cache decoding at head dim {self.head_dim} is not implemented: head dim 128 "
+                                      "decodes with the follow-up to the head-dim-128 training kernels")
+
+    def prefill(self, ids, attention_mask, cache):
+        self._decode_check()
+        return super().prefill(ids, attention_mask, cache)
+
+    def decode_step(self, cache):
+        self._decode_check()
+        return super().decode_step(cache)
+
+    def generate(self, *args, **kw):
+        self._decode_check()
+        return super().generate(*args, **kw)
+
     def new_cache(self, B, Lcap, device=None):
+        self._decode_check()
         m = self.model
         at = m.layers[0].self_attn
         p = m.embed_tokens.weight

@@ -241,21 +241,23 @@ class Dropout(tnn.Module):
 
 
 # ====================================================================================== attention
-def _split_qkv(qkv, H, kv_heads):
-    """(q, k, v) column views of a fused ``[T, (H + 2 Hkv) * 64]`` buffer: H*64 | Hkv*64 | Hkv*64."""
-    D, E = H * 64, (H if kv_heads is None else kv_heads) * 64
+def _split_qkv(qkv, H, kv_heads, head_dim=64):
+    """(q, k, v) column views of a fused ``[T, (H + 2 Hkv) * d]`` buffer: H*d | Hkv*d | Hkv*d,
+    d = head_dim."""
+    D, E = H * head_dim, (H if kv_heads is None else kv_heads) * head_dim
     return qkv[:, :D], qkv[:, D:D + E], qkv[:, D + E:D + 2 * E]
 
 
 class _AttnFn(Function):
     @staticmethod
-    def forward(ctx, qkv, B, H, L, bias, drop=None, causal=False, kv_heads=None):
+    def forward(ctx, qkv, B, H, L, bias, drop=None, causal=False, kv_heads=None, head_dim=64):
         from ..ops import transformer as T
-        q, k, v = _split_qkv(qkv, H, kv_heads)
+        q, k, v = _split_qkv(qkv, H, kv_heads, head_dim)
         keep = T.attn_keep_buffer(B, H, L, qkv.device) if drop is not None and drop[2] > 0.0 else None
-        out, lse = T.attn_fwd(q, k, v, B, H, L, bias=bias, drop=drop, keep=keep, causal=causal, kv_heads=kv_heads)
+        out, lse = T.attn_fwd(q, k, v, B, H, L, bias=bias, drop=drop, keep=keep, causal=causal, kv_heads=kv_heads,
+                              head_dim=head_dim)
         ctx.save = (qkv, out, lse, bias, keep)
-        ctx.dims = (B, H, L, kv_heads)
+        ctx.dims = (B, H, L, kv_heads, head_dim)
         ctx.drop = drop
         ctx.causal = causal
         return out
@@ -264,27 +266,28 @@ class _AttnFn(Function):
     def backward(ctx, dout):
         from ..ops import transformer as T
         qkv, out, lse, bias, keep = ctx.save
-        B, H, L, kv_heads = ctx.dims
+        B, H, L, kv_heads, head_dim = ctx.dims
         dqkv = torch.empty_like(qkv)
-        q, k, v = _split_qkv(qkv, H, kv_heads)
-        dq, dk, dv = _split_qkv(dqkv, H, kv_heads)
+        q, k, v = _split_qkv(qkv, H, kv_heads, head_dim)
+        dq, dk, dv = _split_qkv(dqkv, H, kv_heads, head_dim)
         T.attn_bwd(q, k, v, out, _bf(dout).contiguous(), lse, B, H, L, bias=bias, dq=dq, dk=dk, dv=dv, drop=ctx.drop,
-                   keep=keep, causal=ctx.causal, kv_heads=kv_heads)
+                   keep=keep, causal=ctx.causal, kv_heads=kv_heads, head_dim=head_dim)
         ctx.save = None
-        return dqkv, None, None, None, None, None, None, None
+        return dqkv, None, None, None, None, None, None, None, None
 
 
-def attention_reference(qkv, B, H, L, bias=None, keep=None, causal=False, kv_heads=None):
+def attention_reference(qkv, B, H, L, bias=None, keep=None, causal=False, kv_heads=None, head_dim=64):
     """fp32 torch attention on a fused [B*L, 3*H*64] buffer (CPU path / tests); keep:
     optional [B, H, L, L] dropout multiplier (0 or 1/(1-p)) applied to the probabilities;
     causal: lower-triangular mask (query t attends keys <= t); kv_heads: grouped-query attention
-    on a [B*L, (H + 2 kv_heads)*64] buffer (query head h reads K/V head h // (H // kv_heads))."""
-    D = H * 64
+    on a [B*L, (H + 2 kv_heads)*64] buffer (query head h reads K/V head h // (H // kv_heads));
+    head_dim: the columns of a head (64, or 128 with scale 1/sqrt(128))."""
+    D = H * head_dim
     Hkv = H if kv_heads is None else kv_heads
-    q, k, v = (t.reshape(B, L, -1, 64).permute(0, 2, 1, 3) for t in _split_qkv(qkv, H, kv_heads))
+    q, k, v = (t.reshape(B, L, -1, head_dim).permute(0, 2, 1, 3) for t in _split_qkv(qkv, H, kv_heads, head_dim))
     if Hkv != H:
         k, v = (t.repeat_interleave(H // Hkv, dim=1) for t in (k, v))
-    s = q @ k.transpose(-1, -2) / math.sqrt(64)
+    s = q @ k.transpose(-1, -2) / math.sqrt(head_dim)
     if bias is not None:
         s = s + bias.view(B, 1, 1, L)
     if causal:
@@ -428,27 +431,30 @@ class RMSNorm(tnn.Module):
         return self.add_norm(x, residual)[0].view(shp)
 
 
-def rope_table(max_pos, theta=10000.0, device=None):
-    """fp32 ``[max_pos, 64]`` table of the rotary embedding: row p = cos(p f_i) (32) | sin(p f_i)
-    (32), f_i = theta^(-i/32), computed in fp64 on the host and rounded once."""
-    f = torch.tensor(float(theta), dtype=torch.float64) ** (-torch.arange(32, dtype=torch.float64) / 32)
+def rope_table(max_pos, theta=10000.0, device=None, head_dim=64):
+    """fp32 ``[max_pos, head_dim]`` table of the rotary embedding: with h = head_dim / 2 (32, or 64
+    at head dim 128), row p = cos(p f_i) (h) | sin(p f_i) (h), f_i = theta^(-i/h), computed in fp64
+    on the host and rounded once."""
+    h = head_dim // 2
+    f = torch.tensor(float(theta), dtype=torch.float64) ** (-torch.arange(h, dtype=torch.float64) / h)
     ang = torch.arange(max_pos, dtype=torch.float64)[:, None] * f[None]
     t = torch.cat([ang.cos(), ang.sin()], 1).to(torch.float32)
     return t if device is None else t.to(device)
 
 
-def rope_reference(qkv, table, L, H, kv_heads, pos=None):
+def rope_reference(qkv, table, L, H, kv_heads, pos=None, head_dim=64):
     """Stock-torch rotary embedding of a fused ``[B*L, (H + 2 Hkv)*64]`` buffer (HF ``rotate_half``:
     element i < 32 of a head pairs with i + 32); table: :func:`rope_table`.  ``pos``: the position
-    of every row (a decode step's rows sit at their sequences' lengths) instead of ``row % L``."""
+    of every row (a decode step's rows sit at their sequences' lengths) instead of ``row % L``.
+    ``head_dim`` 128: heads of 128 columns, element i < 64 pairs with i + 64."""
     T_ = qkv.shape[0]
-    n = (H + kv_heads) * 64
+    n, h = (H + kv_heads) * head_dim, head_dim // 2
     if pos is None:
         pos = torch.arange(T_, device=qkv.device) % L
     tb = table.to(qkv.dtype)[pos]
-    c, s = tb[:, None, :32], tb[:, None, 32:]
-    x = qkv[:, :n].reshape(T_, H + kv_heads, 64)
-    a, b = x[..., :32], x[..., 32:]
+    c, s = tb[:, None, :h], tb[:, None, h:]
+    x = qkv[:, :n].reshape(T_, H + kv_heads, head_dim)
+    a, b = x[..., :h], x[..., h:]
     rot = torch.cat([a * c - b * s, b * c + a * s], -1).reshape(T_, n)
     return torch.cat([rot, qkv[:, n:]], 1)
 
@@ -476,11 +482,14 @@ class _RopeFn(Function):
         return dqkv, None, None, None, None
 
 
-def rope(qkv, table, L, H, kv_heads):
+def rope(qkv, table, L, H, kv_heads, head_dim=64):
     """Rotary position embedding of the Q and K heads of a fused projection buffer (position =
-    row % L).  GPU: in place, one launch; CPU: :func:`rope_reference`."""
+    row % L).  GPU: in place, one launch; CPU: :func:`rope_reference`.  ``table`` must be the
+    :func:`rope_table` of the same ``head_dim``."""
+    if table.shape[1] != head_dim:
+        raise ValueError(f"rope: a table of width {table.shape[1]} for head_dim {head_dim}")
     if not qkv.is_cuda:
-        return rope_reference(qkv, table, L, H, kv_heads)
+        return rope_reference(qkv, table, L, H, kv_heads, head_dim=head_dim)
     return _RopeFn.apply(_bf(qkv).contiguous(), table, L, H, kv_heads)
 
 

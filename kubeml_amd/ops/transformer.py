@@ -64,28 +64,45 @@ def _kv_heads(H, kv_heads):
     return Hkv
 
 
-def attn_fwd(q, k, v, B, H, L, bias=None, out=None, scale=None, drop=None, keep=None, causal=False, kv_heads=None):
+def _head_dim(head_dim, drop):
+    """64 (attention.hip) or 128 (attention_d128.hip, which has no attention dropout)."""
+    if head_dim not in (64, 128):
+        raise ValueError(f"head_dim {head_dim}: the attention kernels are written for 64 and 128")
+    if head_dim == 128 and drop is not None and drop[2] > 0.0:
+        raise ValueError("attention dropout is not implemented at head_dim 128")
+    return head_dim
+
+
+def attn_fwd(q, k, v, B, H, L, bias=None, out=None, scale=None, drop=None, keep=None, causal=False, kv_heads=None,
+             head_dim=64):
     """q/k/v: [B*L, ld] bf16 views with head h at columns 64h..64h+63 (may be column
     slices of one fused QKV buffer).  kv_heads: grouped-query attention — k / v hold ``kv_heads``
     heads and query head h reads K/V head ``h // (H // kv_heads)`` (None: H heads, the plain entry
     points).  drop: (ctr, salt, p) attention-probability dropout;
     keep: optional :func:`attn_keep_buffer` that receives the dropout keep bits, so
     :func:`attn_bwd` reads them instead of re-hashing.  causal: query t attends keys <= t only
-    (the key tiles above the diagonal are skipped).  Returns (out [B*L, H*64], lse [B*H, L])."""
+    (the key tiles above the diagonal are skipped).  head_dim: 64, or 128 (head h at columns
+    128h..128h+127; ``kml_attn128_fwd``, no dropout).  Returns (out [B*L, H*head_dim], lse [B*H, L])."""
     Hkv = _kv_heads(H, kv_heads)
+    D = _head_dim(head_dim, drop)
     for n, t, hh in (("q", q, H), ("k", k, Hkv), ("v", v, Hkv)):
         _chk_view(t, n)
-        if t.shape[0] != B * L or t.shape[1] < hh * 64:
-            raise ValueError(f"{n}: expected a row-major [B*L, >= {hh * 64}] view, got {tuple(t.shape)}")
+        if t.shape[0] != B * L or t.shape[1] < hh * D:
+            raise ValueError(f"{n}: expected a row-major [B*L, >= {hh * D}] view, got {tuple(t.shape)}")
     if bias is not None:
         _chk(bias, F32, "bias")
         if bias.numel() != B * L:
             raise ValueError("bias must be [B, L]")
     if out is None:
-        out = torch.empty((B * L, H * 64), dtype=BF16, device=q.device)
+        out = torch.empty((B * L, H * D), dtype=BF16, device=q.device)
     lse = torch.empty((B * H, L), dtype=F32, device=q.device)
-    scale = 1.0 / math.sqrt(64) if scale is None else scale
+    scale = 1.0 / math.sqrt(D) if scale is None else scale
     c, salt, pd = _drop_args(drop)
+    if D == 128:
+        HIP.call("kml_attn128_fwd", "p p p p p p i i i i i i i i f p i f p i s",
+                 _p(q), _p(k), _p(v), _p(out), _p(lse), _p(bias), q.stride(0), k.stride(0), v.stride(0),
+                 out.stride(0), B, H, Hkv, L, float(scale), 0, 0, 0.0, 0, int(bool(causal)), _s())
+        return out, lse
     if kv_heads is not None:
         HIP.call("kml_attn_gqa_fwd", "p p p p p p i i i i i i i i f p i f p i s",
                  _p(q), _p(k), _p(v), _p(out), _p(lse), _p(bias), q.stride(0), k.stride(0), v.stride(0),
@@ -99,29 +116,37 @@ def attn_fwd(q, k, v, B, H, L, bias=None, out=None, scale=None, drop=None, keep=
 
 
 def attn_bwd(q, k, v, o, dout, lse, B, H, L, bias=None, dq=None, dk=None, dv=None, scale=None, drop=None,
-             keep=None, causal=False, kv_heads=None):
+             keep=None, causal=False, kv_heads=None, head_dim=64):
     """Gradients of attention; dq/dk/dv may be column views of one [B*L, 3*H*64] buffer.
     keep: the keep-bit buffer the forward filled (same drop), or None to re-hash the mask;
-    causal, kv_heads: as given to :func:`attn_fwd`.  Grouped-query: dk / dv have ``kv_heads * 64``
-    columns, each head the sum over its group of query heads (fp32 accumulators, fixed order)."""
+    causal, kv_heads, head_dim: as given to :func:`attn_fwd`.  Grouped-query: dk / dv have
+    ``kv_heads * head_dim`` columns, each head the sum over its group of query heads (fp32
+    accumulators, fixed order)."""
     dev = q.device
     Hkv = _kv_heads(H, kv_heads)
+    D = _head_dim(head_dim, drop)
     if dq is None:
-        dq = torch.empty((B * L, H * 64), dtype=BF16, device=dev)
+        dq = torch.empty((B * L, H * D), dtype=BF16, device=dev)
     if dk is None:
-        dk = torch.empty((B * L, Hkv * 64), dtype=BF16, device=dev)
+        dk = torch.empty((B * L, Hkv * D), dtype=BF16, device=dev)
     if dv is None:
-        dv = torch.empty((B * L, Hkv * 64), dtype=BF16, device=dev)
+        dv = torch.empty((B * L, Hkv * D), dtype=BF16, device=dev)
     for n, t, hh in (("q", q, H), ("k", k, Hkv), ("v", v, Hkv), ("o", o, H), ("dout", dout, H), ("dq", dq, H),
                      ("dk", dk, Hkv), ("dv", dv, Hkv)):
         _chk_view(t, n)
-        if t.shape[0] != B * L or t.shape[1] < hh * 64:
-            raise ValueError(f"{n}: expected [B*L, >= {hh * 64}], got {tuple(t.shape)}")
+        if t.shape[0] != B * L or t.shape[1] < hh * D:
+            raise ValueError(f"{n}: expected [B*L, >= {hh * D}], got {tuple(t.shape)}")
     if lse.shape != (B * H, L) or lse.dtype != F32:
         raise ValueError("lse must be fp32 [B*H, L] from attn_fwd")
     dsum = torch.empty((B * H, L), dtype=F32, device=dev)
-    scale = 1.0 / math.sqrt(64) if scale is None else scale
+    scale = 1.0 / math.sqrt(D) if scale is None else scale
     c, salt, pd = _drop_args(drop)
+    if D == 128:
+        HIP.call("kml_attn128_bwd", "p p p p p p p p p p p i i i i i i i i i i i i f p i f p i s",
+                 _p(q), _p(k), _p(v), _p(o), _p(dout), _p(lse), _p(dsum), _p(bias), _p(dq), _p(dk), _p(dv),
+                 q.stride(0), k.stride(0), v.stride(0), o.stride(0), dout.stride(0), dq.stride(0), dk.stride(0),
+                 dv.stride(0), B, H, Hkv, L, float(scale), 0, 0, 0.0, 0, int(bool(causal)), _s())
+        return dq, dk, dv
     if kv_heads is not None:
         HIP.call("kml_attn_gqa_bwd", "p p p p p p p p p p p i i i i i i i i i i i i f p i f p i s",
                  _p(q), _p(k), _p(v), _p(o), _p(dout), _p(lse), _p(dsum), _p(bias), _p(dq), _p(dk), _p(dv),
@@ -222,16 +247,18 @@ def rmsnorm_bwd(dy, xin, rstd, gamma, dgamma, dx_add=None):
 
 
 def rope_(qkv, table, L, H, kv_heads, backward=False):
-    """Rotary embedding in place on the fused ``[B*L, (H + 2 kv_heads) * 64]`` projection buffer (or
+    """Rotary embedding in place on the fused ``[B*L, (H + 2 kv_heads) * D]`` projection buffer (or
     its gradient with ``backward``: the transpose rotation): the H query and kv_heads key heads are
-    rotated by the position ``row % L``, V is left alone.  table: ``nn.transformer.rope_table``."""
+    rotated by the position ``row % L``, V is left alone.  table: ``nn.transformer.rope_table``; its
+    width is the head dim D, 64 or 128."""
     _chk_view(qkv, "qkv")
     _chk(table, F32, "table")
-    if table.dim() != 2 or table.shape[1] != 64 or L > table.shape[0]:
-        raise ValueError(f"rope_: table must be [max_pos >= {L}, 64], got {tuple(table.shape)}")
-    if qkv.shape[1] != (H + 2 * kv_heads) * 64 or qkv.shape[0] % L:
-        raise ValueError(f"rope_: expected [B*{L}, {(H + 2 * kv_heads) * 64}], got {tuple(qkv.shape)}")
-    HIP.call("kml_rope", "p i p l i i i i i s", _p(qkv), qkv.stride(0), _p(table), qkv.shape[0], L, H, kv_heads,
+    if table.dim() != 2 or table.shape[1] not in (64, 128) or L > table.shape[0]:
+        raise ValueError(f"rope_: table must be [max_pos >= {L}, 64 or 128], got {tuple(table.shape)}")
+    D = table.shape[1]
+    if qkv.shape[1] != (H + 2 * kv_heads) * D or qkv.shape[0] % L:
+        raise ValueError(f"rope_: expected [B*{L}, {(H + 2 * kv_heads) * D}], got {tuple(qkv.shape)}")
+    HIP.call("kml_rope128" if D == 128 else "kml_rope", "p i p l i i i i i s", _p(qkv), qkv.stride(0), _p(table), qkv.shape[0], L, H, kv_heads,
              table.shape[0], int(bool(backward)), _s())
     return qkv
 

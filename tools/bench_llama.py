@@ -4,7 +4,7 @@ model's shapes (not the headline bench — see bench.py).  Synthetic token batch
 compute, fp32 master weights, the whole step captured as one hipGraph.
 
     python tools/bench_llama.py [--batch 16] [--seq 1024] [--steps 10] [--warmup 2] [--layers 30]
-                                [--no-step] [--no-kernels] [--reps 20]
+                                [--no-step] [--no-kernels] [--reps 20] [--head-dim 128]
 Prints one JSON line per part: the kernels, then the step (tokens/s over all processed tokens).
 The kernel part gives call times: device events around one launcher call on an idle queue, so each
 includes the launcher's host path (output allocation, the ctypes call) — RMSNorm, RoPE and SwiGLU
@@ -15,6 +15,13 @@ attention backward into dQ and dKV) come from a kernel trace of ``--no-step`` in
 
     rocprofv3 --kernel-trace -d out -o run -- python tools/bench_llama.py --no-step
     python tools/rocpd_summary.py out/*/run_results.db
+
+``--head-dim 128`` switches both parts to a head-dim-128 model (hidden 2048, 16 heads / 4 K/V heads,
+inter 5632, vocab 32000, untied) and the kernel part to csrc/kernels/attention_d128.hip: the forward
+call and the backward call (dQ and dKV launches; their split again from the kernel trace) at H = 16,
+Hkv = 4, D = 128, taking turns in one loop with the D = 64 kernels at H = 32, Hkv = 8 (the same
+FLOPs and bytes) and with ``torch.nn.functional.scaled_dot_product_attention`` on the D = 128
+operands (K/V heads repeated beforehand), and RoPE at 128 forward / backward; median and range.
 """
 import argparse
 import json
@@ -26,6 +33,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 HBM_BYTES_PER_S = 6.3e12
 CFG = dict(vocab=49152, hidden=576, heads=9, kv_heads=3, inter=1536, max_pos=2048, tie_word_embeddings=True)
+CFG128 = dict(vocab=32000, hidden=2048, heads=16, kv_heads=4, inter=5632, max_pos=2048, head_dim=128)
 
 
 def bench_step(a, torch):
@@ -34,7 +42,8 @@ def bench_step(a, torch):
     from kubeml_amd.nn import flatten_module
     from kubeml_amd.optim import AdamW
     dev = torch.device("cuda", 0)
-    m = LlamaForCausalLM(layers=a.layers, seed=1, **CFG).to(dev)
+    cfg = CFG128 if a.head_dim == 128 else CFG
+    m = LlamaForCausalLM(layers=a.layers, seed=1, **cfg).to(dev)
     sp = flatten_module(m)
     m.train()
     opt = AdamW(m.parameters(), lr=1e-4, weight_decay=0.01)
@@ -59,7 +68,8 @@ def bench_step(a, torch):
         loss = step()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    print(json.dumps({"metric": "Llama 576/9/3/1536 causal-LM training tokens/s",
+    name = "/".join(str(cfg[k]) for k in ("hidden", "heads", "kv_heads", "inter"))
+    print(json.dumps({"metric": f"Llama {name} (head dim {a.head_dim}) causal-LM training tokens/s",
                       "value": round(B * L * a.steps / dt, 1), "unit": "tokens/s", "n_gpus": 1,
                       "ms_per_step": round(dt / a.steps * 1e3, 3), "batch_per_gpu": B, "seq": L, "layers": a.layers,
                       "params": sum(p.numel() for p in m.parameters()), "optimizer": "fused AdamW", "dtype": "bf16",
@@ -67,9 +77,10 @@ def bench_step(a, torch):
                       "loss_first_last": [round(first, 4), round(float(loss.detach()), 4)]}), flush=True)
 
 
-def _time_alternating(torch, fns, reps):
+def _time_alternating(torch, fns, reps, spread=False):
     """device-event ms around one call of each fn on an idle queue (host path included), the fns
-    taking turns inside one loop (after a warm-up round); returns the median of ``reps`` rounds per fn"""
+    taking turns inside one loop (after a warm-up round); returns the median of ``reps`` rounds per fn
+    (spread: (median, min, max))"""
     for f in fns:
         f()
     torch.cuda.synchronize()
@@ -82,7 +93,55 @@ def _time_alternating(torch, fns, reps):
             e1.record()
             e1.synchronize()
             ms[i].append(e0.elapsed_time(e1))
+    if spread:
+        return [(sorted(v)[len(v) // 2], min(v), max(v)) for v in ms]
     return [sorted(v)[len(v) // 2] for v in ms]
+
+
+def bench_kernels128(a, torch):
+    """the head-dim-128 attention calls beside D = 64 at twice the heads and torch SDPA; RoPE at 128"""
+    import torch.nn.functional as F
+    from kubeml_amd.nn.transformer import _split_qkv, rope_table
+    from kubeml_amd.ops import transformer as T
+    dev = torch.device("cuda", 0)
+    B, L, H, Hkv = a.batch, a.seq, CFG128["heads"], CFG128["kv_heads"]
+    Tn = B * L
+    g = torch.Generator(device=dev).manual_seed(2)
+    rnd = lambda *s: torch.randn(*s, device=dev, generator=g).to(torch.bfloat16)
+    dout = rnd(Tn, H * 128)
+    runs = {}
+    for name, D, h, hkv in (("d128", 128, H, Hkv), ("d64", 64, 2 * H, 2 * Hkv)):
+        buf = rnd(Tn, (h + 2 * hkv) * D) * 0.5
+        q, k, v = _split_qkv(buf, h, hkv, D)
+        o, lse = T.attn_fwd(q, k, v, B, h, L, causal=True, kv_heads=hkv, head_dim=D)
+        dq, dk, dv = _split_qkv(torch.empty_like(buf), h, hkv, D)
+        runs[name + "_fwd"] = lambda q=q, k=k, v=v, h=h, hkv=hkv, D=D: T.attn_fwd(
+            q, k, v, B, h, L, causal=True, kv_heads=hkv, head_dim=D)
+        runs[name + "_bwd"] = lambda q=q, k=k, v=v, o=o, lse=lse, dq=dq, dk=dk, dv=dv, h=h, hkv=hkv, D=D: T.attn_bwd(
+            q, k, v, o, dout, lse, B, h, L, dq=dq, dk=dk, dv=dv, causal=True, kv_heads=hkv, head_dim=D)
+        if D == 128:   # torch SDPA on the same operands, [B, H, L, 128], K/V heads repeated once outside the timing
+            sq, sk, sv = (t.reshape(B, L, -1, D).transpose(1, 2) for t in (q, k, v))
+            sk, sv = (t.repeat_interleave(H // Hkv, dim=1) for t in (sk, sv))
+            sq, sk, sv = (t.contiguous().requires_grad_(True) for t in (sq, sk, sv))
+            so = F.scaled_dot_product_attention(sq, sk, sv, is_causal=True)
+            sdo = dout.reshape(B, L, H, D).transpose(1, 2).contiguous()
+            runs["sdpa_fwd"] = lambda sq=sq, sk=sk, sv=sv: F.scaled_dot_product_attention(sq, sk, sv, is_causal=True)
+            runs["sdpa_bwd"] = lambda so=so, sq=sq, sk=sk, sv=sv: torch.autograd.grad(so, (sq, sk, sv), sdo,
+                                                                                      retain_graph=True)
+    qkv = rnd(Tn, (H + 2 * Hkv) * 128) * 0.5
+    table = rope_table(L, 10000.0, device=dev, head_dim=128)
+    runs["rope128_fwd"] = lambda: T.rope_(qkv, table, L, H, Hkv)
+    runs["rope128_bwd"] = lambda: T.rope_(qkv, table, L, H, Hkv, backward=True)
+    names = ["d128_fwd", "d64_fwd", "sdpa_fwd", "d128_bwd", "d64_bwd", "sdpa_bwd", "rope128_fwd", "rope128_bwd"]
+    out = {"batch": B, "seq": L, "reps": a.reps, "heads_d128": [H, Hkv], "heads_d64": [2 * H, 2 * Hkv]}
+    for n, (med, lo, hi) in zip(names, _time_alternating(torch, [runs[n] for n in names], a.reps, spread=True)):
+        out[n] = {"call_ms": round(med, 4), "min_ms": round(lo, 4), "max_ms": round(hi, 4)}
+    # causal attention: 2 GEMMs forward, 5 backward, half of the L x L tiles
+    flops = 0.5 * 4.0 * B * H * L * L * 128
+    out["causal_fwd_flops"] = flops
+    out["rope_hbm_floor_ms"] = round(2 * Tn * (H + Hkv) * 128 * 2 / HBM_BYTES_PER_S * 1e3, 4)
+    print(json.dumps({"metric": "head-dim-128 attention calls (device events around one call; median, range)",
+                      **out}), flush=True)
 
 
 def bench_kernels(a, torch):
@@ -148,6 +207,7 @@ def main():
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--no-step", action="store_true")
     ap.add_argument("--no-kernels", action="store_true")
+    ap.add_argument("--head-dim", type=int, default=64, choices=(64, 128))
     a = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
@@ -155,7 +215,7 @@ def main():
     torch.cuda.set_device(0)
     torch.manual_seed(0)
     if not a.no_kernels:
-        bench_kernels(a, torch)
+        (bench_kernels128 if a.head_dim == 128 else bench_kernels)(a, torch)
     if not a.no_step:
         bench_step(a, torch)
 
