@@ -24,7 +24,33 @@ struct AttnArgs {
   int xcd;             // XCD-aware block order (attn_blk); 0: plain grid order (A/B switch)
   unsigned char* keep; // dropout keep bits written by the forward, read by the backward (Drop), or null
   int G;               // grouped-query attention: query heads per K/V head (H = Hkv * G); 1: one K/V head each
+  const int* key_start;   // [B][L] first key each query attends (BAND kernels: packed documents, windows) or null
 };
+
+// BAND kernels: a bound as read from key_start[b][t], held to the contract 0 <= key_start <= t, so
+// that no tensor, whatever it holds, moves a walk or a mask outside the causal triangle
+__device__ __forceinline__ int band_clamp(int v, int t) { return min(max(v, 0), t); }
+
+// number of leading queries of the sequence row ks[0 .. L) whose bound is <= klast, for a dKV block
+// whose last key is klast: the end of its query walk.  At least klast + 1 (key_start[q] <= q), so
+// the search covers klast + 1 .. L.  Every wave runs it on its own, 64 probes a round (a 64-ary
+// search over the monotone row: two dependent loads up to L = 4096, against twelve for a binary
+// one), the verdicts gathered by a ballot, so the result is block-uniform without LDS.  Every probe
+// lies in [lo, hi - 1], inside the row, and a round leaves less than 1/64 of the range, whatever
+// the row holds.  Call with all 64 lanes active.
+__device__ __forceinline__ int band_end(const int* ks, int klast, int L, int lane) {
+  int lo = klast + 1, hi = L;   // the answer lies in [lo, hi]
+  while (lo < hi) {
+    const int step = (hi - lo + 63) >> 6;
+    const int idx = min(lo + (lane + 1) * step, hi) - 1;   // lane 63 probes row hi - 1
+    const unsigned long long past = __ballot(ks[idx] > klast);
+    if (!past) return hi;   // rows lo .. hi - 1 all see klast
+    const int c = __ffsll((long long)past) - 1;   // the first probe past klast
+    hi = min(lo + (c + 1) * step, hi) - 1;   // its row: the answer is at most that
+    lo = min(lo + c * step, hi);             // the row of the probe before it still sees klast
+  }
+  return lo;
+}
 
 // XCD-aware block order.  Blocks are dealt round-robin over the 8 XCDs (b and b + 8 share
 // one), so with the plain (tile, b*h) grid the 8 tiles of one head land on 8 different L2s

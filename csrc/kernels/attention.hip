@@ -160,8 +160,21 @@ __device__ __forceinline__ bf16x8_t frag_tr(const char* lds, int col0, int ks, i
 // additive key bias — compile-time like the backward kernels
 // GQA: the block of query head h reads K / V at column 64 (h / G); everything else, the dropout
 // hash (keyed by the query bh) and the LSE rows included, is per query head as with G = 1
-template <int DM, bool BIAS, bool CAUSAL, bool GQA>
+//
+// BAND (kml_attn_gqa_band_fwd / _bwd; causal, grouped-query, no dropout): query t attends keys
+// key_start[b][t] .. t, key_start non-decreasing along a sequence — the first row of t's document
+// in a packed batch, or max(0, t - W + 1) for a window.  Every bound is read from device memory
+// (the grid does not depend on it) and clamped to [0, t].  A forward / dQ block starts its walk at
+// key tile kb0 = key_start[q0] / 64, the block's minimum, with the double buffer's parity on
+// kb - kb0; the tiles that begin before key_start of the block's last query take the general path,
+// where a key before the lane's own bound scores -inf (dQ: probability exactly 0) like a key past
+// the query, and the tiles between those and the diagonal keep the fast path.  A row always sees
+// its own key, so none is empty.  A dKV block ends its walk at the tile of the last query whose
+// bound is not past the block's last key (band_end, block-uniform) and stages the tile's bounds with
+// its LSE and D.  With key_start = 0 a BAND kernel does its CAUSAL twin's arithmetic in its order.
+template <int DM, bool BIAS, bool CAUSAL, bool GQA, bool BAND = false>
 __device__ __forceinline__ void attn_fwd_body(const AttnArgs& a) {
+  static_assert(!BAND || (CAUSAL && GQA && DM == 0), "BAND: causal grouped-query without dropout");
   // K/V double-buffered (40 KB: 4 blocks per CU, the VGPR occupancy): one barrier per key
   // tile, and the register-staged next tile is stored after this tile's MFMAs, a whole tile
   // after its global loads were issued
@@ -181,32 +194,41 @@ __device__ __forceinline__ void attn_fwd_body(const AttnArgs& a) {
   const float* bias = BIAS ? a.bias + (long long)b * L : nullptr;
   Drop drop;
   drop.init(a, bh);
+  const int qq = q0 + 16 * w + (lane & 15);   // this lane's query
+  // BAND: first tile of the walk, the bound of the block's last query, this lane's own bound
+  int kb0 = 0, kse = 0, ksq = 0;
+  if constexpr (BAND) {
+    const int* ksr = a.key_start + (long long)b * L;
+    const int qe = min(q0 + 63, L - 1);
+    kb0 = band_clamp(ksr[q0], q0) >> 6;
+    kse = band_clamp(ksr[qe], qe);
+    ksq = qq < L ? band_clamp(ksr[qq], qq) : 0;
+  }
 
   TileRegs rq, rk, rv;
   tile_load(rq, Qb, a.ldq, q0, L, tid);
-  tile_load(rk, Kb, a.ldk, 0, L, tid);
-  tile_load(rv, Vb, a.ldv, 0, L, tid);
+  tile_load(rk, Kb, a.ldk, kb0 * 64, L, tid);
+  tile_load(rv, Vb, a.ldv, kb0 * 64, L, tid);
   tile_store(sQ, rq, tid);
   tile_store(sK2[0], rk, tid);
   tile_store(sV2[0], rv, tid);
   const int nkb = (L + 63) / 64;
   const int nk = CAUSAL ? min(nkb, xt + 1) : nkb;   // key tiles this block visits (causal: 0 .. xt)
-  if (nk > 1) {
-    tile_load(rk, Kb, a.ldk, 64, L, tid);
-    tile_load(rv, Vb, a.ldv, 64, L, tid);
+  if (nk > kb0 + 1) {
+    tile_load(rk, Kb, a.ldk, (kb0 + 1) * 64, L, tid);
+    tile_load(rv, Vb, a.ldv, (kb0 + 1) * 64, L, tid);
   }
   __syncthreads();
   const bf16x8_t qf0 = frag_rows(sQ, 16 * w, 0, lane), qf1 = frag_rows(sQ, 16 * w, 1, lane);
-  const int qq = q0 + 16 * w + (lane & 15);   // this lane's query
 
   float m2 = -INFINITY, lsum = 0.f;
   f32x4_t acc[4];
 #pragma unroll
   for (int d = 0; d < 4; ++d) acc[d] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
-  for (int kb = 0; kb < nk; ++kb) {
-    const char* sK = sK2[kb & 1];
-    const char* sV = sV2[kb & 1];
+  for (int kb = kb0; kb < nk; ++kb) {
+    const char* sK = sK2[(kb - kb0) & 1];
+    const char* sV = sV2[(kb - kb0) & 1];
     f32x4_t s[4];
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
@@ -216,7 +238,7 @@ __device__ __forceinline__ void attn_fwd_body(const AttnArgs& a) {
     }
     // bias, key tail or the causal diagonal tile: scale + bias + mask every score; otherwise
     // the max of the raw scores (scale > 0) and one fma per probability below
-    const bool gen = BIAS || kb * 64 + 64 > L || (CAUSAL && kb == xt);
+    const bool gen = BIAS || kb * 64 + 64 > L || (CAUSAL && kb == xt) || (BAND && kb * 64 < kse);
     float mx = -INFINITY;
     if (gen) {
       const int lim = qq - kb * 64 - 4 * g;   // causal: 16t + i > lim is a key past the query
@@ -229,6 +251,7 @@ __device__ __forceinline__ void attn_fwd_body(const AttnArgs& a) {
           if (BIAS && key < L) v += bias[key] * LOG2E;
           if (key >= L) v = -INFINITY;
           if (CAUSAL && 16 * t + i > lim) v = -INFINITY;
+          if (BAND && key < ksq) v = -INFINITY;
           s[t][i] = v;
           mx = fmaxf(mx, v);
         }
@@ -283,8 +306,8 @@ __device__ __forceinline__ void attn_fwd_body(const AttnArgs& a) {
       acc[d] = MFMA16(frag_tr(sV, 16 * d, 1, lane), p1, acc[d]);
     }
     if (kb + 1 < nk) {   // buffer (kb+1)&1 last held tile kb-1: every wave left it at the last barrier
-      tile_store(sK2[(kb + 1) & 1], rk, tid);
-      tile_store(sV2[(kb + 1) & 1], rv, tid);
+      tile_store(sK2[(kb + 1 - kb0) & 1], rk, tid);
+      tile_store(sV2[(kb + 1 - kb0) & 1], rv, tid);
       if (kb + 2 < nk) {
         tile_load(rk, Kb, a.ldk, (kb + 2) * 64, L, tid);
         tile_load(rv, Vb, a.ldv, (kb + 2) * 64, L, tid);
@@ -312,13 +335,18 @@ template <int OCC, int DM, bool BIAS, bool CAUSAL>
 __global__ __launch_bounds__(256, OCC) void k_attn_gqa_fwd(AttnArgs a) {
   attn_fwd_body<DM, BIAS, CAUSAL, true>(a);
 }
+template <int OCC, bool BIAS>
+__global__ __launch_bounds__(256, OCC) void k_attn_gqa_band_fwd(AttnArgs a) {
+  attn_fwd_body<0, BIAS, true, true, true>(a);
+}
 
 // ------------------------------------------------------------------------------ backward: dQ (+D)
 // DM: dropout mode (0 none, 1 the forward's keep bits, 2 re-hashed), BIAS: additive key bias —
 // compile-time, so the per-probability code carries no uniform branches (a branch per element
 // was a scheduling barrier between the VALU work and the MFMAs around it)
-template <int DM, bool BIAS, bool CAUSAL, bool GQA>
+template <int DM, bool BIAS, bool CAUSAL, bool GQA, bool BAND = false>
 __device__ __forceinline__ void attn_bwd_dq_body(const AttnArgs& a) {
+  static_assert(!BAND || (CAUSAL && GQA && DM == 0), "BAND: causal grouped-query without dropout");
   __shared__ __attribute__((aligned(16))) char sK2[2][8192];   // K/V double-buffered (k_attn_fwd)
   __shared__ __attribute__((aligned(16))) char sV2[2][8192];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, g = lane >> 4;
@@ -360,16 +388,24 @@ __device__ __forceinline__ void attn_bwd_dq_body(const AttnArgs& a) {
   f32x4_t acc[4];
 #pragma unroll
   for (int d = 0; d < 4; ++d) acc[d] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+  int kb0 = 0, kse = 0, ksq = 0;   // BAND: as in attn_fwd_body
+  if constexpr (BAND) {
+    const int* ksr = a.key_start + (long long)b * L;
+    const int q0 = xt * 64, qe = min(q0 + 63, L - 1);
+    kb0 = band_clamp(ksr[q0], q0) >> 6;
+    kse = band_clamp(ksr[qe], qe);
+    ksq = qok ? band_clamp(ksr[q], q) : 0;
+  }
   TileRegs rk, rv;
-  tile_load(rk, Kb, a.ldk, 0, L, tid);
-  tile_load(rv, Vb, a.ldv, 0, L, tid);
+  tile_load(rk, Kb, a.ldk, kb0 * 64, L, tid);
+  tile_load(rv, Vb, a.ldv, kb0 * 64, L, tid);
   const int nkb = (L + 63) / 64;
   const int nk = CAUSAL ? min(nkb, xt + 1) : nkb;   // key tiles this block visits (k_attn_fwd)
   tile_store(sK2[0], rk, tid);
   tile_store(sV2[0], rv, tid);
-  if (nk > 1) {
-    tile_load(rk, Kb, a.ldk, 64, L, tid);
-    tile_load(rv, Vb, a.ldv, 64, L, tid);
+  if (nk > kb0 + 1) {
+    tile_load(rk, Kb, a.ldk, (kb0 + 1) * 64, L, tid);
+    tile_load(rv, Vb, a.ldv, (kb0 + 1) * 64, L, tid);
   }
   __syncthreads();
   // this lane's u16 of the stored keep bits for key tile kb (Drop), prefetched with K/V
@@ -378,9 +414,9 @@ __device__ __forceinline__ void attn_bwd_dq_body(const AttnArgs& a) {
       reinterpret_cast<const unsigned short*>(a.keep + ((long long)bh * nkb * (nkb * 64) + (qok ? q : 0)) * 8 + 2 * g);
   const long long kstride = (long long)nkb * 64 * 4;   // u16 units per key tile
   unsigned knext = kbits ? kp16[0] : 0xFFFFu;
-  for (int kb = 0; kb < nk; ++kb) {
-    const char* sK = sK2[kb & 1];
-    const char* sV = sV2[kb & 1];
+  for (int kb = kb0; kb < nk; ++kb) {
+    const char* sK = sK2[(kb - kb0) & 1];
+    const char* sV = sV2[(kb - kb0) & 1];
     unsigned bits = knext;
     if (kbits && kb + 1 < nk) knext = kp16[(kb + 1) * kstride];
     if constexpr (DM == 2) bits = drop.bits16(q, kb * 64 + 4 * g);
@@ -396,7 +432,7 @@ __device__ __forceinline__ void attn_bwd_dq_body(const AttnArgs& a) {
     }
     // dS = P (.) (dP (.) Z/(1-p) - D); bias / key tail / causal diagonal only on the general
     // path.  A masked probability (key > q) is exactly 0: the LSE excludes it
-    const bool gen = BIAS || kb * 64 + 64 > L || (CAUSAL && kb == xt);
+    const bool gen = BIAS || kb * 64 + 64 > L || (CAUSAL && kb == xt) || (BAND && kb * 64 < kse);
     const int lim = q - kb * 64 - 4 * g;   // causal: 16t + i > lim is a key past the query
 #pragma unroll
     for (int t = 0; t < 4; ++t)
@@ -407,7 +443,7 @@ __device__ __forceinline__ void attn_bwd_dq_body(const AttnArgs& a) {
         if (gen) {
           float v = s[t][i] * sl2;
           if (BIAS && key < L) v += bias[key] * LOG2E;
-          if (key < L && !(CAUSAL && 16 * t + i > lim)) p = fexp2(v - lse);
+          if (key < L && !(CAUSAL && 16 * t + i > lim) && !(BAND && key < ksq)) p = fexp2(v - lse);
         } else {
           p = fexp2(fmaf(s[t][i], sl2, -lse));
         }
@@ -425,8 +461,8 @@ __device__ __forceinline__ void attn_bwd_dq_body(const AttnArgs& a) {
       acc[d] = MFMA16(frag_tr(sK, 16 * d, 1, lane), d1, acc[d]);
     }
     if (kb + 1 < nk) {
-      tile_store(sK2[(kb + 1) & 1], rk, tid);
-      tile_store(sV2[(kb + 1) & 1], rv, tid);
+      tile_store(sK2[(kb + 1 - kb0) & 1], rk, tid);
+      tile_store(sV2[(kb + 1 - kb0) & 1], rv, tid);
       if (kb + 2 < nk) {
         tile_load(rk, Kb, a.ldk, (kb + 2) * 64, L, tid);
         tile_load(rv, Vb, a.ldv, (kb + 2) * 64, L, tid);
@@ -449,6 +485,10 @@ template <int OCC, int DM, bool BIAS, bool CAUSAL>
 __global__ __launch_bounds__(256, OCC) void k_attn_gqa_bwd_dq(AttnArgs a) {
   attn_bwd_dq_body<DM, BIAS, CAUSAL, true>(a);
 }
+template <int OCC, bool BIAS>
+__global__ __launch_bounds__(256, OCC) void k_attn_gqa_band_bwd_dq(AttnArgs a) {
+  attn_bwd_dq_body<0, BIAS, true, true, true>(a);
+}
 
 // ------------------------------------------------------------------------------ backward: dK, dV
 // DM / BIAS as k_attn_bwd_dq.  Without a bias the keys past L keep a zero bias: their dK / dV
@@ -462,8 +502,9 @@ __global__ __launch_bounds__(256, OCC) void k_attn_gqa_bwd_dq(AttnArgs a) {
 // Every head accumulates into the same fp32 dK / dV MFMA accumulators, rounded to bf16 once at
 // the end — no atomics, no partial buffers, a fixed summation order (bit-reproducible).  With
 // G = 1 the sequence is the query-tile loop of before, step for step.
-template <int DM, bool BIAS, bool CAUSAL, bool GQA>
+template <int DM, bool BIAS, bool CAUSAL, bool GQA, bool BAND = false>
 __device__ __forceinline__ void attn_bwd_dkv_body(const AttnArgs& a) {
+  static_assert(!BAND || (CAUSAL && GQA && DM == 0), "BAND: causal grouped-query without dropout");
   // double-buffered like k_attn_fwd: Q, dO, LSE, D and the keep bits of a query tile
   __shared__ __attribute__((aligned(16))) char sQ2[2][8192];
   __shared__ __attribute__((aligned(16))) char sO2[2][8192];  // dO tile
@@ -472,6 +513,7 @@ __device__ __forceinline__ void attn_bwd_dkv_body(const AttnArgs& a) {
   // keep bits: the tile's 64 u64 words as two planes of 32-bit halves, sM2[j][half][q], so a
   // lane's four queries 16t + 4g + i are one ds_read_b128 (like LSE and D)
   __shared__ __attribute__((aligned(16))) unsigned sM2[2][2][64];
+  __shared__ __attribute__((aligned(16))) int sS2[2][BAND ? 64 : 4];   // BAND: the tile's key_start
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, g = lane >> 4;
   int xt, bkv;   // bkv: b * Hkv + K/V head (G = 1: the query bh)
   attn_blk(a, xt, bkv);
@@ -506,9 +548,13 @@ __device__ __forceinline__ void attn_bwd_dkv_body(const AttnArgs& a) {
   uint4 mnext = make_uint4(0, 0, 0, 0);
   // causal: query tiles xt .. nqb-1 (earlier queries never see this key tile)
   const int qs = CAUSAL ? xt : 0;
+  // BAND: the walk ends with the last query that still sees this block's last key (> qs tiles)
+  const int* ksr = BAND ? a.key_start + (long long)b * L : nullptr;
+  const int qe = BAND ? (band_end(ksr, min(xt * 64 + 63, L - 1), L, lane) + 63) >> 6 : nqb;
+  int pks = 0;
   // the walk: step it = (head in group fh, query tile fq), tile fastest; fetch() requests the
   // next step's operands and moves on, across the head boundary too
-  const int nit = GQA ? G * (nqb - qs) : nqb - qs;
+  const int nit = GQA ? G * (qe - qs) : qe - qs;
   int fh = 0, fq = qs;
   auto fetch = [&]() {
     const int nq0 = fq * 64, bh = bh0 + fh;
@@ -518,16 +564,20 @@ __device__ __forceinline__ void attn_bwd_dkv_body(const AttnArgs& a) {
       const int qq = nq0 + tid;
       pl = qq < L ? a.lse[(long long)bh * L + qq] : INFINITY;
       pd = qq < L ? a.dsum[(long long)bh * L + qq] : 0.f;
+      if constexpr (BAND) pks = qq < L ? band_clamp(ksr[qq], qq) : 0;
     }
     if (kbits && tid < 32)
       mnext = reinterpret_cast<const uint4*>(a.keep + ((long long)bh * nqb + xt) * (nqb * 64) * 8)[fq * 32 + tid];
     ++fq;
-    if (GQA && fq == nqb) { fq = qs; ++fh; }
+    if (GQA && fq == qe) { fq = qs; ++fh; }
   };
   auto stage = [&](int j) {
     tile_store(sQ2[j], rq, tid);
     tile_store(sO2[j], ro, tid);
     if (tid < 64) { sL2[j][tid] = pl; sD2[j][tid] = pd; }
+    if constexpr (BAND) {
+      if (tid < 64) sS2[j][tid] = pks;
+    }
     if (kbits && tid < 32) {   // words 2tid, 2tid+1 = (mnext.x, .y), (mnext.z, .w)
       *reinterpret_cast<uint2*>(&sM2[j][0][2 * tid]) = make_uint2(mnext.x, mnext.z);
       *reinterpret_cast<uint2*>(&sM2[j][1][2 * tid]) = make_uint2(mnext.y, mnext.w);
@@ -575,6 +625,9 @@ __device__ __forceinline__ void attn_bwd_dkv_body(const AttnArgs& a) {
         // diagonal tile: query < key is masked, its probability (and dS) exactly 0 — not
         // exp2(s - lse), the LSE excludes it
         if (CAUSAL && 16 * t + i < lim) p = 0.f;
+        if constexpr (BAND) {   // a key before the query's bound, likewise
+          if (key < sS2[cur][r]) p = 0.f;
+        }
         if constexpr (DM != 0) {
           const int m = DM == 1 ? bitmask(mv[i], kbit & 31) : drop.keep1(qb * 64 + r, key);
           // dV takes P (.) Z (1/(1-p) applied at the store), dS = P (.) (dP (.) Z/(1-p) - D)
@@ -601,7 +654,7 @@ __device__ __forceinline__ void attn_bwd_dkv_body(const AttnArgs& a) {
       __syncthreads();
     }
     ++qb;
-    if (GQA && qb == nqb) { qb = qs; ++hg; }
+    if (GQA && qb == qe) { qb = qs; ++hg; }
   }
   if (kok) {
     bf16_t* kp = a.dk + (long long)(b * L + key) * a.lddk + hk * 64;
@@ -622,6 +675,10 @@ template <int OCC, int DM, bool BIAS, bool CAUSAL>
 __global__ __launch_bounds__(256, OCC) void k_attn_gqa_bwd_dkv(AttnArgs a) {
   attn_bwd_dkv_body<DM, BIAS, CAUSAL, true>(a);
 }
+template <int OCC, bool BIAS>
+__global__ __launch_bounds__(256, OCC) void k_attn_gqa_band_bwd_dkv(AttnArgs a) {
+  attn_bwd_dkv_body<0, BIAS, true, true, true>(a);
+}
 
 }  // namespace
 
@@ -632,17 +689,26 @@ __global__ __launch_bounds__(256, OCC) void k_attn_gqa_bwd_dkv(AttnArgs a) {
 template <bool CAUSAL, bool GQA = false>
 static int attn_fwd_launch(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* out, float* lse,
                            const float* bias, int ldq, int ldk, int ldv, int ldout, int B, int H, int L, float scale,
-                           const float* ctr, int salt, float pdrop, unsigned char* keep, hipStream_t s, int G = 1) {
+                           const float* ctr, int salt, float pdrop, unsigned char* keep, hipStream_t s, int G = 1,
+                           const int* key_start = nullptr) {
   if (L <= 0 || B <= 0 || H <= 0 || ldq % 8 || ldk % 8 || ldv % 8 || ldout % 4) return (int)hipErrorInvalidValue;
   if (!aligned16(q) || !aligned16(k) || !aligned16(v)) return (int)hipErrorInvalidValue;
   AttnArgs a{};
-  a.q = q; a.k = k; a.v = v; a.out = out; a.lse = lse; a.bias = bias;
+  a.q = q; a.k = k; a.v = v; a.out = out; a.lse = lse; a.bias = bias; a.key_start = key_start;
   a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldout = ldout;
   a.B = B; a.H = H; a.L = L; a.scale = scale;
   a.ctr = ctr; a.salt = (unsigned)salt; a.pdrop = pdrop; a.xcd = 1; a.keep = keep; a.G = G;
   if (pdrop < 0.f || pdrop >= 1.f) return (int)hipErrorInvalidValue;
   const dim3 grid((L + 63) / 64, B * H);
   const bool dm = ctr != nullptr && pdrop > 0.f;
+  if constexpr (CAUSAL && GQA) {
+    if (key_start) {   // the BAND kernels: no dropout mode
+      if (dm) return (int)hipErrorInvalidValue;
+      if (bias) hipLaunchKernelGGL((k_attn_gqa_band_fwd<4, true>), grid, dim3(256), 0, s, a);
+      else hipLaunchKernelGGL((k_attn_gqa_band_fwd<4, false>), grid, dim3(256), 0, s, a);
+      KML_LAUNCH_CHECK();
+    }
+  }
 #define KML_ATTN_FWD(DM, BI)                                                                        \
   do {                                                                                              \
     if constexpr (GQA) hipLaunchKernelGGL((k_attn_gqa_fwd<4, DM, BI, CAUSAL>), grid, dim3(256), 0, s, a); \
@@ -666,12 +732,12 @@ static int attn_bwd_launch(const bf16_t* q, const bf16_t* k, const bf16_t* v, co
                            const float* lse, float* dsum, const float* bias, bf16_t* dq, bf16_t* dk, bf16_t* dv,
                            int ldq, int ldk, int ldv, int ldo, int lddo, int lddq, int lddk, int lddv, int B, int H,
                            int L, float scale, const float* ctr, int salt, float pdrop, const unsigned char* keep,
-                           hipStream_t s, int G = 1) {
+                           hipStream_t s, int G = 1, const int* key_start = nullptr) {
   if (L <= 0 || ldq % 8 || ldk % 8 || ldv % 8 || ldo % 8 || lddo % 8 || lddq % 4 || lddk % 4 || lddv % 4)
     return (int)hipErrorInvalidValue;
   AttnArgs a{};
   a.q = q; a.k = k; a.v = v; a.o = o; a.dout = dout; a.lse = const_cast<float*>(lse); a.dsum = dsum;
-  a.bias = bias; a.dq = dq; a.dk = dk; a.dv = dv;
+  a.bias = bias; a.key_start = key_start; a.dq = dq; a.dk = dk; a.dv = dv;
   a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo; a.lddo = lddo; a.lddq = lddq; a.lddk = lddk; a.lddv = lddv;
   a.B = B; a.H = H; a.L = L; a.scale = scale;
   a.ctr = ctr; a.salt = (unsigned)salt; a.pdrop = pdrop; a.xcd = 1;
@@ -684,6 +750,19 @@ static int attn_bwd_launch(const bf16_t* q, const bf16_t* k, const bf16_t* v, co
   // (124 VGPRs, no spills), dKV at 2 (~211 VGPRs; 3 spills and doubles its time)
   const int dm = (ctr == nullptr || pdrop <= 0.f) ? 0 : (keep != nullptr ? 1 : 2);
   constexpr int DKV_OCC = 3;
+  if constexpr (CAUSAL && GQA) {
+    if (key_start) {   // the BAND kernels: no dropout mode, the budgets of DM 0
+      if (dm) return (int)hipErrorInvalidValue;
+      if (bias) {
+        hipLaunchKernelGGL((k_attn_gqa_band_bwd_dq<4, true>), grid, dim3(256), 0, s, a);
+        hipLaunchKernelGGL((k_attn_gqa_band_bwd_dkv<DKV_OCC, true>), grid_kv, dim3(256), 0, s, a);
+      } else {
+        hipLaunchKernelGGL((k_attn_gqa_band_bwd_dq<4, false>), grid, dim3(256), 0, s, a);
+        hipLaunchKernelGGL((k_attn_gqa_band_bwd_dkv<DKV_OCC, false>), grid_kv, dim3(256), 0, s, a);
+      }
+      KML_LAUNCH_CHECK();
+    }
+  }
   // causal re-hash mode (DM 2: the hash and the diagonal mask live together): one wave per SIMD
   // less, so that no causal instantiation spills (profiles/r11/causal_attention.md)
 #define KML_ATTN_BWD(DM, BI)                                                                             \
@@ -774,4 +853,26 @@ KML_API int kml_attn_gqa_bwd(const bf16_t* q, const bf16_t* k, const bf16_t* v, 
   if (G == 1) return causal ? KML_GQA_BWD(true, false) : KML_GQA_BWD(false, false);
   return causal ? KML_GQA_BWD(true, true) : KML_GQA_BWD(false, true);
 #undef KML_GQA_BWD
+}
+
+// Causal grouped-query attention with a per-query key start (the BAND kernels): key_start int32
+// [B, L] on the device, query t attends keys key_start[b][t] .. t; 0 <= key_start[b][t] <= t,
+// non-decreasing in t (values are clamped to [0, t] as read).  The other arguments as
+// kml_attn_gqa_fwd / _bwd; Hkv == H runs the grouped-query kernels with groups of one; no dropout.
+KML_API int kml_attn_gqa_band_fwd(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* out, float* lse,
+                                  const float* bias, const int* key_start, int ldq, int ldk, int ldv, int ldout,
+                                  int B, int H, int Hkv, int L, float scale, hipStream_t s) {
+  if (!key_start || H <= 0 || Hkv <= 0 || H % Hkv) return (int)hipErrorInvalidValue;
+  return attn_fwd_launch<true, true>(q, k, v, out, lse, bias, ldq, ldk, ldv, ldout, B, H, L, scale, nullptr, 0, 0.f,
+                                     nullptr, s, H / Hkv, key_start);
+}
+
+KML_API int kml_attn_gqa_band_bwd(const bf16_t* q, const bf16_t* k, const bf16_t* v, const bf16_t* o,
+                                  const bf16_t* dout, const float* lse, float* dsum, const float* bias,
+                                  const int* key_start, bf16_t* dq, bf16_t* dk, bf16_t* dv, int ldq, int ldk, int ldv,
+                                  int ldo, int lddo, int lddq, int lddk, int lddv, int B, int H, int Hkv, int L,
+                                  float scale, hipStream_t s) {
+  if (!key_start || B <= 0 || H <= 0 || Hkv <= 0 || H % Hkv) return (int)hipErrorInvalidValue;
+  return attn_bwd_launch<true, true>(q, k, v, o, dout, lse, dsum, bias, dq, dk, dv, ldq, ldk, ldv, ldo, lddo, lddq,
+                                     lddk, lddv, B, H, L, scale, nullptr, 0, 0.f, nullptr, s, H / Hkv, key_start);
 }

@@ -83,9 +83,24 @@ __device__ __forceinline__ bf16x8_t frag_tr(const char* lds, int col0, int lane)
   return f;
 }
 
+// BAND (causal, kml_attn128_band_fwd / _bwd): query t attends keys key_start[b][t] .. t, key_start
+// non-decreasing along a sequence — the first row of t's document in a packed batch, or
+// max(0, t - W + 1) for a window.  Every bound is read from device memory (the grid does not depend
+// on it) and clamped to [0, t].
+//   fwd / dQ : the walk starts at tile kb0 = key_start[q0] / 32, the block's minimum, and the double
+//              buffer's parity runs on kb - kb0.  Tiles that begin before key_start of the block's
+//              last query take the general path, where a key before the lane's own bound scores
+//              -inf (dQ: probability exactly 0) like a key past the query; the tiles between those
+//              and the diagonal keep the fast path.  A row always sees its own key: no empty rows.
+//   dKV      : the walk ends at the tile of the last query whose bound is not past the block's last
+//              key (band_end: a 64-ary search of the monotone row by every wave, so block-uniform);
+//              the tile's bounds are staged with its LSE and D.
+// With key_start = 0 every BAND kernel does the arithmetic of its CAUSAL twin in the same order.
+
 // ------------------------------------------------------------------------------ forward
-template <bool BIAS, bool CAUSAL, bool GQA>
+template <bool BIAS, bool CAUSAL, bool GQA, bool BAND = false>
 __global__ __launch_bounds__(256, 4) void k_attn128_fwd(AttnArgs a) {
+  static_assert(!BAND || CAUSAL, "BAND narrows the causal triangle");
   __shared__ __attribute__((aligned(16))) char sK2[2][TR * 256];
   __shared__ __attribute__((aligned(16))) char sV2[2][TR * 256];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, g = lane >> 4;
@@ -100,10 +115,19 @@ __global__ __launch_bounds__(256, 4) void k_attn128_fwd(AttnArgs a) {
   const bf16_t* Vb = a.v + (long long)b * L * a.ldv + hk * HD;
   const float sl2 = a.scale * LOG2E;
   const float* bias = BIAS ? a.bias + (long long)b * L : nullptr;
+  // BAND: first tile of the walk, the bound of the block's last query, this lane's own bound
+  int kb0 = 0, kse = 0, ksq = 0;
+  if constexpr (BAND) {
+    const int* ksr = a.key_start + (long long)b * L;
+    const int qe = min(q0 + 63, L - 1);
+    kb0 = band_clamp(ksr[q0], q0) / TR;
+    kse = band_clamp(ksr[qe], qe);
+    ksq = qok ? band_clamp(ksr[qq], qq) : 0;
+  }
 
   TileRegs rk, rv;
-  tile_load(rk, Kb, a.ldk, 0, L, tid);
-  tile_load(rv, Vb, a.ldv, 0, L, tid);
+  tile_load(rk, Kb, a.ldk, kb0 * TR, L, tid);
+  tile_load(rv, Vb, a.ldv, kb0 * TR, L, tid);
   // Q: this lane's row as the B operand of the 4 k-steps, straight from global
   const bf16_t* qrow = a.q + (long long)(b * L + (qok ? qq : 0)) * a.ldq + h * HD;
   bf16x8_t qf[4];
@@ -113,9 +137,9 @@ __global__ __launch_bounds__(256, 4) void k_attn128_fwd(AttnArgs a) {
   tile_store(sV2[0], rv, tid);
   const int nkb = (L + TR - 1) / TR;
   const int nk = CAUSAL ? min(nkb, 2 * xt + 2) : nkb;   // key tiles this block visits (causal: keys < q0 + 64)
-  if (nk > 1) {
-    tile_load(rk, Kb, a.ldk, TR, L, tid);
-    tile_load(rv, Vb, a.ldv, TR, L, tid);
+  if (nk > kb0 + 1) {
+    tile_load(rk, Kb, a.ldk, (kb0 + 1) * TR, L, tid);
+    tile_load(rv, Vb, a.ldv, (kb0 + 1) * TR, L, tid);
   }
   __syncthreads();
 
@@ -124,9 +148,9 @@ __global__ __launch_bounds__(256, 4) void k_attn128_fwd(AttnArgs a) {
 #pragma unroll
   for (int d = 0; d < 8; ++d) acc[d] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
-  for (int kb = 0; kb < nk; ++kb) {
-    const char* sK = sK2[kb & 1];
-    const char* sV = sV2[kb & 1];
+  for (int kb = kb0; kb < nk; ++kb) {
+    const char* sK = sK2[(kb - kb0) & 1];
+    const char* sV = sV2[(kb - kb0) & 1];
     f32x4_t s[2];
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
@@ -136,7 +160,7 @@ __global__ __launch_bounds__(256, 4) void k_attn128_fwd(AttnArgs a) {
     }
     // bias, key tail or a tile on the causal diagonal: scale + bias + mask every score; otherwise
     // the max of the raw scores (scale > 0) and one fma per probability below
-    const bool gen = BIAS || kb * TR + TR > L || (CAUSAL && kb * TR + TR - 1 > q0);
+    const bool gen = BIAS || kb * TR + TR > L || (CAUSAL && kb * TR + TR - 1 > q0) || (BAND && kb * TR < kse);
     float mx = -INFINITY;
     if (gen) {
       const int lim = qq - kb * TR - 4 * g;   // causal: 16t + i > lim is a key past the query
@@ -149,6 +173,7 @@ __global__ __launch_bounds__(256, 4) void k_attn128_fwd(AttnArgs a) {
           if (BIAS && key < L) v += bias[key] * LOG2E;
           if (key >= L) v = -INFINITY;
           if (CAUSAL && 16 * t + i > lim) v = -INFINITY;
+          if (BAND && key < ksq) v = -INFINITY;
           s[t][i] = v;
           mx = fmaxf(mx, v);
         }
@@ -187,8 +212,8 @@ __global__ __launch_bounds__(256, 4) void k_attn128_fwd(AttnArgs a) {
 #pragma unroll
     for (int d = 0; d < 8; ++d) acc[d] = MFMA16(frag_tr(sV, 16 * d, lane), p, acc[d]);
     if (kb + 1 < nk) {   // buffer (kb+1)&1 last held tile kb-1: every wave left it at the last barrier
-      tile_store(sK2[(kb + 1) & 1], rk, tid);
-      tile_store(sV2[(kb + 1) & 1], rv, tid);
+      tile_store(sK2[(kb + 1 - kb0) & 1], rk, tid);
+      tile_store(sV2[(kb + 1 - kb0) & 1], rv, tid);
       if (kb + 2 < nk) {
         tile_load(rk, Kb, a.ldk, (kb + 2) * TR, L, tid);
         tile_load(rv, Vb, a.ldv, (kb + 2) * TR, L, tid);
@@ -208,8 +233,9 @@ __global__ __launch_bounds__(256, 4) void k_attn128_fwd(AttnArgs a) {
 }
 
 // ------------------------------------------------------------------------------ backward: dQ (+D)
-template <bool BIAS, bool CAUSAL, bool GQA>
+template <bool BIAS, bool CAUSAL, bool GQA, bool BAND = false>
 __global__ __launch_bounds__(256, 3) void k_attn128_bwd_dq(AttnArgs a) {
+  static_assert(!BAND || CAUSAL, "BAND narrows the causal triangle");
   __shared__ __attribute__((aligned(16))) char sK2[2][TR * 256];
   __shared__ __attribute__((aligned(16))) char sV2[2][TR * 256];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, g = lane >> 4;
@@ -224,10 +250,18 @@ __global__ __launch_bounds__(256, 3) void k_attn128_bwd_dq(AttnArgs a) {
   const bf16_t* Vb = a.v + (long long)b * L * a.ldv + hk * HD;
   const float sl2 = a.scale * LOG2E;
   const float* bias = BIAS ? a.bias + (long long)b * L : nullptr;
+  int kb0 = 0, kse = 0, ksq = 0;   // BAND: as in k_attn128_fwd
+  if constexpr (BAND) {
+    const int* ksr = a.key_start + (long long)b * L;
+    const int qe = min(q0 + 63, L - 1);
+    kb0 = band_clamp(ksr[q0], q0) / TR;
+    kse = band_clamp(ksr[qe], qe);
+    ksq = qok ? band_clamp(ksr[q], q) : 0;
+  }
 
   TileRegs rk, rv;
-  tile_load(rk, Kb, a.ldk, 0, L, tid);
-  tile_load(rv, Vb, a.ldv, 0, L, tid);
+  tile_load(rk, Kb, a.ldk, kb0 * TR, L, tid);
+  tile_load(rv, Vb, a.ldv, kb0 * TR, L, tid);
   const bf16_t* qrow = a.q + (long long)(b * L + (qok ? q : 0)) * a.ldq + h * HD;
   const bf16_t* dorow = a.dout + (long long)(b * L + (qok ? q : 0)) * a.lddo + h * HD;
   const bf16_t* orow = a.o + (long long)(b * L + (qok ? q : 0)) * a.ldo + h * HD;
@@ -260,14 +294,14 @@ __global__ __launch_bounds__(256, 3) void k_attn128_bwd_dq(AttnArgs a) {
   const int nk = CAUSAL ? min(nkb, 2 * xt + 2) : nkb;   // key tiles this block visits (k_attn128_fwd)
   tile_store(sK2[0], rk, tid);
   tile_store(sV2[0], rv, tid);
-  if (nk > 1) {
-    tile_load(rk, Kb, a.ldk, TR, L, tid);
-    tile_load(rv, Vb, a.ldv, TR, L, tid);
+  if (nk > kb0 + 1) {
+    tile_load(rk, Kb, a.ldk, (kb0 + 1) * TR, L, tid);
+    tile_load(rv, Vb, a.ldv, (kb0 + 1) * TR, L, tid);
   }
   __syncthreads();
-  for (int kb = 0; kb < nk; ++kb) {
-    const char* sK = sK2[kb & 1];
-    const char* sV = sV2[kb & 1];
+  for (int kb = kb0; kb < nk; ++kb) {
+    const char* sK = sK2[(kb - kb0) & 1];
+    const char* sV = sV2[(kb - kb0) & 1];
     f32x4_t s[2], dp[2];
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
@@ -281,7 +315,7 @@ __global__ __launch_bounds__(256, 3) void k_attn128_bwd_dq(AttnArgs a) {
     }
     // dS = P (.) (dP - D); bias / key tail / causal diagonal only on the general path.  A masked
     // probability (key > q) is exactly 0: the LSE excludes it
-    const bool gen = BIAS || kb * TR + TR > L || (CAUSAL && kb * TR + TR - 1 > q0);
+    const bool gen = BIAS || kb * TR + TR > L || (CAUSAL && kb * TR + TR - 1 > q0) || (BAND && kb * TR < kse);
     const int lim = q - kb * TR - 4 * g;   // causal: 16t + i > lim is a key past the query
 #pragma unroll
     for (int t = 0; t < 2; ++t)
@@ -292,7 +326,7 @@ __global__ __launch_bounds__(256, 3) void k_attn128_bwd_dq(AttnArgs a) {
         if (gen) {
           float v = s[t][i] * sl2;
           if (BIAS && key < L) v += bias[key] * LOG2E;
-          if (key < L && !(CAUSAL && 16 * t + i > lim)) p = fexp2(v - lse);
+          if (key < L && !(CAUSAL && 16 * t + i > lim) && !(BAND && key < ksq)) p = fexp2(v - lse);
         } else {
           p = fexp2(fmaf(s[t][i], sl2, -lse));
         }
@@ -302,8 +336,8 @@ __global__ __launch_bounds__(256, 3) void k_attn128_bwd_dq(AttnArgs a) {
 #pragma unroll
     for (int d = 0; d < 8; ++d) acc[d] = MFMA16(frag_tr(sK, 16 * d, lane), ds, acc[d]);
     if (kb + 1 < nk) {
-      tile_store(sK2[(kb + 1) & 1], rk, tid);
-      tile_store(sV2[(kb + 1) & 1], rv, tid);
+      tile_store(sK2[(kb + 1 - kb0) & 1], rk, tid);
+      tile_store(sV2[(kb + 1 - kb0) & 1], rv, tid);
       if (kb + 2 < nk) {
         tile_load(rk, Kb, a.ldk, (kb + 2) * TR, L, tid);
         tile_load(rv, Vb, a.ldv, (kb + 2) * TR, L, tid);
@@ -326,12 +360,14 @@ __global__ __launch_bounds__(256, 3) void k_attn128_bwd_dq(AttnArgs a) {
 // same fp32 accumulators, rounded to bf16 once at the end: a fixed order, bit-reproducible.
 // Without a bias the keys past L score 0 instead of -inf: their rows are never stored and no other
 // key's rows read them.
-template <bool BIAS, bool CAUSAL, bool GQA>
+template <bool BIAS, bool CAUSAL, bool GQA, bool BAND = false>
 __global__ __launch_bounds__(256, 2) void k_attn128_bwd_dkv(AttnArgs a) {
+  static_assert(!BAND || CAUSAL, "BAND narrows the causal triangle");
   __shared__ __attribute__((aligned(16))) char sQ2[2][TR * 256];
   __shared__ __attribute__((aligned(16))) char sO2[2][TR * 256];   // dO tile
   __shared__ __attribute__((aligned(16))) float sL2[2][TR];
   __shared__ __attribute__((aligned(16))) float sD2[2][TR];
+  __shared__ __attribute__((aligned(16))) int sS2[2][BAND ? TR : 4];   // BAND: the tile's key_start
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, g = lane >> 4;
   int xt, bkv;   // bkv: b * Hkv + K/V head
   attn_blk(a, xt, bkv);
@@ -360,9 +396,13 @@ __global__ __launch_bounds__(256, 2) void k_attn128_bwd_dkv(AttnArgs a) {
   for (int d = 0; d < 8; ++d) { adk[d] = f32x4_t{0.f, 0.f, 0.f, 0.f}; adv[d] = adk[d]; }
   const int nqb = (L + TR - 1) / TR;
   const int qs = CAUSAL ? 2 * xt : 0;   // 64 xt < L, so qs < nqb
-  const int nit = G * (nqb - qs);
+  // BAND: the walk ends with the last query that still sees this block's last key (> qs tiles)
+  const int* ksr = BAND ? a.key_start + (long long)b * L : nullptr;
+  const int qe = BAND ? (band_end(ksr, min(xt * 64 + 63, L - 1), L, lane) + TR - 1) / TR : nqb;
+  const int nit = G * (qe - qs);
   TileRegs rq, ro;
   float pl = 0.f, pd = 0.f;
+  int pks = 0;
   int fh = 0, fq = qs;
   auto fetch = [&]() {   // request the next step's operands and move on, across the head boundary too
     const int nq0 = fq * TR, bh = bh0 + fh;
@@ -372,14 +412,19 @@ __global__ __launch_bounds__(256, 2) void k_attn128_bwd_dkv(AttnArgs a) {
       const int qq = nq0 + tid;
       pl = qq < L ? a.lse[(long long)bh * L + qq] : INFINITY;
       pd = qq < L ? a.dsum[(long long)bh * L + qq] : 0.f;
+      if constexpr (BAND) pks = qq < L ? band_clamp(ksr[qq], qq) : 0;
     }
     ++fq;
-    if (GQA && fq == nqb) { fq = qs; ++fh; }
+    if (GQA && fq == qe) { fq = qs; ++fh; }
   };
   auto stage = [&](int j) {
     tile_store(sQ2[j], rq, tid);
     tile_store(sO2[j], ro, tid);
-    if (tid < TR) { sL2[j][tid] = pl; sD2[j][tid] = pd; }
+    if (tid < TR) {
+      sL2[j][tid] = pl;
+      sD2[j][tid] = pd;
+      if constexpr (BAND) sS2[j][tid] = pks;
+    }
   };
   fetch();
   stage(0);
@@ -411,11 +456,14 @@ __global__ __launch_bounds__(256, 2) void k_attn128_bwd_dkv(AttnArgs a) {
       const float4 l4 = *reinterpret_cast<const float4*>(sL + 16 * t + 4 * g);
       const float4 d4 = *reinterpret_cast<const float4*>(sD + 16 * t + 4 * g);
       const float lv[4] = {l4.x, l4.y, l4.z, l4.w}, dv[4] = {d4.x, d4.y, d4.z, d4.w};
+      const int4 s4 = BAND ? *reinterpret_cast<const int4*>(sS2[cur] + 16 * t + 4 * g) : make_int4(0, 0, 0, 0);
+      const int sv[4] = {s4.x, s4.y, s4.z, s4.w};
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         float p = fexp2(fmaf(s[t][i], sl2, BIAS ? kb2 - lv[i] : -lv[i]));
         // diagonal: query < key is masked, its probability (and dS) exactly 0 — the LSE excludes it
         if (CAUSAL && 16 * t + i < lim) p = 0.f;
+        if (BAND && key < sv[i]) p = 0.f;   // a key before the query's bound, likewise
         s[t][i] = p;
         dp[t][i] = p * (dp[t][i] - dv[i]);
       }
@@ -432,7 +480,7 @@ __global__ __launch_bounds__(256, 2) void k_attn128_bwd_dkv(AttnArgs a) {
       __syncthreads();
     }
     ++qb;
-    if (GQA && qb == nqb) qb = qs;
+    if (GQA && qb == qe) qb = qs;
   }
   if (kok) {
     bf16_t* kp = a.dk + (long long)(b * L + key) * a.lddk + hk * HD;
@@ -445,26 +493,62 @@ __global__ __launch_bounds__(256, 2) void k_attn128_bwd_dkv(AttnArgs a) {
   }
 }
 
-template <bool CAUSAL, bool GQA>
+template <bool CAUSAL, bool GQA, bool BAND = false>
 int fwd_launch(const AttnArgs& a, hipStream_t s) {
   const dim3 grid((a.L + 63) / 64, a.B * a.H);
-  if (a.bias) hipLaunchKernelGGL((k_attn128_fwd<true, CAUSAL, GQA>), grid, dim3(256), 0, s, a);
-  else hipLaunchKernelGGL((k_attn128_fwd<false, CAUSAL, GQA>), grid, dim3(256), 0, s, a);
+  if (a.bias) hipLaunchKernelGGL((k_attn128_fwd<true, CAUSAL, GQA, BAND>), grid, dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((k_attn128_fwd<false, CAUSAL, GQA, BAND>), grid, dim3(256), 0, s, a);
   KML_LAUNCH_CHECK();
 }
 
-template <bool CAUSAL, bool GQA>
+template <bool CAUSAL, bool GQA, bool BAND = false>
 int bwd_launch(const AttnArgs& a, hipStream_t s) {
   const dim3 grid((a.L + 63) / 64, a.B * a.H);
   const dim3 grid_kv((a.L + 63) / 64, a.B * (a.H / a.G));   // dKV: one block per (key tile, b, K/V head)
   if (a.bias) {
-    hipLaunchKernelGGL((k_attn128_bwd_dq<true, CAUSAL, GQA>), grid, dim3(256), 0, s, a);
-    hipLaunchKernelGGL((k_attn128_bwd_dkv<true, CAUSAL, GQA>), grid_kv, dim3(256), 0, s, a);
+    hipLaunchKernelGGL((k_attn128_bwd_dq<true, CAUSAL, GQA, BAND>), grid, dim3(256), 0, s, a);
+    hipLaunchKernelGGL((k_attn128_bwd_dkv<true, CAUSAL, GQA, BAND>), grid_kv, dim3(256), 0, s, a);
   } else {
-    hipLaunchKernelGGL((k_attn128_bwd_dq<false, CAUSAL, GQA>), grid, dim3(256), 0, s, a);
-    hipLaunchKernelGGL((k_attn128_bwd_dkv<false, CAUSAL, GQA>), grid_kv, dim3(256), 0, s, a);
+    hipLaunchKernelGGL((k_attn128_bwd_dq<false, CAUSAL, GQA, BAND>), grid, dim3(256), 0, s, a);
+    hipLaunchKernelGGL((k_attn128_bwd_dkv<false, CAUSAL, GQA, BAND>), grid_kv, dim3(256), 0, s, a);
   }
   KML_LAUNCH_CHECK();
+}
+
+// the argument checks and the launch table of kml_attn128_fwd / kml_attn128_band_fwd.  key_start:
+// the BAND kernels (causal; the grouped-query instantiation serves Hkv == H too, with G = 1)
+int fwd128(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* out, float* lse, const float* bias,
+           const int* key_start, int ldq, int ldk, int ldv, int ldout, int B, int H, int Hkv, int L, float scale,
+           int causal, hipStream_t s) {
+  if (B <= 0 || L <= 0 || H <= 0 || Hkv <= 0 || H % Hkv) return (int)hipErrorInvalidValue;
+  if (ldq % 8 || ldk % 8 || ldv % 8 || ldout % 4 || !aligned16(q) || !aligned16(k) || !aligned16(v))
+    return (int)hipErrorInvalidValue;
+  AttnArgs a{};
+  a.q = q; a.k = k; a.v = v; a.out = out; a.lse = lse; a.bias = bias; a.key_start = key_start;
+  a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldout = ldout;
+  a.B = B; a.H = H; a.L = L; a.scale = scale; a.xcd = 1; a.G = H / Hkv;
+  if (key_start) return fwd_launch<true, true, true>(a, s);
+  if (a.G == 1) return causal ? fwd_launch<true, false>(a, s) : fwd_launch<false, false>(a, s);
+  return causal ? fwd_launch<true, true>(a, s) : fwd_launch<false, true>(a, s);
+}
+
+int bwd128(const bf16_t* q, const bf16_t* k, const bf16_t* v, const bf16_t* o, const bf16_t* dout, const float* lse,
+           float* dsum, const float* bias, const int* key_start, bf16_t* dq, bf16_t* dk, bf16_t* dv, int ldq, int ldk,
+           int ldv, int ldo, int lddo, int lddq, int lddk, int lddv, int B, int H, int Hkv, int L, float scale,
+           int causal, hipStream_t s) {
+  if (B <= 0 || L <= 0 || H <= 0 || Hkv <= 0 || H % Hkv) return (int)hipErrorInvalidValue;
+  if (ldq % 8 || ldk % 8 || ldv % 8 || ldo % 8 || lddo % 8 || lddq % 4 || lddk % 4 || lddv % 4)
+    return (int)hipErrorInvalidValue;
+  if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(o) || !aligned16(dout))
+    return (int)hipErrorInvalidValue;
+  AttnArgs a{};
+  a.q = q; a.k = k; a.v = v; a.o = o; a.dout = dout; a.lse = const_cast<float*>(lse); a.dsum = dsum;
+  a.bias = bias; a.key_start = key_start; a.dq = dq; a.dk = dk; a.dv = dv;
+  a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo; a.lddo = lddo; a.lddq = lddq; a.lddk = lddk; a.lddv = lddv;
+  a.B = B; a.H = H; a.L = L; a.scale = scale; a.xcd = 1; a.G = H / Hkv;
+  if (key_start) return bwd_launch<true, true, true>(a, s);
+  if (a.G == 1) return causal ? bwd_launch<true, false>(a, s) : bwd_launch<false, false>(a, s);
+  return causal ? bwd_launch<true, true>(a, s) : bwd_launch<false, true>(a, s);
 }
 
 }  // namespace
@@ -478,15 +562,18 @@ KML_API int kml_attn128_fwd(const bf16_t* q, const bf16_t* k, const bf16_t* v, b
                             float scale, const float* ctr, int salt, float pdrop, unsigned char* keep, int causal,
                             hipStream_t s) {
   (void)ctr; (void)salt; (void)keep;
-  if (!(pdrop == 0.f) || B <= 0 || L <= 0 || H <= 0 || Hkv <= 0 || H % Hkv) return (int)hipErrorInvalidValue;
-  if (ldq % 8 || ldk % 8 || ldv % 8 || ldout % 4 || !aligned16(q) || !aligned16(k) || !aligned16(v))
-    return (int)hipErrorInvalidValue;
-  AttnArgs a{};
-  a.q = q; a.k = k; a.v = v; a.out = out; a.lse = lse; a.bias = bias;
-  a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldout = ldout;
-  a.B = B; a.H = H; a.L = L; a.scale = scale; a.xcd = 1; a.G = H / Hkv;
-  if (a.G == 1) return causal ? fwd_launch<true, false>(a, s) : fwd_launch<false, false>(a, s);
-  return causal ? fwd_launch<true, true>(a, s) : fwd_launch<false, true>(a, s);
+  if (!(pdrop == 0.f)) return (int)hipErrorInvalidValue;
+  return fwd128(q, k, v, out, lse, bias, nullptr, ldq, ldk, ldv, ldout, B, H, Hkv, L, scale, causal, s);
+}
+
+// Causal attention with a per-query key start (the BAND kernels): key_start int32 [B, L] on the
+// device, query t attends keys key_start[b][t] .. t; 0 <= key_start[b][t] <= t, non-decreasing in t
+// (values are clamped to [0, t] as read).  The other arguments as kml_attn128_fwd; no dropout.
+KML_API int kml_attn128_band_fwd(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* out, float* lse,
+                                 const float* bias, const int* key_start, int ldq, int ldk, int ldv, int ldout,
+                                 int B, int H, int Hkv, int L, float scale, hipStream_t s) {
+  if (!key_start) return (int)hipErrorInvalidValue;
+  return fwd128(q, k, v, out, lse, bias, key_start, ldq, ldk, ldv, ldout, B, H, Hkv, L, scale, 1, s);
 }
 
 // Head dim 128 with the argument list of kml_attn_gqa_bwd: dq / dk / dv may point into one fused
@@ -498,16 +585,18 @@ KML_API int kml_attn128_bwd(const bf16_t* q, const bf16_t* k, const bf16_t* v, c
                             int Hkv, int L, float scale, const float* ctr, int salt, float pdrop,
                             const unsigned char* keep, int causal, hipStream_t s) {
   (void)ctr; (void)salt; (void)keep;
-  if (!(pdrop == 0.f) || B <= 0 || L <= 0 || H <= 0 || Hkv <= 0 || H % Hkv) return (int)hipErrorInvalidValue;
-  if (ldq % 8 || ldk % 8 || ldv % 8 || ldo % 8 || lddo % 8 || lddq % 4 || lddk % 4 || lddv % 4)
-    return (int)hipErrorInvalidValue;
-  if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(o) || !aligned16(dout))
-    return (int)hipErrorInvalidValue;
-  AttnArgs a{};
-  a.q = q; a.k = k; a.v = v; a.o = o; a.dout = dout; a.lse = const_cast<float*>(lse); a.dsum = dsum;
-  a.bias = bias; a.dq = dq; a.dk = dk; a.dv = dv;
-  a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo; a.lddo = lddo; a.lddq = lddq; a.lddk = lddk; a.lddv = lddv;
-  a.B = B; a.H = H; a.L = L; a.scale = scale; a.xcd = 1; a.G = H / Hkv;
-  if (a.G == 1) return causal ? bwd_launch<true, false>(a, s) : bwd_launch<false, false>(a, s);
-  return causal ? bwd_launch<true, true>(a, s) : bwd_launch<false, true>(a, s);
+  if (!(pdrop == 0.f)) return (int)hipErrorInvalidValue;
+  return bwd128(q, k, v, o, dout, lse, dsum, bias, nullptr, dq, dk, dv, ldq, ldk, ldv, ldo, lddo, lddq, lddk, lddv, B,
+                H, Hkv, L, scale, causal, s);
+}
+
+// The backward of kml_attn128_band_fwd (same key_start); the other arguments as kml_attn128_bwd.
+KML_API int kml_attn128_band_bwd(const bf16_t* q, const bf16_t* k, const bf16_t* v, const bf16_t* o,
+                                 const bf16_t* dout, const float* lse, float* dsum, const float* bias,
+                                 const int* key_start, bf16_t* dq, bf16_t* dk, bf16_t* dv, int ldq, int ldk, int ldv,
+                                 int ldo, int lddo, int lddq, int lddk, int lddv, int B, int H, int Hkv, int L,
+                                 float scale, hipStream_t s) {
+  if (!key_start) return (int)hipErrorInvalidValue;
+  return bwd128(q, k, v, o, dout, lse, dsum, bias, key_start, dq, dk, dv, ldq, ldk, ldv, ldo, lddo, lddq, lddk, lddv,
+                B, H, Hkv, L, scale, 1, s);
 }

@@ -12,7 +12,12 @@
 * gated SiLU MLP: one fused ``gate_up`` projection ``[2 I, hidden]``, ``kml_swiglu_fwd / _bwd``,
   ``down_proj``;
 * one token table (no position table), optionally tied to ``lm_head``; shifted labels and the
-  fused cross entropy as in ``GPT2LMHeadModel``.
+  fused cross entropy as in ``GPT2LMHeadModel``;
+* packed rows: ``forward(..., doc_ids=...)`` (``nn.transformer.pack_documents``) keeps attention
+  inside each document — the band variants of the attention kernels, ``kml_attn_gqa_band_fwd / _bwd``
+  and ``kml_attn128_band_fwd / _bwd``, which also skip the key tiles of earlier documents — and
+  scores no token against the next document.  Training and evaluation only: ``generate`` and the
+  decode path take one document a row.
 
 ``state_dict`` / ``load_state_dict`` split and concatenate the fused ``qkv`` / ``gate_up``
 parameters, so HF checkpoints of the family load directly.  Build from a checkpoint's
@@ -42,8 +47,8 @@ from torch.autograd import Function
 from ..nn.decode import DecodeMixin, KVCache, advance_cpu
 from ..nn.flat import grad_storage_of, shadow_of
 from ..nn.modules import Linear, _pad_nograd, cross_entropy
-from ..nn.transformer import (RMSNorm, _AttnFn, _bf, attention_reference, gather_rows, rope, rope_reference,
-                              rope_table, swiglu)
+from ..nn.transformer import (RMSNorm, _AttnFn, _bf, attention_reference, doc_key_start, gather_rows, rope,
+                              rope_reference, rope_table, swiglu)
 
 
 class _TokEmbFn(Function):
@@ -97,13 +102,15 @@ class LlamaAttention(tnn.Module):
         if all(n in sd for n in names):
             sd[prefix + "qkv.weight"] = torch.cat([sd.pop(n) for n in names], 0)
 
-    def forward(self, x, B, L, table, bias=None):
+    def forward(self, x, B, L, table, bias=None, key_start=None):
+        """key_start: int32 ``[B, L]`` of packed rows (``doc_key_start``) — a token attends its own
+        document only.  RoPE keeps the row position: its scores depend on position differences alone."""
         H, Hkv, d = self.heads, self.kv_heads, self.head_dim
         qkv = rope(self.qkv(x), table, L, H, Hkv, head_dim=d)
         if not x.is_cuda:
-            ctx = attention_reference(qkv, B, H, L, bias, causal=True, kv_heads=Hkv, head_dim=d)
+            ctx = attention_reference(qkv, B, H, L, bias, causal=True, kv_heads=Hkv, head_dim=d, key_start=key_start)
         else:
-            ctx = _AttnFn.apply(qkv, B, H, L, bias, None, True, Hkv, d)
+            ctx = _AttnFn.apply(qkv, B, H, L, bias, None, True, Hkv, d, key_start)
         return self.o_proj(ctx)
 
 
@@ -165,8 +172,8 @@ class LlamaDecoderLayer(tnn.Module):
         self.input_layernorm = RMSNorm(hidden, eps)
         self.post_attention_layernorm = RMSNorm(hidden, eps)
 
-    def forward(self, x, s, B, L, table, bias=None):
-        a = self.self_attn(x, B, L, table, bias)
+    def forward(self, x, s, B, L, table, bias=None, key_start=None):
+        a = self.self_attn(x, B, L, table, bias, key_start)
         x2, s2 = self.post_attention_layernorm.add_norm(a, residual=s)
         return self.mlp(x2), s2
 
@@ -186,10 +193,15 @@ class LlamaModel(tnn.Module):
         self.embed_tokens.weight._kml_storage_shape = (vp, hidden)
         self.embed_tokens.weight._kml_view = lambda st: st[:vocab, :hidden]
 
-    def forward(self, ids, attention_mask=None):
+    def forward(self, ids, attention_mask=None, doc_ids=None):
         B, L = ids.shape
         if L > self.max_pos:
             raise ValueError(f"sequence length {L} exceeds max_pos {self.max_pos}")
+        key_start = None
+        if doc_ids is not None:   # packed rows: every layer's attention stays inside a document
+            if doc_ids.shape != ids.shape:
+                raise ValueError(f"doc_ids {tuple(doc_ids.shape)} must have the shape of ids {tuple(ids.shape)}")
+            key_start = doc_key_start(doc_ids)
         bias = None
         if attention_mask is not None:
             bias = ((1.0 - attention_mask.float()) * -10000.0).reshape(B, L).contiguous()
@@ -203,7 +215,7 @@ class LlamaModel(tnn.Module):
         x, s = self.layers[0].input_layernorm.add_norm(e)
         closers = [lay.input_layernorm for lay in self.layers[1:]] + [self.norm]
         for lay, norm in zip(self.layers, closers):
-            m, s = lay(x, s, B, L, self.rope_table, bias)
+            m, s = lay(x, s, B, L, self.rope_table, bias, key_start)
             x, s = norm.add_norm(m, residual=s)
         return x
 
@@ -281,13 +293,23 @@ class LlamaForCausalLM(DecodeMixin, tnn.Module):
                 and prefix + "model.embed_tokens.weight" in sd:
             sd[prefix + "lm_head.weight"] = sd[prefix + "model.embed_tokens.weight"]
 
-    def forward(self, ids, attention_mask=None, labels=None, return_correct=False):
+    def forward(self, ids, attention_mask=None, labels=None, return_correct=False, doc_ids=None):
         """ids [B, L]; labels [B, L] (may be ``ids`` itself): position t is scored against
         labels[:, t + 1], the last position of every sequence is ignored.  Returns logits
-        ``[B*L, vocab]``, or the mean loss (and the correct count) when labels are given."""
-        z = self.model(ids, attention_mask)
+        ``[B*L, vocab]``, or the mean loss (and the correct count) when labels are given.
+
+        doc_ids int [B, L]: rows packed from several documents (``nn.transformer.pack_documents``),
+        constant within a document and changing at each boundary.  A token then attends its own
+        document only (the band attention kernels, ``key_start`` = the row at which its document
+        starts; rotary positions stay the row's, which gives the scores of positions restarted at 0),
+        and the last token of a document is not scored against the first token of the next."""
+        z = self.model(ids, attention_mask, doc_ids)
         if labels is None:
             return self.lm_head(z)
+        if doc_ids is not None:   # a document's first token is nobody's target
+            first = torch.zeros_like(doc_ids, dtype=torch.bool)
+            first[:, 1:] = doc_ids[:, 1:] != doc_ids[:, :-1]
+            labels = labels.masked_fill(first, -100)
         if ids.is_cuda:
             from ..ops import transformer as T
             tgt = T.lm_shift_labels(labels, -100)

@@ -11,6 +11,8 @@ fp32 stock-torch path on CPU with identical parameters / ``state_dict`` names).
 * :class:`RMSNorm`, :func:`rope`, :func:`swiglu` — the Llama block's norm (fused residual add),
   rotary embedding (in place on the fused QKV buffer) and gated SiLU (csrc/kernels/llama.hip);
   ``_AttnFn`` / :func:`attention_reference` take ``kv_heads`` for grouped-query attention
+* :func:`pack_documents`, :func:`doc_key_start` — rows packed from several documents and the
+  ``key_start`` operand that keeps causal attention inside each of them
 """
 from __future__ import annotations
 
@@ -250,13 +252,14 @@ def _split_qkv(qkv, H, kv_heads, head_dim=64):
 
 class _AttnFn(Function):
     @staticmethod
-    def forward(ctx, qkv, B, H, L, bias, drop=None, causal=False, kv_heads=None, head_dim=64):
+    def forward(ctx, qkv, B, H, L, bias, drop=None, causal=False, kv_heads=None, head_dim=64, key_start=None):
         from ..ops import transformer as T
         q, k, v = _split_qkv(qkv, H, kv_heads, head_dim)
         keep = T.attn_keep_buffer(B, H, L, qkv.device) if drop is not None and drop[2] > 0.0 else None
         out, lse = T.attn_fwd(q, k, v, B, H, L, bias=bias, drop=drop, keep=keep, causal=causal, kv_heads=kv_heads,
-                              head_dim=head_dim)
+                              head_dim=head_dim, key_start=key_start)
         ctx.save = (qkv, out, lse, bias, keep)
+        ctx.key_start = key_start
         ctx.dims = (B, H, L, kv_heads, head_dim)
         ctx.drop = drop
         ctx.causal = causal
@@ -271,17 +274,19 @@ class _AttnFn(Function):
         q, k, v = _split_qkv(qkv, H, kv_heads, head_dim)
         dq, dk, dv = _split_qkv(dqkv, H, kv_heads, head_dim)
         T.attn_bwd(q, k, v, out, _bf(dout).contiguous(), lse, B, H, L, bias=bias, dq=dq, dk=dk, dv=dv, drop=ctx.drop,
-                   keep=keep, causal=ctx.causal, kv_heads=kv_heads, head_dim=head_dim)
+                   keep=keep, causal=ctx.causal, kv_heads=kv_heads, head_dim=head_dim, key_start=ctx.key_start)
         ctx.save = None
-        return dqkv, None, None, None, None, None, None, None, None
+        return dqkv, None, None, None, None, None, None, None, None, None
 
 
-def attention_reference(qkv, B, H, L, bias=None, keep=None, causal=False, kv_heads=None, head_dim=64):
+def attention_reference(qkv, B, H, L, bias=None, keep=None, causal=False, kv_heads=None, head_dim=64,
+                        key_start=None):
     """fp32 torch attention on a fused [B*L, 3*H*64] buffer (CPU path / tests); keep:
     optional [B, H, L, L] dropout multiplier (0 or 1/(1-p)) applied to the probabilities;
     causal: lower-triangular mask (query t attends keys <= t); kv_heads: grouped-query attention
     on a [B*L, (H + 2 kv_heads)*64] buffer (query head h reads K/V head h // (H // kv_heads));
-    head_dim: the columns of a head (64, or 128 with scale 1/sqrt(128))."""
+    head_dim: the columns of a head (64, or 128 with scale 1/sqrt(128)); key_start: int ``[B, L]``,
+    query t also masks the keys before ``key_start[b, t]`` (with ``causal``: packed documents)."""
     D = H * head_dim
     Hkv = H if kv_heads is None else kv_heads
     q, k, v = (t.reshape(B, L, -1, head_dim).permute(0, 2, 1, 3) for t in _split_qkv(qkv, H, kv_heads, head_dim))
@@ -292,6 +297,9 @@ def attention_reference(qkv, B, H, L, bias=None, keep=None, causal=False, kv_hea
         s = s + bias.view(B, 1, 1, L)
     if causal:
         s = s.masked_fill(torch.ones(L, L, dtype=torch.bool, device=s.device).triu(1), float("-inf"))
+    if key_start is not None:
+        before = torch.arange(L, device=s.device).view(1, 1, L) < key_start.view(B, L, 1)   # [b, query, key]
+        s = s.masked_fill(before.view(B, 1, L, L), float("-inf"))
     pr = s.softmax(-1)
     if keep is not None:
         pr = pr * keep
@@ -303,6 +311,48 @@ def attention_reference_dropout(qkv, B, H, L, bias, p, causal=False):
     """CPU attention with probability dropout (torch RNG; same semantics as the kernel)."""
     keep = (torch.rand(B, H, L, L) >= p).float() / (1.0 - p)
     return attention_reference(qkv, B, H, L, bias, keep=keep, causal=causal)
+
+
+def doc_key_start(doc_ids):
+    """``key_start`` of packed rows: doc_ids int ``[B, L]``, constant within a document and changing
+    at every boundary; returns int32 ``[B, L]``, the row position at which each token's document
+    starts — the running maximum of the boundary positions, so non-decreasing and ``<= t`` by
+    construction.  Torch ops on the ids' device (no host sync: usable inside a captured step)."""
+    if doc_ids.dim() != 2 or doc_ids.is_floating_point():
+        raise ValueError(f"doc_key_start: integer [B, L] document ids, got {doc_ids.dtype} {tuple(doc_ids.shape)}")
+    pos = torch.arange(doc_ids.shape[1], device=doc_ids.device).expand_as(doc_ids)
+    first = torch.ones_like(doc_ids, dtype=torch.bool)
+    first[:, 1:] = doc_ids[:, 1:] != doc_ids[:, :-1]
+    return torch.where(first, pos, torch.zeros_like(pos)).cummax(1).values.to(torch.int32).contiguous()
+
+
+def pack_documents(docs, L, pad_id=0):
+    """Greedily pack 1-d token-id tensors into rows of ``L`` (host helper): a document goes into the
+    current row if it still fits, else the row is padded and a new one opened; a document longer than
+    ``L`` is cut into separate documents of at most ``L`` tokens.  Returns int64 ``[R, L]`` tensors
+    ``(ids, attention_mask, doc_ids)``: doc_ids numbers a row's documents from 0 and the padding, one
+    trailing document of its own, with the next number; feed them to ``LlamaForCausalLM.forward``."""
+    if L < 1:
+        raise ValueError("pack_documents: L must be positive")
+    pieces = [p for d in docs for p in torch.as_tensor(d).reshape(-1).long().split(L) if p.numel()]
+    rows = [[]]
+    for p in pieces:
+        if sum(x.numel() for x in rows[-1]) + p.numel() > L:
+            rows.append([])
+        rows[-1].append(p)
+    R = len(rows)
+    ids = torch.full((R, L), pad_id, dtype=torch.int64)
+    mask = torch.zeros((R, L), dtype=torch.int64)
+    doc = torch.zeros((R, L), dtype=torch.int64)
+    for r, row in enumerate(rows):
+        t = 0
+        for i, p in enumerate(row):
+            ids[r, t:t + p.numel()] = p
+            doc[r, t:t + p.numel()] = i
+            t += p.numel()
+        mask[r, :t] = 1
+        doc[r, t:] = len(row)
+    return ids, mask, doc
 
 
 class SelfAttention(tnn.Module):

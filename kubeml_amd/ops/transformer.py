@@ -73,8 +73,22 @@ def _head_dim(head_dim, drop):
     return head_dim
 
 
+def _key_start(key_start, B, L, causal, kv_heads, drop):
+    """The ``key_start`` operand of the band kernels: int32 ``[B, L]`` contiguous on the GPU, with
+    ``causal=True``, ``kv_heads`` given (``kv_heads=H`` for plain multi-head) and no dropout."""
+    if not causal or kv_heads is None:
+        raise ValueError("key_start needs causal=True and kv_heads (kv_heads=H for one K/V head per query head)")
+    if drop is not None and drop[2] > 0.0:
+        raise ValueError("key_start with attention dropout is not implemented")
+    if not torch.is_tensor(key_start) or key_start.dtype != torch.int32:
+        raise ValueError(f"key_start: expected an int32 tensor, got {getattr(key_start, 'dtype', type(key_start))}")
+    if not key_start.is_cuda or tuple(key_start.shape) != (B, L) or not key_start.is_contiguous():
+        raise ValueError(f"key_start: expected a contiguous GPU [{B}, {L}] tensor, got {tuple(key_start.shape)}")
+    return key_start.data_ptr()
+
+
 def attn_fwd(q, k, v, B, H, L, bias=None, out=None, scale=None, drop=None, keep=None, causal=False, kv_heads=None,
-             head_dim=64):
+             head_dim=64, key_start=None):
     """q/k/v: [B*L, ld] bf16 views with head h at columns 64h..64h+63 (may be column
     slices of one fused QKV buffer).  kv_heads: grouped-query attention — k / v hold ``kv_heads``
     heads and query head h reads K/V head ``h // (H // kv_heads)`` (None: H heads, the plain entry
@@ -82,9 +96,14 @@ def attn_fwd(q, k, v, B, H, L, bias=None, out=None, scale=None, drop=None, keep=
     keep: optional :func:`attn_keep_buffer` that receives the dropout keep bits, so
     :func:`attn_bwd` reads them instead of re-hashing.  causal: query t attends keys <= t only
     (the key tiles above the diagonal are skipped).  head_dim: 64, or 128 (head h at columns
-    128h..128h+127; ``kml_attn128_fwd``, no dropout).  Returns (out [B*L, H*head_dim], lse [B*H, L])."""
+    128h..128h+127; ``kml_attn128_fwd``, no dropout).  key_start: int32 ``[B, L]`` on the GPU —
+    query t attends keys ``key_start[b, t] .. t`` only (``0 <= key_start[b, t] <= t``, non-decreasing
+    in t: the row at which t's document starts in a packed batch, ``nn.transformer.doc_key_start``,
+    or ``max(0, t - W + 1)`` for a window); the key tiles before it are skipped.  Needs ``causal``,
+    ``kv_heads`` and no dropout.  Returns (out [B*L, H*head_dim], lse [B*H, L])."""
     Hkv = _kv_heads(H, kv_heads)
     D = _head_dim(head_dim, drop)
+    ks = None if key_start is None else _key_start(key_start, B, L, causal, kv_heads, drop)
     for n, t, hh in (("q", q, H), ("k", k, Hkv), ("v", v, Hkv)):
         _chk_view(t, n)
         if t.shape[0] != B * L or t.shape[1] < hh * D:
@@ -98,6 +117,11 @@ def attn_fwd(q, k, v, B, H, L, bias=None, out=None, scale=None, drop=None, keep=
     lse = torch.empty((B * H, L), dtype=F32, device=q.device)
     scale = 1.0 / math.sqrt(D) if scale is None else scale
     c, salt, pd = _drop_args(drop)
+    if ks is not None:
+        HIP.call("kml_attn128_band_fwd" if D == 128 else "kml_attn_gqa_band_fwd", "p p p p p p p i i i i i i i i f s",
+                 _p(q), _p(k), _p(v), _p(out), _p(lse), _p(bias), ks, q.stride(0), k.stride(0), v.stride(0),
+                 out.stride(0), B, H, Hkv, L, float(scale), _s())
+        return out, lse
     if D == 128:
         HIP.call("kml_attn128_fwd", "p p p p p p i i i i i i i i f p i f p i s",
                  _p(q), _p(k), _p(v), _p(out), _p(lse), _p(bias), q.stride(0), k.stride(0), v.stride(0),
@@ -116,10 +140,10 @@ def attn_fwd(q, k, v, B, H, L, bias=None, out=None, scale=None, drop=None, keep=
 
 
 def attn_bwd(q, k, v, o, dout, lse, B, H, L, bias=None, dq=None, dk=None, dv=None, scale=None, drop=None,
-             keep=None, causal=False, kv_heads=None, head_dim=64):
+             keep=None, causal=False, kv_heads=None, head_dim=64, key_start=None):
     """Gradients of attention; dq/dk/dv may be column views of one [B*L, 3*H*64] buffer.
     keep: the keep-bit buffer the forward filled (same drop), or None to re-hash the mask;
-    causal, kv_heads, head_dim: as given to :func:`attn_fwd`.  Grouped-query: dk / dv have
+    causal, kv_heads, head_dim, key_start: as given to :func:`attn_fwd`.  Grouped-query: dk / dv have
     ``kv_heads * head_dim`` columns, each head the sum over its group of query heads (fp32
     accumulators, fixed order)."""
     dev = q.device
@@ -141,6 +165,14 @@ def attn_bwd(q, k, v, o, dout, lse, B, H, L, bias=None, dq=None, dk=None, dv=Non
     dsum = torch.empty((B * H, L), dtype=F32, device=dev)
     scale = 1.0 / math.sqrt(D) if scale is None else scale
     c, salt, pd = _drop_args(drop)
+    if key_start is not None:
+        ks = _key_start(key_start, B, L, causal, kv_heads, drop)
+        HIP.call("kml_attn128_band_bwd" if D == 128 else "kml_attn_gqa_band_bwd",
+                 "p p p p p p p p p p p p i i i i i i i i i i i i f s",
+                 _p(q), _p(k), _p(v), _p(o), _p(dout), _p(lse), _p(dsum), _p(bias), ks, _p(dq), _p(dk), _p(dv),
+                 q.stride(0), k.stride(0), v.stride(0), o.stride(0), dout.stride(0), dq.stride(0), dk.stride(0),
+                 dv.stride(0), B, H, Hkv, L, float(scale), _s())
+        return dq, dk, dv
     if D == 128:
         HIP.call("kml_attn128_bwd", "p p p p p p p p p p p i i i i i i i i i i i i f p i f p i s",
                  _p(q), _p(k), _p(v), _p(o), _p(dout), _p(lse), _p(dsum), _p(bias), _p(dq), _p(dk), _p(dv),

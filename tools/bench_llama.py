@@ -22,6 +22,10 @@ call and the backward call (dQ and dKV launches; their split again from the kern
 Hkv = 4, D = 128, taking turns in one loop with the D = 64 kernels at H = 32, Hkv = 8 (the same
 FLOPs and bytes) and with ``torch.nn.functional.scaled_dot_product_attention`` on the D = 128
 operands (K/V heads repeated beforehand), and RoPE at 128 forward / backward; median and range.
+
+``--docs N [N ...]`` times only the attention forward and backward calls with ``key_start`` (rows
+packed from N equal documents; the band kernels) beside the plain causal calls on the same operands,
+at the head dim of ``--head-dim``: ``python tools/bench_llama.py --docs 1 4 16 [--head-dim 128]``.
 """
 import argparse
 import json
@@ -144,6 +148,37 @@ def bench_kernels128(a, torch):
                       **out}), flush=True)
 
 
+def bench_docs(a, torch):
+    """the band attention calls (key_start of N equal documents a row, for every N of --docs) beside
+    the plain causal calls on the same operands, all taking turns in one loop; median and range"""
+    from kubeml_amd.nn.transformer import _split_qkv, doc_key_start
+    from kubeml_amd.ops import transformer as T
+    dev = torch.device("cuda", 0)
+    D, cfg = a.head_dim, CFG128 if a.head_dim == 128 else CFG
+    B, L, H, Hkv = a.batch, a.seq, cfg["heads"], cfg["kv_heads"]
+    g = torch.Generator(device=dev).manual_seed(2)
+    rnd = lambda *s: torch.randn(*s, device=dev, generator=g).to(torch.bfloat16)
+    buf, dout = rnd(B * L, (H + 2 * Hkv) * D) * 0.5, rnd(B * L, H * D)
+    q, k, v = _split_qkv(buf, H, Hkv, D)
+    dq, dk, dv = _split_qkv(torch.empty_like(buf), H, Hkv, D)
+    kw = dict(causal=True, kv_heads=Hkv, head_dim=D)
+    runs = {}
+    for n in [0] + a.docs:   # 0: no key_start, the plain causal kernels
+        ks = None
+        if n:
+            ks = doc_key_start((torch.arange(L, device=dev) * n // L).expand(B, L))
+        o, lse = T.attn_fwd(q, k, v, B, H, L, key_start=ks, **kw)
+        name = f"docs{n}" if n else "causal"
+        runs[name + "_fwd"] = lambda ks=ks: T.attn_fwd(q, k, v, B, H, L, key_start=ks, **kw)
+        runs[name + "_bwd"] = lambda ks=ks, o=o, lse=lse: T.attn_bwd(q, k, v, o, dout, lse, B, H, L, dq=dq, dk=dk,
+                                                                     dv=dv, key_start=ks, **kw)
+    out = {"batch": B, "seq": L, "reps": a.reps, "head_dim": D, "heads": [H, Hkv]}
+    for n, (med, lo, hi) in zip(runs, _time_alternating(torch, list(runs.values()), a.reps, spread=True)):
+        out[n] = {"call_ms": round(med, 4), "min_ms": round(lo, 4), "max_ms": round(hi, 4)}
+    print(json.dumps({"metric": "band attention calls, N equal documents a row (device events around one call; "
+                                "median, range)", **out}), flush=True)
+
+
 def bench_kernels(a, torch):
     from kubeml_amd.nn.transformer import _split_qkv, rope_table
     from kubeml_amd.ops import transformer as T
@@ -208,12 +243,15 @@ def main():
     ap.add_argument("--no-step", action="store_true")
     ap.add_argument("--no-kernels", action="store_true")
     ap.add_argument("--head-dim", type=int, default=64, choices=(64, 128))
+    ap.add_argument("--docs", type=int, nargs="+", default=[], metavar="N")
     a = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("bench_llama.py needs a GPU")
     torch.cuda.set_device(0)
     torch.manual_seed(0)
+    if a.docs:   # the packed-document attention calls alone
+        return bench_docs(a, torch)
     if not a.no_kernels:
         (bench_kernels128 if a.head_dim == 128 else bench_kernels)(a, torch)
     if not a.no_step:
