@@ -20,6 +20,10 @@
 //                        head once and the query heads of the group take turns against it
 //   kml_gemm_skinny_glu  silu(x · Wgᵀ) * (x · Wuᵀ): the skinny GEMM with two accumulators and the
 //                        gate in its epilogue
+//   weight-only int8 decode (Linear.quantize_small, DecodeMixin.quantize_decode_weights):
+//   kml_quant_rows_i8    bf16 weight rows -> int8 rows and one fp32 scale per row
+//   kml_gemm_skinny_w8 / kml_gemm_skinny_glu_w8   the two skinny GEMMs streaming int8 weights:
+//                        half the bytes, converted to bf16 in registers (exact), scaled after the fold
 // Sequence lengths, the sampling temperature, seed, step and eos live in device memory, so one
 // captured step replays for every token.  No float atomics anywhere: every reduction has a fixed
 // order (lane butterflies, wave order in LDS, chunk / split order in the fold).
@@ -431,6 +435,283 @@ __global__ __launch_bounds__(NW * 64) void k_gemm_skinny_glu(const bf16_t* __res
   auto finish = [&](int e, float gt, float uv) {
     const int m = e & 15, n = n0 + ((e & 63) >> 4) * 4 + (e >> 6);
     if (m >= M || n >= I) return;
+    y[(long long)m * ldy + n] = f2bf(gt * sigmoidf_fast(gt) * uv);
+  };
+  float* mine = ws + ((long long)nb * S + sp) * (2 * E);
+  for (int e = threadIdx.x; e < E; e += NT) {
+    float gt = red[0][0][e], uv = red[0][1][e];
+#pragma unroll
+    for (int k = 1; k < NW; ++k) {
+      gt += red[k][0][e];
+      uv += red[k][1][e];
+    }
+    if (S > 1) {
+      st_part(mine + e, gt);
+      st_part(mine + E + e, uv);
+    } else {
+      finish(e, gt, uv);
+    }
+  }
+  if (S == 1) return;
+  if (!last_block(cnt + nb, (unsigned)S, &sh_last)) return;
+  const float* p0 = ws + (long long)nb * S * (2 * E);
+  for (int e = threadIdx.x; e < E; e += NT) {
+    float gt = ld_part(p0 + e), uv = ld_part(p0 + E + e);
+    for (int s2 = 1; s2 < S; ++s2) {
+      gt += ld_part(p0 + (long long)s2 * (2 * E) + e);
+      uv += ld_part(p0 + (long long)s2 * (2 * E) + E + e);
+    }
+    finish(e, gt, uv);
+  }
+}
+
+// ===================================================================== weight-only int8 decode
+// A Linear's weight as int8 rows with one fp32 scale per output row (symmetric: w ~ q * scale[n],
+// |q| <= 127).  x stays bf16, the sums stay fp32: only the weight stream halves.
+
+// ------------------------------------------------------------------------------- row quantiser
+// One wave per row, four rows a block.  Pass 1: 16-byte loads of the bf16 row, the maximum of |w|
+// over the wave.  scale = amax / 127 (fp32 division).  Pass 2 (the row comes from L2): q =
+// clamp(rint(w / scale), -127, 127), round to nearest even, 8 bytes stored per lane.  The columns
+// K .. ldq - 1 of the int8 row (its padding to 16 bytes) are written as 0.  A row of zeros gives
+// scale 0 and q 0 without a division; -128 is never produced.
+__global__ __launch_bounds__(256) void k_quant_rows_i8(const bf16_t* __restrict__ w, int ldw,
+                                                       signed char* __restrict__ q, int ldq,
+                                                       float* __restrict__ scale, int N, int K) {
+  const int lane = threadIdx.x & 63, n = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (n >= N) return;   // wave-uniform
+  const bf16_t* row = w + (long long)n * ldw;
+  float amax = 0.f;
+  for (int c = lane * 8; c < K; c += 512) {
+    float f[8];
+    unpack8(*reinterpret_cast<const uint4*>(row + c), f);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) amax = fmaxf(amax, fabsf(f[k]));
+  }
+  amax = wave_max(amax);
+  const float sc = amax / 127.f;
+  if (lane == 0) scale[n] = sc;
+  signed char* qrow = q + (long long)n * ldq;
+  for (int c = lane * 8; c < ldq; c += 512) {   // ldq % 8 == 0
+    uint2 o = make_uint2(0u, 0u);
+    if (c < K && amax > 0.f) {
+      float f[8];
+      unpack8(*reinterpret_cast<const uint4*>(row + c), f);
+      unsigned b[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        const float t = fminf(fmaxf(rintf(f[k] / sc), -127.f), 127.f);   // NaN -> -127 by fmaxf: finite anyway
+        b[k] = (unsigned)(int)t & 0xffu;
+      }
+      o.x = b[0] | (b[1] << 8) | (b[2] << 16) | (b[3] << 24);
+      o.y = b[4] | (b[5] << 8) | (b[6] << 16) | (b[7] << 24);
+    }
+    *reinterpret_cast<uint2*>(qrow + c) = o;
+  }
+}
+
+// ------------------------------------------------------------------------- skinny GEMM, int8 weights
+// y[M <= 16][N] = act((x · qᵀ) * scale[n] + bias): k_gemm_skinny with the weight stream in int8.
+// grid (ceil(N / 16), S), NW waves; a block owns 16 weight rows and `cps` K chunks of 128, wave w
+// takes chunks w, w + NW, ...  A lane (r = lane & 15, g = lane >> 4) still reads 32 contiguous
+// bytes of weight row n0 + r per chunk — now 32 k values, k = 128 c + 32 g + 0 .. 31 — so a wave
+// instruction pair reads 128 contiguous bytes of each of its 16 rows, and beside them 64 bytes of
+// x row r at the same k.  Bytes 8 j .. 8 j + 7 become the weight fragment of MFMA j (j = 0 .. 3)
+// against x[k + 8 j .. k + 8 j + 7]: within one v_mfma_f32_16x16x32_bf16 group g supplies k slots
+// 8 g .. 8 g + 7 of both operands, so the k order is the same on both sides.
+//
+// int8 -> bf16 is exact (|q| <= 127 has 7 significant bits; bf16 keeps 8): the byte is converted
+// to fp32 and the upper halves of two fp32 are packed by one v_perm_b32.  The weight fragments are
+// integer-valued; the row scale multiplies the fp32 sum once, after the wave and split fold, so
+// the only inexact steps are the fp32 sums and the final rounding to bf16.
+// VALU budget: a CU streams ~10 weight bytes a clock at the HBM floor and issues 64 lane-ops a
+// clock (4 SIMDs x 16 lanes), 6.4 lane-ops per byte in all.  The conversion costs 1.5 per byte
+// (one sign-extending byte convert, v_cvt_f32_i32 with an SDWA byte select, and half a v_perm_b32)
+// — under a quarter of the issue slots; addressing and masks are per 16 bytes and add < 0.3.
+//
+// Tails: K % 8 == 0 is all that is promised, so a 16-byte weight load may end past K: it is then
+// replaced by an 8-byte load (or nothing), and the x fragments past K are zero.  Rows n0 + r >= N
+// and x rows >= M are zero.  The waves are summed in wave order through LDS and the splits by the
+// last block in split order, as in k_gemm_skinny; every order depends on (N, K) alone, so a row's
+// result depends on neither M nor the other rows.
+__device__ __forceinline__ unsigned i8x2_bf(unsigned d, int b) {   // bytes b, b + 1 of d as a bf16 pair
+  const float lo = (float)(int)(signed char)(d >> (8 * b)), hi = (float)(int)(signed char)(d >> (8 * b + 8));
+  return __builtin_amdgcn_perm(__float_as_uint(hi), __float_as_uint(lo), 0x07060302u);
+}
+__device__ __forceinline__ bf16x8_t i8x8_bf(unsigned d0, unsigned d1) {
+  typedef __attribute__((ext_vector_type(4))) unsigned u32x4_t;
+  const u32x4_t v = {i8x2_bf(d0, 0), i8x2_bf(d0, 2), i8x2_bf(d1, 0), i8x2_bf(d1, 2)};
+  return __builtin_bit_cast(bf16x8_t, v);
+}
+// 32 weight bytes at p covering k0 .. k0 + 31 of a row of K (K % 8 == 0) values, zero past K
+__device__ __forceinline__ void ld_w8(const signed char* p, int k0, int K, bool ok, uint4& a, uint4& b) {
+  a = b = make_uint4(0u, 0u, 0u, 0u);
+  if (!ok) return;
+  if (k0 + 16 <= K) a = *reinterpret_cast<const uint4*>(p);
+  else if (k0 < K) { const uint2 t = *reinterpret_cast<const uint2*>(p); a.x = t.x; a.y = t.y; }
+  if (k0 + 32 <= K) b = *reinterpret_cast<const uint4*>(p + 16);
+  else if (k0 + 16 < K) { const uint2 t = *reinterpret_cast<const uint2*>(p + 16); b.x = t.x; b.y = t.y; }
+}
+
+template <int NW, int U>
+__global__ __launch_bounds__(NW * 64) void k_gemm_skinny_w8(const bf16_t* __restrict__ x, int ldx,
+                                                            const signed char* __restrict__ w, int ldw,
+                                                            const float* __restrict__ scale,
+                                                            const float* __restrict__ bias, bf16_t* __restrict__ y,
+                                                            int ldy, int M, int N, int K, int cps, int act,
+                                                            float* __restrict__ ws, unsigned* __restrict__ cnt) {
+  constexpr int NT = NW * 64, E = 256;
+  __shared__ float red[NW][E];
+  __shared__ unsigned sh_last;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int r = lane & 15, g = lane >> 4;
+  const int nb = blockIdx.x, sp = blockIdx.y, S = gridDim.y;
+  const int n0 = nb * 16;
+  const int nk = (K + 127) >> 7;
+  const int c0 = sp * cps;
+  const int c1 = c0 + cps < nk ? c0 + cps : nk;
+  const bool xok = r < M, wok = n0 + r < N;
+  const signed char* wp = w + (long long)(wok ? n0 + r : 0) * ldw + g * 32;
+  const bf16_t* xp = x + (long long)(xok ? r : 0) * ldx + g * 32;
+  const bf16x8_t zero = {0, 0, 0, 0, 0, 0, 0, 0};
+  f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
+  for (int cb = c0 + wv; cb < c1; cb += NW * U) {
+    uint4 a[U][2];
+    bf16x8_t bq[U][4];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int c = cb + NW * u, k0 = c * 128 + g * 32;
+      ld_w8(wp + c * 128, k0, K, c < c1 && wok, a[u][0], a[u][1]);
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        bq[u][j] = c < c1 && xok && k0 + j * 8 < K ? *reinterpret_cast<const bf16x8_t*>(xp + c * 128 + j * 8) : zero;
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(i8x8_bf(a[u][h].x, a[u][h].y), bq[u][2 * h], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(i8x8_bf(a[u][h].z, a[u][h].w), bq[u][2 * h + 1], acc, 0, 0, 0);
+      }
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) red[wv][i * 64 + lane] = acc[i];
+  __syncthreads();
+  // element e = 64 i + lane of the block's 16 x 16 tile, as stored above
+  auto finish = [&](int e, float v) {
+    const int m = e & 15, n = n0 + ((e & 63) >> 4) * 4 + (e >> 6);
+    if (m >= M || n >= N) return;
+    v *= scale[n];
+    if (bias) v += bias[n];
+    if (act == SK_GELU) v = kml_gelu(v);
+    else if (act == SK_GELU_TANH) v = kml_gelu_tanh(v);
+    y[(long long)m * ldy + n] = f2bf(v);
+  };
+  float* mine = ws + ((long long)nb * S + sp) * E;
+  for (int e = threadIdx.x; e < E; e += NT) {
+    float v = red[0][e];
+#pragma unroll
+    for (int k = 1; k < NW; ++k) v += red[k][e];
+    if (S > 1) st_part(mine + e, v);
+    else finish(e, v);
+  }
+  if (S == 1) return;
+  if (!last_block(cnt + nb, (unsigned)S, &sh_last)) return;
+  const float* p0 = ws + (long long)nb * S * E;
+  for (int e = threadIdx.x; e < E; e += NT) {
+    float v = ld_part(p0 + e);
+    for (int s2 = 1; s2 < S; ++s2) v += ld_part(p0 + (long long)s2 * E + e);
+    finish(e, v);
+  }
+}
+
+// The plan of the int8 kernels, a function of (N, K) alone, in chunks of 128: skinny_plan's two
+// block shapes at the same N; below 96 row groups K is split until ~192 blocks stream, at least 6
+// chunks each — the K extent (768) of skinny_plan's 12, so a weight gets the split count it has in
+// bf16 and each block half the bytes.  splits > 0 overrides the split (tuning).
+static inline SkinnyPlan skinny_plan_w8(int N, int K, int splits) {
+  const int nk = (K + 127) / 128, n16 = (N + 15) / 16;
+  SkinnyPlan p;
+  p.big = n16 >= 2048;
+  int S = 1;
+  if (splits > 0) {
+    S = splits;
+  } else if (!p.big && n16 < 96) {
+    S = (192 + n16 - 1) / n16;
+    if (S > nk / 6) S = nk / 6;
+  }
+  if (S > nk) S = nk;
+  if (S < 1) S = 1;
+  p.cps = (nk + S - 1) / S;
+  p.S = (nk + p.cps - 1) / p.cps;
+  p.groups = n16;
+  return p;
+}
+
+// ------------------------------------------------------------- skinny GEMM, gated, int8 weights
+// h[M <= 16][I] = silu(g) * u, g = (x · Qgᵀ) * scale[n], u = (x · Quᵀ) * scale[I + n]; w = [2 I, K]
+// int8, gate rows first.  k_gemm_skinny_w8 with two accumulators as k_gemm_skinny_glu has them: a
+// wave loads its four x fragments of a chunk once and issues them against the gate slab and the up
+// slab.  Rows n0 + r >= I of the last group are masked in BOTH slabs.  Each sum is scaled by its
+// own row scale after the fold, then the gate is applied in fp32 — k_swiglu_fwd's expression — and
+// the product rounded once to bf16.  Plan: skinny_plan_w8(I, K).
+template <int NW, int U>
+__global__ __launch_bounds__(NW * 64) void k_gemm_skinny_glu_w8(const bf16_t* __restrict__ x, int ldx,
+                                                                const signed char* __restrict__ w, int ldw,
+                                                                const float* __restrict__ scale,
+                                                                bf16_t* __restrict__ y, int ldy, int M, int I, int K,
+                                                                int cps, float* __restrict__ ws,
+                                                                unsigned* __restrict__ cnt) {
+  constexpr int NT = NW * 64, E = 256;
+  __shared__ float red[NW][2][E];
+  __shared__ unsigned sh_last;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int r = lane & 15, g = lane >> 4;
+  const int nb = blockIdx.x, sp = blockIdx.y, S = gridDim.y;
+  const int n0 = nb * 16;
+  const int nk = (K + 127) >> 7;
+  const int c0 = sp * cps;
+  const int c1 = c0 + cps < nk ? c0 + cps : nk;
+  const bool xok = r < M, wok = n0 + r < I;
+  const signed char* gp = w + (long long)(wok ? n0 + r : 0) * ldw + g * 32;
+  const signed char* up = gp + (long long)I * ldw;
+  const bf16_t* xp = x + (long long)(xok ? r : 0) * ldx + g * 32;
+  const bf16x8_t zero = {0, 0, 0, 0, 0, 0, 0, 0};
+  f32x4_t accg = {0.f, 0.f, 0.f, 0.f}, accu = {0.f, 0.f, 0.f, 0.f};
+  for (int cb = c0 + wv; cb < c1; cb += NW * U) {
+    uint4 ag[U][2], au[U][2];
+    bf16x8_t bq[U][4];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int c = cb + NW * u, k0 = c * 128 + g * 32;
+      ld_w8(gp + c * 128, k0, K, c < c1 && wok, ag[u][0], ag[u][1]);
+      ld_w8(up + c * 128, k0, K, c < c1 && wok, au[u][0], au[u][1]);
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        bq[u][j] = c < c1 && xok && k0 + j * 8 < K ? *reinterpret_cast<const bf16x8_t*>(xp + c * 128 + j * 8) : zero;
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        accg = __builtin_amdgcn_mfma_f32_16x16x32_bf16(i8x8_bf(ag[u][h].x, ag[u][h].y), bq[u][2 * h], accg, 0, 0, 0);
+        accu = __builtin_amdgcn_mfma_f32_16x16x32_bf16(i8x8_bf(au[u][h].x, au[u][h].y), bq[u][2 * h], accu, 0, 0, 0);
+        accg = __builtin_amdgcn_mfma_f32_16x16x32_bf16(i8x8_bf(ag[u][h].z, ag[u][h].w), bq[u][2 * h + 1], accg, 0, 0, 0);
+        accu = __builtin_amdgcn_mfma_f32_16x16x32_bf16(i8x8_bf(au[u][h].z, au[u][h].w), bq[u][2 * h + 1], accu, 0, 0, 0);
+      }
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    red[wv][0][i * 64 + lane] = accg[i];
+    red[wv][1][i * 64 + lane] = accu[i];
+  }
+  __syncthreads();
+  // element e = 64 i + lane of a 16 x 16 tile, as stored above
+  auto finish = [&](int e, float gt, float uv) {
+    const int m = e & 15, n = n0 + ((e & 63) >> 4) * 4 + (e >> 6);
+    if (m >= M || n >= I) return;
+    gt *= scale[n];
+    uv *= scale[I + n];
     y[(long long)m * ldy + n] = f2bf(gt * sigmoidf_fast(gt) * uv);
   };
   float* mine = ws + ((long long)nb * S + sp) * (2 * E);
@@ -1371,6 +1652,71 @@ KML_API int kml_gemm_skinny_glu(const bf16_t* x, int ldx, const bf16_t* w, int l
   else
     hipLaunchKernelGGL((k_gemm_skinny_glu<16, 2>), grid, dim3(1024), 0, s, x, ldx, w, ldw, y, ldy, M, I, K, p.cps, ws,
                        cnt);
+  KML_LAUNCH_CHECK();
+}
+
+// w [N, K] bf16 rows ldw apart -> q [N, K] int8 rows ldq apart (ldq % 16 == 0; columns K .. ldq - 1 are
+// zeroed) and scale[N] fp32: symmetric, scale[n] = max |w[n, :]| / 127, q = rint(w / scale) in -127 .. 127
+KML_API int kml_quant_rows_i8(const bf16_t* w, int ldw, signed char* q, int ldq, float* scale, int N, int K,
+                              hipStream_t s) {
+  if (!w || !q || !scale || N < 1 || K < 8 || K % 8 || ldw % 8 || ldw < K || ldq % 16 || ldq < K)
+    return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_quant_rows_i8, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, w, ldw, q, ldq, scale, N, K);
+  KML_LAUNCH_CHECK();
+}
+
+// K splits kml_gemm_skinny_w8 takes for an (N, K) int8 weight by default (workspace and tickets as
+// kml_gemm_skinny_splits describes them)
+KML_API int kml_gemm_skinny_w8_splits(int N, int K) {
+  if (N < 1 || K < 8) return 0;
+  return skinny_plan_w8(N, K, 0).S;
+}
+
+// y[M <= 16][N] = act((x · wᵀ) * scale[n] + bias), w [N, K] int8 rows ldw apart (16-byte aligned rows)
+// splits: 0 = the default plan, > 0 = that many K splits (the tuning sweep)
+KML_API int kml_gemm_skinny_w8(const bf16_t* x, int ldx, const signed char* w, int ldw, const float* scale,
+                               const float* bias, bf16_t* y, int ldy, int M, int N, int K, int act, int splits,
+                               float* ws, unsigned* cnt, hipStream_t s) {
+  if (!x || !w || !scale || !y || M < 1 || M > 16 || N < 1 || K < 8 || K % 8 || ldx % 8 || ldw % 16 || ldx < K ||
+      ldw < K || ldy < N || (act != SK_NONE && act != SK_GELU && act != SK_GELU_TANH) || splits < 0)
+    return (int)hipErrorInvalidValue;
+  const SkinnyPlan p = skinny_plan_w8(N, K, splits);
+  if (p.S > 1 && (!ws || !cnt)) return (int)hipErrorInvalidValue;
+  if (p.S > 65535) return (int)hipErrorInvalidValue;
+  const dim3 grid((unsigned)p.groups, (unsigned)p.S);
+  if (p.big)
+    hipLaunchKernelGGL((k_gemm_skinny_w8<4, 4>), grid, dim3(256), 0, s, x, ldx, w, ldw, scale, bias, y, ldy, M, N, K,
+                       p.cps, act, ws, cnt);
+  else
+    hipLaunchKernelGGL((k_gemm_skinny_w8<16, 2>), grid, dim3(1024), 0, s, x, ldx, w, ldw, scale, bias, y, ldy, M, N,
+                       K, p.cps, act, ws, cnt);
+  KML_LAUNCH_CHECK();
+}
+
+// K splits kml_gemm_skinny_glu_w8 takes for an [2 I, K] int8 gate_up weight by default (512 floats of
+// workspace per (group, split), as kml_gemm_skinny_glu_splits describes)
+KML_API int kml_gemm_skinny_glu_w8_splits(int I, int K) {
+  if (I < 8 || K < 8) return 0;
+  return skinny_plan_w8(I, K, 0).S;
+}
+
+// y[M <= 16][I] = silu(g) * u, g = (x · w[:I]ᵀ) * scale[:I], u = (x · w[I:2I]ᵀ) * scale[I:2I]; w [2 I, K] int8
+KML_API int kml_gemm_skinny_glu_w8(const bf16_t* x, int ldx, const signed char* w, int ldw, const float* scale,
+                                   bf16_t* y, int ldy, int M, int I, int K, int splits, float* ws, unsigned* cnt,
+                                   hipStream_t s) {
+  if (!x || !w || !scale || !y || M < 1 || M > 16 || I < 8 || I % 8 || K < 8 || K % 8 || ldx % 8 || ldw % 16 ||
+      ldx < K || ldw < K || ldy < I || splits < 0)
+    return (int)hipErrorInvalidValue;
+  const SkinnyPlan p = skinny_plan_w8(I, K, splits);
+  if (p.S > 1 && (!ws || !cnt)) return (int)hipErrorInvalidValue;
+  if (p.S > 65535) return (int)hipErrorInvalidValue;
+  const dim3 grid((unsigned)p.groups, (unsigned)p.S);
+  if (p.big)
+    hipLaunchKernelGGL((k_gemm_skinny_glu_w8<4, 2>), grid, dim3(256), 0, s, x, ldx, w, ldw, scale, y, ldy, M, I, K,
+                       p.cps, ws, cnt);
+  else
+    hipLaunchKernelGGL((k_gemm_skinny_glu_w8<16, 2>), grid, dim3(1024), 0, s, x, ldx, w, ldw, scale, y, ldy, M, I,
+                       K, p.cps, ws, cnt);
   KML_LAUNCH_CHECK();
 }
 

@@ -454,7 +454,7 @@ class GPT2LMHeadModel(DecodeMixin, tnn.Module):
         """The GPU verify round as one captured graph per (cache, sampling, q), as :meth:`_replay`
         keeps the plain step: drafts, start, limit, seed, temperature and eos are device memory."""
         key = ("verify", bool(cache.sample), cache.draft_tokens + 1)
-        ent = cache._graphs.get(key)
+        ent = self._graphs_of(cache).get(key)
         if ent is None:
             from ..engine.step import capture_graph
             state = [cache.lens, cache.tokens, cache.next_ids, cache.finished, cache.stats]

@@ -146,7 +146,8 @@ class LlamaMLP(tnn.Module):
 
     def forward_small(self, x):
         """Inference-only forward for M <= 16 rows (a decode step): the gate / up GEMM with the
-        SwiGLU in its epilogue (``kml_gemm_skinny_glu``), then ``down_proj.forward_small``.  On the
+        SwiGLU in its epilogue (``kml_gemm_skinny_glu``; ``kml_gemm_skinny_glu_w8`` once ``gate_up``
+        holds an int8 copy, ``Linear.quantize_small``), then ``down_proj.forward_small``.  On the
         CPU the plain forward."""
         if not x.is_cuda:
             return self.forward(x)
@@ -156,7 +157,10 @@ class LlamaMLP(tnn.Module):
             x = _bf(x)
             if x.shape[1] != gu.in_pad:
                 x = _pad_nograd(x, gu.in_pad)
-            h = D.gemm_skinny_glu(x.contiguous(), shadow_of(gu.weight).view(gu.out_pad, gu.in_pad))
+            if gu._buffers.get("w8") is not None:   # Linear.quantize_small("int8")
+                h = D.gemm_skinny_glu_w8(x.contiguous(), gu.w8, gu.w8_scale)
+            else:
+                h = D.gemm_skinny_glu(x.contiguous(), shadow_of(gu.weight).view(gu.out_pad, gu.in_pad))
             return self.down_proj.forward_small(h)
 
 

@@ -331,12 +331,52 @@ class DecodeMixin:
             D.decode_advance(logits, self.vocab, cache.ctl, cache.temp, cache.next_ids, cache.tokens, cache.lens,
                              cache.finished, sample=cache.sample)
 
+    def quantize_decode_weights(self, dtype="int8"):
+        """Weight-only quantisation of the decode step: every :class:`~kubeml_amd.nn.Linear` the step
+        reaches (the attention and MLP projections and the output head, a tied one included) gets
+        an int8 copy of its current bf16 shadow weight with one fp32 scale per output row
+        (``Linear.quantize_small``), and ``forward_small`` — the captured step and the verify
+        round — streams that copy through the int8 skinny GEMMs.  Activations, sums, the token
+        gather, the prefill and training keep bf16.  ``dtype=None`` undoes it.
+
+        This is a speed feature: a step reads half the weight bytes.  The bf16 weights stay
+        resident, so memory grows by the int8 copies instead of shrinking.  The copies are a
+        snapshot: after training or ``load_state_dict`` call this again.  Needs a flattened model
+        on the GPU in eval mode (``ValueError`` otherwise: there is no int8 CPU path).  Every call
+        retires the captured steps, which hold weight addresses.  Returns the names of the layers
+        left in bf16: an input width that is no multiple of 16, or a shape at which the int8 kernel
+        measured slower (``nn.modules._SMALL_W8_SLOWER``: the 576-wide Llama's, whose step is
+        launch-bound, stays bf16 altogether)."""
+        from .modules import Linear
+        if dtype not in (None, "int8"):
+            raise ValueError(f"quantize_decode_weights: dtype {dtype!r} (\"int8\" or None)")
+        if dtype is not None:
+            if not self._decode_table.is_cuda:
+                raise ValueError("quantize_decode_weights: the int8 decode kernels are GPU only")
+            if getattr(self, "_kml_flat", None) is None or self.training:
+                raise ValueError("quantize_decode_weights: needs a flattened model (nn.flatten_module) in eval mode")
+        left = [name for name, m in self.named_modules() if isinstance(m, Linear) and not m.quantize_small(dtype)]
+        # a new stamp: no step captured before this call is replayed (_graphs_of), and generate's
+        # own caches go with their captures
+        self.__dict__["_kml_w8_stamp"] = self.__dict__.get("_kml_w8_stamp", 0) + 1
+        self.__dict__.get("_kml_decode_caches", {}).clear()
+        return left if dtype is not None else []
+
+    def _graphs_of(self, cache):
+        """``cache._graphs``, emptied first if its steps were captured under another quantisation
+        state of the model than the current one (they hold the addresses of the weights they read)."""
+        stamp = self.__dict__.get("_kml_w8_stamp", 0)
+        if getattr(cache, "_w8_stamp", 0) != stamp:
+            cache._graphs.clear()
+            cache._w8_stamp = stamp
+        return cache._graphs
+
     def _replay(self, cache, advance):
         """The GPU step as one captured graph per (cache, advance, sampling, filtered); captured
         on first use after an eager warm-up whose effect on the decode state is rolled back.  The
         filter parameters live in device memory: other values replay the same graph."""
         key = (bool(advance), bool(cache.sample), bool(cache.filtered))
-        ent = cache._graphs.get(key)
+        ent = self._graphs_of(cache).get(key)
         if ent is None:
             from ..engine.step import capture_graph
             state = [cache.lens, cache.tokens, cache.next_ids, cache.finished, cache.ctl]

@@ -364,7 +364,8 @@ class Linear(tnn.Module):
         kernel measured slower) and fused-ReLU layers take :meth:`forward` instead.  ``skinny``:
         ignore ``_SMALL_EXISTING`` and take the skinny GEMM at every row count up to 16 — a row of
         its result does not depend on the row count, which a verify round of the speculative
-        ``generate`` relies on."""
+        ``generate`` relies on.  After :meth:`quantize_small` the skinny GEMM is the int8-weight
+        one (``gemm_skinny_w8``), with the same row independence."""
         with torch.no_grad():
             rows = x.shape[0] if x.dim() == 2 else 0
             if (not _on_gpu(x) or self.fused_relu or
@@ -381,11 +382,42 @@ class Linear(tnn.Module):
             if x.shape[1] != self.in_pad:
                 x = _pad_nograd(x, self.in_pad)
             from ..ops import decode as D
-            w = shadow_of(self.weight).view(self.out_pad, self.in_pad)
-            y = D.gemm_skinny(x.contiguous(), w, None if self.bias is None else master_of(self.bias), act=act)
+            bias = None if self.bias is None else master_of(self.bias)
+            if self._buffers.get("w8") is not None:   # quantize_small("int8"): half the weight bytes
+                y = D.gemm_skinny_w8(x.contiguous(), self.w8, self.w8_scale, bias, act=act)
+            else:
+                w = shadow_of(self.weight).view(self.out_pad, self.in_pad)
+                y = D.gemm_skinny(x.contiguous(), w, bias, act=act)
             if self.out_pad != self.out_features and not keep_pad:
                 y = y[:, :self.out_features].contiguous()
             return y
+
+    def quantize_small(self, dtype: Optional[str] = "int8") -> bool:
+        """Give :meth:`forward_small` an int8 copy of the current bf16 shadow weight (``"int8"``:
+        symmetric, one fp32 scale per output row, ``ops.decode.quant_rows_i8``) or drop it
+        (``None``).  The copy lives in the non-persistent buffers ``w8`` (int8 ``[out_pad,
+        in_pad]``) and ``w8_scale`` (fp32 ``[out_pad]``): ``state_dict()`` does not change,
+        :meth:`forward` does not read them, and the bf16 weight stays resident.  It is a snapshot:
+        call again after the weight changes.  GPU only.  Returns whether the layer is quantised
+        afterwards: a fused-ReLU layer, an ``in_pad`` that is no multiple of 16 and the shapes of
+        ``_SMALL_W8_SLOWER`` (where the int8 kernel measured slower) stay bf16."""
+        if dtype not in (None, "int8"):
+            raise ValueError(f"quantize_small: dtype {dtype!r} (\"int8\" or None)")
+        for name in ("w8", "w8_scale"):
+            self._buffers.pop(name, None)
+            self._non_persistent_buffers_set.discard(name)
+        if dtype is None:
+            return False
+        if not self.weight.is_cuda:
+            raise ValueError("quantize_small: the int8 kernels are GPU only; move the layer to the GPU first")
+        if self.fused_relu or self.in_pad % 16 or (self.out_pad, self.in_pad) in _SMALL_W8_SLOWER:
+            return False
+        from ..ops import decode as D
+        with torch.no_grad():
+            q, scale = D.quant_rows_i8(shadow_of(self.weight).view(self.out_pad, self.in_pad))
+        self.register_buffer("w8", q, persistent=False)
+        self.register_buffer("w8_scale", scale, persistent=False)
+        return True
 
 
 # (out_pad, in_pad) -> fewest rows at which forward_small takes the existing route instead: where
@@ -393,6 +425,13 @@ class Linear(tnn.Module):
 # kernel wins at 1 and 4 rows and loses at 16 (x is re-read from L2 by 3142 blocks); 5 .. 15 rows
 # were not measured and go with 16.
 _SMALL_EXISTING: dict = {(50264, 768): 5}
+
+# (out_pad, in_pad) that quantize_small leaves in bf16: where the int8 skinny kernel measured slower
+# than the bf16 one at 1, 4 and 16 rows (profiles/r24/decode_w8.md: the 576-wide Llama's weights,
+# 0.3 - 0.7 us a launch behind at K = 576, level at best at K = 1536; such a launch is a few
+# microseconds of latency, not bytes, and a lane converts twice the k values before its sum is
+# ready).  From K = 2048 on the int8 kernel won every shape measured.
+_SMALL_W8_SLOWER: set = {(960, 576), (576, 576), (3072, 576), (576, 1536), (32000, 576)}
 
 
 # ======================================================================================

@@ -244,6 +244,107 @@ def gemm_skinny_glu(x, w, out=None, splits=None):
     return out
 
 
+# ------------------------------------------------------------------ weight-only int8 decode
+I8 = torch.int8
+
+
+def quant_rows_i8(w):
+    """Symmetric int8 copy of a bf16 weight ``w [N, K]`` (a row-major view, K a multiple of 8), one
+    fp32 scale per row: ``scale[n] = max|w[n, :]| / 127``, ``q = rint(w / scale)`` (to nearest even)
+    in -127 .. 127; a row of zeros gives scale 0 and q 0.  Returns ``(q, scale)``: q is an ``[N, K]``
+    int8 view whose rows start 16 bytes aligned (row stride K rounded up to 16, the padding zeroed),
+    which is what :func:`gemm_skinny_w8` reads."""
+    _chk_view(w, "w")
+    N, K = w.shape
+    if K % 8 or K < 8 or N < 1:
+        raise ValueError(f"quant_rows_i8: w {tuple(w.shape)} (K a multiple of 8)")
+    ld = -(-K // 16) * 16
+    q = torch.empty((N, ld), dtype=I8, device=w.device)
+    scale = torch.empty(N, dtype=F32, device=w.device)
+    HIP.call("kml_quant_rows_i8", "p i p i p i i s", _p(w), w.stride(0), _p(q), ld, _p(scale), N, K, _s())
+    return q[:, :K], scale
+
+
+def _chk_w8(wq, scale, name):
+    if wq.dtype != I8 or not wq.is_cuda or wq.dim() != 2 or wq.stride(1) != 1 or wq.stride(0) % 16 or wq.data_ptr() % 16:
+        raise ValueError(f"{name}: wq must be a row-major int8 GPU view with 16-byte aligned rows "
+                         f"(quant_rows_i8 gives one), got {wq.dtype} stride {tuple(wq.stride())}")
+    _chk(scale, F32, "scale", ndim=1)
+    if scale.numel() != wq.shape[0]:
+        raise ValueError(f"{name}: {scale.numel()} scales for {wq.shape[0]} weight rows")
+
+
+def gemm_skinny_w8(x, wq, scale, bias=None, act=None, out=None, splits=None):
+    """:func:`gemm_skinny` on an int8 weight: ``y[M, N] = act((x[M, K] @ wq[N, K]ᵀ) * scale + bias)``
+    for M <= 16, ``wq, scale`` from :func:`quant_rows_i8`.  x and y are bf16 and the sums fp32 as
+    there; the int8 values enter the matrix instruction as exact bf16 integers and the row scale
+    multiplies the finished fp32 sum, so the weight bytes halve and nothing else changes.  Row m of
+    the result does not depend on M or on the other rows.  ``splits``: another K split than the
+    kernel's plan for (N, K) (the tuning sweep only)."""
+    _chk_view(x, "x")
+    _chk_w8(wq, scale, "gemm_skinny_w8")
+    M, K = x.shape
+    N = wq.shape[0]
+    if not 1 <= M <= 16:
+        raise ValueError(f"gemm_skinny_w8: M = {M} rows; the skinny kernel takes 1..16")
+    if wq.shape[1] != K or K % 8 or K < 8:
+        raise ValueError(f"gemm_skinny_w8: x {tuple(x.shape)} vs wq {tuple(wq.shape)} (K a multiple of 8)")
+    if act not in _SKINNY_ACT:
+        raise ValueError(f"gemm_skinny_w8: act {act!r}")
+    if bias is not None:
+        _chk(bias, F32, "bias")
+        if bias.numel() < N:
+            raise ValueError("bias shorter than N")
+    if out is None:
+        out = torch.empty((M, N), dtype=BF16, device=x.device)
+    if out.dtype != BF16 or not out.is_cuda or out.dim() != 2 or out.stride(1) != 1 or out.shape != (M, N):
+        raise ValueError(f"out: expected a row-major bf16 [{M}, {N}] GPU view")
+    S = int(HIP.raw("kml_gemm_skinny_w8_splits", N, K)) if splits is None else int(splits)
+    if S < 1:
+        raise ValueError(f"gemm_skinny_w8: no plan for N = {N}, K = {K}" if splits is None else "splits must be >= 1")
+    ws = cnt = None
+    if S > 1:
+        groups = -(-N // 16)
+        ws = torch.empty(groups * S * 256, dtype=F32, device=x.device)
+        cnt = _COUNTERS.take(x.device, groups)
+    HIP.call("kml_gemm_skinny_w8", "p i p i p p p i i i i i i p p s", _p(x), x.stride(0), _p(wq), wq.stride(0),
+             _p(scale), _p(bias), _p(out), out.stride(0), M, N, K, _SKINNY_ACT[act], 0 if splits is None else S,
+             _p(ws), _p(cnt), _s())
+    return out
+
+
+def gemm_skinny_glu_w8(x, wq, scale, out=None, splits=None):
+    """:func:`gemm_skinny_glu` on the int8 ``gate_up`` weight ``wq [2*I, K]`` (gate rows first) with
+    its row scales: ``h = silu(g) * u``, ``g = (x @ wq[:I]ᵀ) * scale[:I]``, ``u = (x @ wq[I:]ᵀ) *
+    scale[I:]``, each scaled in fp32 before the gate, the product rounded once to bf16.  Row m of
+    the result does not depend on M or on the other rows."""
+    _chk_view(x, "x")
+    _chk_w8(wq, scale, "gemm_skinny_glu_w8")
+    M, K = x.shape
+    if not 1 <= M <= 16:
+        raise ValueError(f"gemm_skinny_glu_w8: M = {M} rows; the skinny kernel takes 1..16")
+    if wq.shape[1] != K or K % 8 or K < 8 or wq.shape[0] % 16 or wq.shape[0] < 16:
+        raise ValueError(f"gemm_skinny_glu_w8: x {tuple(x.shape)} vs wq {tuple(wq.shape)} (wq [2 I, K], I and K "
+                         "multiples of 8)")
+    I = wq.shape[0] // 2
+    if out is None:
+        out = torch.empty((M, I), dtype=BF16, device=x.device)
+    if out.dtype != BF16 or not out.is_cuda or out.dim() != 2 or out.stride(1) != 1 or out.shape != (M, I):
+        raise ValueError(f"out: expected a row-major bf16 [{M}, {I}] GPU view")
+    S = int(HIP.raw("kml_gemm_skinny_glu_w8_splits", I, K)) if splits is None else int(splits)
+    if S < 1:
+        raise ValueError(f"gemm_skinny_glu_w8: no plan for I = {I}, K = {K}" if splits is None
+                         else "splits must be >= 1")
+    ws = cnt = None
+    if S > 1:
+        groups = -(-I // 16)
+        ws = torch.empty(groups * S * 512, dtype=F32, device=x.device)
+        cnt = _COUNTERS.take(x.device, groups)
+    HIP.call("kml_gemm_skinny_glu_w8", "p i p i p p i i i i i p p s", _p(x), x.stride(0), _p(wq), wq.stride(0),
+             _p(scale), _p(out), out.stride(0), M, I, K, 0 if splits is None else S, _p(ws), _p(cnt), _s())
+    return out
+
+
 def embed2_at(ids, lens, word, pos, out=None):
     """out[b] = word[ids[b]] + pos[lens[b]] (bf16 tables; ids int64 [B], lens int32 [B])."""
     _chk(ids, I64, "ids", ndim=1)

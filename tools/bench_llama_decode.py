@@ -3,6 +3,18 @@
 launches it replaces.
 
     python tools/bench_llama_decode.py [--rounds 7] [--iters 20] [--new 256] [--skip-model] [--out FILE.json]
+                                       [--preset {576,tinyllama}] [--weights {bf16,int8}]
+
+``--preset tinyllama``: the TinyLlama-1.1B shape (hidden 2048, 32 heads / 4 K/V heads, inter 5632, 22
+layers, vocab 32000), random weights.  ``--weights int8``: only the weight-only int8 comparison —
+* w8: ``gemm_skinny_w8`` / ``gemm_skinny_glu_w8`` against the bf16 kernels on the preset's five weight
+  shapes, M in {1, 4, 16}, alternating; every launch reads the next of a ring of weight copies of more
+  than 320 MB per variant (past the 256 MB last-level cache).  ``floor_us``: the variant's weight bytes
+  over 6.3 TB/s — derived, not measured.
+* step: the captured step in bf16 and after ``quantize_decode_weights("int8")``, alternating, B in
+  {1, 4, 16}; ``floor_us`` / ``floor_us_int8``: the weight bytes a token reads, derived the same way.
+  Layers whose shape is in ``nn.modules._SMALL_W8_SLOWER`` (all of the 576 preset's) stay bf16 in the
+  step; the w8 section calls the kernels directly and measures them whatever the table says.
 
 * step: B in {1, 4, 16}, prompt 128, ``--new`` tokens: the captured step of ``generate``
   (``decode_step`` replays, timed between device events after the prefill) and the same step with
@@ -35,7 +47,11 @@ def main():
     ap.add_argument("--new", type=int, default=256)
     ap.add_argument("--skip-model", action="store_true")
     ap.add_argument("--out")
+    ap.add_argument("--preset", choices=("576", "tinyllama"), default="576")
+    ap.add_argument("--weights", choices=("bf16", "int8"), default="bf16")
     a = ap.parse_args()
+    cfg = {"576": dict(hidden=576, heads=9, kv_heads=3, inter=1536, layers=30, vocab=32000),
+           "tinyllama": dict(hidden=2048, heads=32, kv_heads=4, inter=5632, layers=22, vocab=32000)}[a.preset]
     import torch
     from kubeml_amd.engine.step import capture_graph
     from kubeml_amd.nn.transformer import rope_table
@@ -79,7 +95,10 @@ def main():
     def rnd(*shape):
         return torch.randn(*shape, device=dev, generator=gen).to(BF)
 
-    res = {"device": torch.cuda.get_device_name(0), "rounds": a.rounds, "iters": a.iters}
+    res = {"device": torch.cuda.get_device_name(0), "rounds": a.rounds, "iters": a.iters, "preset": a.preset,
+           "weights": a.weights}
+    if a.weights == "int8":
+        return w8_bench(a, cfg, res, torch, D, dev, graphed, alternate, rnd)
 
     # ---- the gated GEMM alone
     I, K, ring = 1536, 576, 20
@@ -144,7 +163,7 @@ def main():
         from kubeml_amd.nn import flatten_module
         from kubeml_amd.nn.flat import shadow_of
         torch.manual_seed(0)
-        model = LlamaForCausalLM().to(dev).eval()
+        model = LlamaForCausalLM(**cfg).to(dev).eval()
         flatten_module(model)
         wbytes = 2 * sum(p.numel() for n, p in model.named_parameters() if "embed_tokens" not in n)
         res["floor_us"] = round(wbytes / 6.3e12 * 1e6, 2)
@@ -157,7 +176,7 @@ def main():
         prompt, new = 128, a.new
         res["step"] = []
         for B in (1, 4, 16):
-            ids = torch.randint(0, 32000, (B, prompt), device=dev, generator=gen)
+            ids = torch.randint(0, cfg["vocab"], (B, prompt), device=dev, generator=gen)
             caches = {}
             for name, fs in (("step", fused_small), ("mlp_unfused", unfused_small)):
                 LlamaMLP.forward_small = fs
@@ -192,11 +211,83 @@ def main():
             res["step"].append(row)
             print(json.dumps(row), file=sys.stderr, flush=True)
 
+    finish(a, res)
+
+
+def finish(a, res):
     line = json.dumps(res)
     print(line)
     if a.out:
         with open(a.out, "w") as f:
             f.write(line + "\n")
+
+
+def w8_bench(a, cfg, res, torch, D, dev, graphed, alternate, rnd):
+    """``--weights int8``: bf16 against int8, single GEMMs and the captured step."""
+    BF = torch.bfloat16
+    hid, inter, hd = cfg["hidden"], cfg["inter"], 64
+    shapes = [("qkv", (cfg["heads"] + 2 * cfg["kv_heads"]) * hd, hid, False), ("o_proj", hid, hid, False),
+              ("gate_up", 2 * inter, hid, True), ("down_proj", hid, inter, False), ("lm_head", cfg["vocab"], hid, False)]
+    res["w8"] = []
+    for name, N, K, glu in shapes:
+        ring = max(a.iters, -(-320 * 2 ** 20 // (N * K)))   # int8 copies of N*K bytes: > 320 MB; bf16: twice that
+        wb = [rnd(N, K) * 0.05 for _ in range(ring)]
+        wq = [D.quant_rows_i8(w) for w in wb]
+        for M in (1, 4, 16):
+            x = rnd(M, K)
+            o = torch.empty(M, N // 2 if glu else N, dtype=BF, device=dev)
+
+            def bf16():
+                for w in wb:
+                    (D.gemm_skinny_glu if glu else D.gemm_skinny)(x, w, out=o)
+
+            def int8():
+                for q, sc in wq:
+                    (D.gemm_skinny_glu_w8(x, q, sc, out=o) if glu else D.gemm_skinny_w8(x, q, sc, out=o))
+            row = {"layer": name, "N": N, "K": K, "M": M, "ring": ring,
+                   "floor_us": {"bf16": round(2 * N * K / 6.3e6, 3), "int8": round(N * K / 6.3e6, 3)},
+                   **alternate({"bf16": graphed(bf16), "int8": graphed(int8)}, ring)}
+            res["w8"].append(row)
+            print(json.dumps(row), file=sys.stderr, flush=True)
+        del wb, wq
+        torch.cuda.empty_cache()
+    if not a.skip_model:
+        from kubeml_amd.models.llama import LlamaForCausalLM
+        from kubeml_amd.nn import flatten_module
+        torch.manual_seed(0)
+        model = LlamaForCausalLM(**cfg).to(dev).eval()
+        flatten_module(model)
+        wbytes = sum(p.numel() for n, p in model.named_parameters() if "embed_tokens" not in n)
+        res["floor_us"], res["floor_us_int8"] = round(2 * wbytes / 6.3e6, 2), round(wbytes / 6.3e6, 2)
+        prompt, new = 128, a.new
+        res["step"] = []
+        for B in (1, 4, 16):
+            ids = torch.randint(0, cfg["vocab"], (B, prompt), device=dev)
+            c = model.new_cache(B, prompt + new, dev)
+            times = {"bf16": [], "int8": []}
+            for _ in range(a.rounds + 1):   # the first round is a warm-up and is dropped
+                for k in times:
+                    # switching retires the captured step: the untimed decode_step below captures this variant's
+                    model.quantize_decode_weights(None if k == "bf16" else "int8")
+                    c.reset()
+                    model.prefill(ids, None, c)
+                    model.decode_step(c)
+                    torch.cuda.synchronize()
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    for _ in range(new - 2):
+                        model.decode_step(c)
+                    e1.record()
+                    e1.synchronize()
+                    times[k].append(e0.elapsed_time(e1) * 1e3 / (new - 2))
+            row = {"B": B}
+            for k, v in times.items():
+                us = statistics.median(v[1:])
+                row[k] = {"us": round(us, 2), "min": round(min(v[1:]), 2), "max": round(max(v[1:]), 2),
+                          "tokens_per_s": round(B / us * 1e6, 1)}
+            res["step"].append(row)
+            print(json.dumps(row), file=sys.stderr, flush=True)
+    finish(a, res)
 
 
 if __name__ == "__main__":
